@@ -9,6 +9,8 @@ One "step" = one learner ROUND over one batch of synthetic rollouts (SURVEY.md Â
 value = (n_gpus * W * T) / t_round  [samples/s], inputs resident in HBM before timing.
 
     python bench.py                       # N=1, config C2: 1 worker x 128 steps, 288x288, fp32
+    python bench.py --full                # + nested C3 section, latent-cache / direct-conv / stem rounds, rooflines, peaks, CPU baseline
+    python bench.py --dump-outputs DIR    # + what the last timed round computed, as DIR/<name>.npy
     python bench.py --gpus N              # N ranks: the parent (no GPU call) starts one child per GPU and relays the line
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
@@ -387,9 +389,42 @@ def roofline_of(prof, steps):
     return dom, r
 
 
-def run_config(name, args, rank, local_rank, world, use_dist, steps, warmup, episodes_dir=None, dedup=None, section=None):
+DUMP_PARAMS_SAMPLE = 1 << 22       # parameter entries written by --dump-outputs (16 MB; the arena holds ~20 M)
+DUMP_SEED = 20240607
+
+
+def dump_outputs(dump_dir, agent, workers, dev_l):
+    """--dump-outputs: what the last timed round handed its caller â€” the per-minibatch losses, the parameters after the
+    round's last Adam step (a fixed, seeded sample of the arena), the encoder features written into the rollout storages and
+    the returns / advantages of both heads â€” as DIR/<name>.npy in float32 (< 64 MB in all)."""
+    os.makedirs(dump_dir, exist_ok=True)
+    params = agent.arena.params
+    n = params.numel()
+    if n > DUMP_PARAMS_SAMPLE:
+        idx = np.sort(np.random.RandomState(DUMP_SEED).choice(n, DUMP_PARAMS_SAMPLE, replace=False))
+        params = params[torch.from_numpy(idx).to(params.device)]
+    arrays = {
+        "losses": torch.as_tensor(dev_l, dtype=torch.float32),
+        "params_sample": params,
+        "features": torch.stack([wk.stor[0].obs for wk in workers]),
+        "returns": torch.stack([torch.stack([s.returns for s in wk.stor]) for wk in workers]),
+        "advantages": torch.stack([torch.stack([s.advantages for s in wk.stor]) for wk in workers]),
+    }
+    total = 0
+    for k, v in arrays.items():
+        a = v.detach().float().cpu().numpy()
+        total += a.nbytes
+        np.save(os.path.join(dump_dir, k + ".npy"), a)
+    assert total <= 64 << 20, total
+    log("[bench] outputs of the last timed round written to %s (%s; %.1f MB)" % (dump_dir, ", ".join(arrays), total / 2**20))
+
+
+def run_config(name, args, rank, local_rank, world, use_dist, steps, warmup, episodes_dir=None, dedup=None, section=None,
+               dump_dir=None):
     """Build the agent + workers of BASELINE config `name`, warm up, time `steps` learner rounds (barrier +
-    synchronize on both sides, MAX over ranks) and return the result dict (rank 0) plus what cpu_baseline needs."""
+    synchronize on both sides, MAX over ranks) and return the result dict (rank 0) plus what cpu_baseline needs.
+    Without --full that is all; --full adds the per-kernel launch profile of the timed region, three untimed split rounds
+    (t_encode / t_update, update roofline) and, at N > 1, the exchange timing and parameter checksums."""
     import torch.distributed as dist
     from cadre_amd import hip, synth
     from ppo_agent.agent import CadreAgent
@@ -442,7 +477,7 @@ def run_config(name, args, rank, local_rank, world, use_dist, steps, warmup, epi
     sync()
     log("[bench] %s warmup done %.1f s" % (name, time.perf_counter() - T_START))
     n_ex0 = shared.n_allreduce
-    hip.PROFILE = prof = []
+    hip.PROFILE = prof = [] if args.full else None
     marks = [torch.cuda.Event(enable_timing=True) for _ in range(steps + 1)]
     t0 = time.perf_counter()
     for i in range(steps):
@@ -458,10 +493,46 @@ def run_config(name, args, rank, local_rank, world, use_dist, steps, warmup, epi
     n_ex = shared.n_allreduce - n_ex0
     per_step = sorted(marks[i].elapsed_time(marks[i + 1]) for i in range(steps))
     log("[bench] %s timed region %.3f s for %d steps" % (name, elapsed, steps))
+    if dump_dir and rank == 0:
+        dump_outputs(dump_dir, agent, workers, dev_l)
     if use_dist:
         tt = torch.tensor([elapsed], device=dev, dtype=torch.float64)
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         elapsed = float(tt.item())
+    ms = elapsed / steps * 1e3
+    frames = nW * (T + SEQ - 1 if dedup else T * SEQ)
+    n_wino = agent.vae_model.winograd_convs()
+    out = {
+        "value": round(world * nW * T / (elapsed / steps), 2), "ms_per_step": round(ms, 3), "steps": steps, "warmup": warmup,
+        "dtype": "f32" if enc_dtype == "f32" else "bf16 encoder (fp32 accumulate) / f32 PPO update",
+        "data": "synthetic" if episodes is None else "replayed records from %s" % episodes_dir,
+        "config": {"workload": "%s: %d worker(s) x %d-step rollout, %dx%dx3 synthetic obs (+route), DANet encoder "
+                               "(%s) + PPO update (4 epochs x 2 minibatches), %s"
+                               % (name, nW, T, H, W,
+                                  "latent cache: each distinct frame encoded once" if dedup
+                                  else "8 frames/transition, reference convention",
+                                  "fp32" if enc_dtype == "f32" else "bf16 encoder / fp32 losses"),
+                   "workers_per_gpu": nW, "num_steps": T, "obs": [H, W], "minibatch_per_gpu": nW * T // MINI_BATCH_NUM,
+                   "parallelism": "dp%d" % world, "frames_per_round_per_gpu": frames,
+                   "conv_algorithm": ("Winograd in fp32 on %d stride-1 3x3 convs: F(4x4,3x3) on the 36x36 maps (layer2: plane products and inverse "
+                                      "transform in one kernel), F(6x6,3x3) on the 18x18 maps (layer3), F(3x3,3x3) on the 9x9 maps (layer4, head) â€” exact "
+                                      "tilings â€”, the fused F(2x2,3x3) kernel on the 64-channel stage (layer1); direct convolution elsewhere; "
+                                      "CADRE_WINOGRAD=0 = direct everywhere (c2_direct_conv)" % n_wino) if n_wino else "direct"},
+        "ms_per_step_min_median_max": [round(per_step[0], 3), round(per_step[len(per_step) // 2], 3), round(per_step[-1], 3)],
+        "last_losses": [round(x, 6) for x in losses[-1]],
+    }
+    if args.full:
+        out.update(full_figures(agent, workers, cfg, shared, joint, prof, steps, section, dedup, enc_dtype, frames))
+    if use_dist and args.full:
+        out.update(exchange_figures(agent, shared, world, n_ex, sync))
+    del workers, shared, agent
+    torch.cuda.empty_cache()
+    return out, cfg, enc_state, ppo_state
+
+
+def full_figures(agent, workers, cfg, shared, joint, prof, steps, section, dedup, enc_dtype, frames):
+    """--full: rooflines of the timed region's launch profile and the t_encode / t_update split of three untimed rounds."""
+    T, nW, cw = cfg["T"], cfg["workers"], cfg["chunk_windows"]
     # ---- per-kernel roofline from the HIP events recorded (on the launch stream) inside the timed region
     dom, roof = roofline_of(prof, steps)
     if roof is not None:
@@ -489,7 +560,6 @@ def run_config(name, args, rank, local_rank, world, use_dist, steps, warmup, epi
     for _ in range(3):
         learner_round(agent, workers, cfg, shared, timers, joint=joint)
     t_enc, t_upd, step_ms = sorted(timers, key=lambda t: t[1])[1]
-    ms = elapsed / steps * 1e3
     # ---- update step against its HBM roof: parameters P read by forward and backward (8P bytes),
     # gradients written (4P), [all-reduce buffer 4P,] clip read (4P), Adam p/g/m/v in + p/m/v out (28P) = 48P bytes,
     # plus the activations of the 8 nets x 8 steps
@@ -526,28 +596,11 @@ def run_config(name, args, rank, local_rank, world, use_dist, steps, warmup, epi
                 "reference's command-masked work (every net on every row), flops_per_step_executed = a quarter of it (rows "
                 "sorted by command, each net on its own run); hbm_frac = bytes / 8 TB/s, mfma_frac = executed FLOPs / "
                 "157.3 TFLOP/s (fp32 matrix pipe), bound = the larger time" % (P, act_bytes)}
-    frames = nW * (T + SEQ - 1 if dedup else T * SEQ)
     flops_frame = agent.vae_model.flops_per_frame()
     flops_exec = agent.vae_model.flops_per_frame(executed=True)
-    n_wino = agent.vae_model.winograd_convs()
     nwin = nW * T if joint is not None else T
     enc_bytes = sum(agent.vae_model.algorithmic_bytes(min(cw, nwin - t0) * SEQ) for t0 in range(0, nwin, cw)) * (1 if joint is not None else nW)
-    out = {
-        "value": round(world * nW * T / (elapsed / steps), 2), "ms_per_step": round(ms, 3), "steps": steps, "warmup": warmup,
-        "dtype": "f32" if enc_dtype == "f32" else "bf16 encoder (fp32 accumulate) / f32 PPO update",
-        "data": "synthetic" if episodes is None else "replayed records from %s" % episodes_dir,
-        "config": {"workload": "%s: %d worker(s) x %d-step rollout, %dx%dx3 synthetic obs (+route), DANet encoder "
-                               "(%s) + PPO update (4 epochs x 2 minibatches), %s"
-                               % (name, nW, T, H, W,
-                                  "latent cache: each distinct frame encoded once" if dedup
-                                  else "8 frames/transition, reference convention",
-                                  "fp32" if enc_dtype == "f32" else "bf16 encoder / fp32 losses"),
-                   "workers_per_gpu": nW, "num_steps": T, "obs": [H, W], "minibatch_per_gpu": nW * T // MINI_BATCH_NUM,
-                   "parallelism": "dp%d" % world, "frames_per_round_per_gpu": frames,
-                   "conv_algorithm": ("Winograd in fp32 on %d stride-1 3x3 convs: F(4x4,3x3) on the 36x36 maps (layer2: plane products and inverse "
-                                      "transform in one kernel), F(6x6,3x3) on the 18x18 maps (layer3), F(3x3,3x3) on the 9x9 maps (layer4, head) â€” exact "
-                                      "tilings â€”, the fused F(2x2,3x3) kernel on the 64-channel stage (layer1); direct convolution elsewhere; "
-                                      "CADRE_WINOGRAD=0 = direct everywhere (c2_direct_conv)" % n_wino) if n_wino else "direct"},
+    return {
         "t_encode_ms": round(t_enc * 1e3, 3), "t_update_ms": round(t_upd * 1e3, 3),
         "encoder_frames_per_sec": round(frames / t_enc, 1),
         "encoder_tflops": round(frames * flops_frame / t_enc / 1e12, 2),
@@ -569,44 +622,44 @@ def run_config(name, args, rank, local_rank, world, use_dist, steps, warmup, epi
                                  "8000 GB/s; the fp32 conv stack is MFMA-bound (see roofline)",
         "roofline": roof,
         "update_roofline": update_roofline,
-        "ms_per_step_min_median_max": [round(per_step[0], 3), round(per_step[len(per_step) // 2], 3), round(per_step[-1], 3)],
-        "last_losses": [round(x, 6) for x in losses[-1]],
     }
-    if use_dist:
-        # gradient exchange alone: the collective(s) of one optimiser step on the arena, timed back to back after the run
-        import torch.distributed as dist
-        g = agent.arena.grads
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        mode = shared.exchange_mode()
-        reps = 10
-        sync()
-        e0.record()
-        for _ in range(reps):
-            if mode == "sharded":                          # (the collectives chief_step issues in this mode)
-                shared.counter.increment()
-                shared.reduce_scatter()
-                shared.all_gather_params()
-            else:
-                dist.all_reduce(g, op=dist.ReduceOp.SUM)
-        e1.record()
-        sync()
-        shared.reset(zero=True)
-        out["rccl_ranks"] = world
-        out["grad_exchange"] = mode + (" in 3 buckets (MLP towers, steer LSTMs, throttle LSTMs), the first two beside the backward"
-                                        if shared.overlap_hook(agent.arena) is not None else "")
-        out["allreduce_ms_per_step"] = round(e0.elapsed_time(e1) / reps, 4)
-        out["allreduce_bytes"] = int(g.numel() * 4)
-        out["exchanges_in_timed_region"] = n_ex          # one per optimiser step: 8 per round
-        # replicated optimiser: every rank must hold the same parameter bits after the timed rounds.  Checksum = the parameters'
-        # bit patterns summed as int64, gathered from every rank (the first multi-GPU box checks C4 without a builder turn)
-        cs = agent.arena.params.view(torch.int32).to(torch.int64).sum().reshape(1)
-        allcs = [torch.zeros_like(cs) for _ in range(world)]
-        dist.all_gather(allcs, cs)
-        out["param_checksum_by_rank"] = [int(c.item()) for c in allcs]
-        out["params_identical_across_ranks"] = len(set(out["param_checksum_by_rank"])) == 1
-    del workers, shared, agent
-    torch.cuda.empty_cache()
-    return out, cfg, enc_state, ppo_state
+
+
+def exchange_figures(agent, shared, world, n_ex, sync):
+    """--full at N > 1: the gradient exchange of one optimiser step timed alone, and the parameter checksums of every rank."""
+    # gradient exchange alone: the collective(s) of one optimiser step on the arena, timed back to back after the run
+    import torch.distributed as dist
+    g = agent.arena.grads
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    mode = shared.exchange_mode()
+    out = {}
+    reps = 10
+    sync()
+    e0.record()
+    for _ in range(reps):
+        if mode == "sharded":                          # (the collectives chief_step issues in this mode)
+            shared.counter.increment()
+            shared.reduce_scatter()
+            shared.all_gather_params()
+        else:
+            dist.all_reduce(g, op=dist.ReduceOp.SUM)
+    e1.record()
+    sync()
+    shared.reset(zero=True)
+    out["rccl_ranks"] = world
+    out["grad_exchange"] = mode + (" in 3 buckets (MLP towers, steer LSTMs, throttle LSTMs), the first two beside the backward"
+                                    if shared.overlap_hook(agent.arena) is not None else "")
+    out["allreduce_ms_per_step"] = round(e0.elapsed_time(e1) / reps, 4)
+    out["allreduce_bytes"] = int(g.numel() * 4)
+    out["exchanges_in_timed_region"] = n_ex          # one per optimiser step: 8 per round
+    # replicated optimiser: every rank must hold the same parameter bits after the timed rounds.  Checksum = the parameters'
+    # bit patterns summed as int64, gathered from every rank (the first multi-GPU box checks C4 without a builder turn)
+    cs = agent.arena.params.view(torch.int32).to(torch.int64).sum().reshape(1)
+    allcs = [torch.zeros_like(cs) for _ in range(world)]
+    dist.all_gather(allcs, cs)
+    out["param_checksum_by_rank"] = [int(c.item()) for c in allcs]
+    out["params_identical_across_ranks"] = len(set(out["param_checksum_by_rank"])) == 1
+    return out
 
 
 def spawn_ranks(n, timeout_s=None):
@@ -714,7 +767,17 @@ def main():
     ap.add_argument("--dedup", action="store_true",
                     help="encode each distinct frame once (sliding-window latent cache) instead of the "
                          "reference's 8 frames per transition; NOT the default metric convention")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline: the nested section, the latent-cache / direct-conv / stem-bf16x3 rounds, "
+                         "the per-kernel and update rooflines (HIP events around every encoder launch of the timed region, three "
+                         "untimed split rounds), the measured peaks, the CPU baseline and, at N > 1, the exchange timing and "
+                         "parameter checksums.  Without it a run sets up, warms up, times --steps rounds and prints the line")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed rounds, write what the last one computed (losses, a fixed sample of the updated "
+                         "parameters, encoder features, returns, advantages) as DIR/<name>.npy in float32")
     args = ap.parse_args()
+    if not args.full:
+        args.no_c3 = args.no_latent_cache = args.no_direct_conv = args.no_peaks = args.no_cpu_baseline = True
     if args.section:
         args.config = "C2" if args.section == "headline" else "C3"
         args.no_c3 = args.no_latent_cache = args.no_direct_conv = args.no_peaks = args.no_cpu_baseline = True
@@ -782,7 +845,8 @@ def main():
     head = args.config or "C2"
     other = {"C2": "C3", "C3": "C2"}.get(head) if args.config is None else None
     res, cfg, enc_state, ppo_state = run_config(head, args, rank, dev_index, world, use_dist, args.steps, args.warmup,
-                                                args.replay, section={"C2": "headline", "C3": "c3"}.get(head))
+                                                args.replay, section={"C2": "headline", "C3": "c3"}.get(head),
+                                                dump_dir=args.dump_outputs)
     out = {"metric": "ppo_update_samples_per_sec", "value": res.pop("value"), "unit": "samples/s", "n_gpus": world,
            "steps": args.steps, "warmup": args.warmup, "ms_per_step": res.pop("ms_per_step"), "higher_is_better": True,
            "scaling": "weak", "vs_baseline": None}

@@ -418,7 +418,60 @@ def gen_insert():
          command=s.command.numpy(), hn=s.hn.numpy(), cn=s.cn.numpy(), snapshot_keys=np.array(keys))
 
 
-SETS = dict(prep=gen_prep, gae=gen_gae, sampler=gen_sampler, insert=gen_insert, act=gen_act,
+def gen_snapshot(seed=23):
+    """A `ppo_model_<ep>.pt` as the reference's CadreAgent.save_snapshot writes it (agent.py:245-260: a dict of pickled
+    nn.Modules; the quirk omits throttle_lstm), parameters from synth.ppo_state(seed).  Stored without its 40 MB of
+    tensor data: the archive's small records verbatim (the pickle with its class references among them), and for every
+    data/<key> record of a parameter the (module, parameter) of ppo_state(seed) whose float32 bytes it holds — the test
+    rebuilds the archive byte for byte.  Plus what the reference sees when it loads the file: every module's class paths and
+    state_dict shapes (tests/test_snapshot_compat_cpu.py)."""
+    import json
+    import zipfile
+    import ppo_agent.models as rm
+    shim.assert_reference(rm)
+    st = synth.ppo_state(seed)
+    out = {}
+    for c in range(4):
+        for kind in ("throttle_ppo_", "steer_ppo_", "steer_lstm_"):
+            name = kind + str(c)
+            m = rm.LSTM(530, hid_size=530) if "lstm" in name else rm.Model(530, 33 if name.startswith("steer") else 3)
+            m.load_state_dict({n: torch.from_numpy(v) for n, v in st[name].items()})
+            out[name] = m
+    p = os.path.join(TMP, "ppo_model_ref.pt")
+    torch.save(out, p)
+    by_bytes = {}
+    for name in sorted(st):
+        for k in sorted(st[name]):
+            by_bytes.setdefault(np.ascontiguousarray(st[name][k], dtype=np.float32).tobytes(), (name, k))
+    rec_names, rec_bytes, data_keys, data_src = [], [], [], []
+    with zipfile.ZipFile(p) as z:
+        for info in z.infolist():
+            rel = info.filename.split("/", 1)[1]
+            if rel in ("version", ".data/serialization_id"):          # written by the archive writer itself
+                continue
+            blob = z.read(info)
+            if rel.startswith("data/") and blob in by_bytes:
+                data_keys.append(rel[len("data/"):])
+                data_src.append("%s/%s" % by_bytes[blob])
+            elif rel.startswith("data/"):                              # a module's own small tensor (action masks): verbatim
+                assert len(blob) <= 65536, rel
+                data_keys.append(rel[len("data/"):])
+                data_src.append("")
+                rec_bytes.append(np.frombuffer(blob, dtype=np.uint8))
+                rec_names.append(rel)
+            else:
+                rec_names.append(rel)
+                rec_bytes.append(np.frombuffer(blob, dtype=np.uint8))
+    loaded = torch.load(p, map_location="cpu", weights_only=False)
+    view = {name: {"class": type(mod).__module__ + "." + type(mod).__qualname__,
+                   "classes": sorted({type(s).__module__ + "." + type(s).__qualname__ for s in mod.modules()}),
+                   "state_dict": {k: list(v.shape) for k, v in mod.state_dict().items()}} for name, mod in loaded.items()}
+    save("snapshot_ref", seed=seed, record_names=np.array(rec_names), data_keys=np.array(data_keys),
+         data_src=np.array(data_src), reference_view=np.array(json.dumps(view, sort_keys=True)),
+         **{"record_%d" % i: b for i, b in enumerate(rec_bytes)})
+
+
+SETS = dict(prep=gen_prep, gae=gen_gae, sampler=gen_sampler, insert=gen_insert, act=gen_act, snapshot=gen_snapshot,
             act_288=lambda: gen_act("act_288", 288, 288, 4, 4322),
             update=gen_update, chief=gen_clip,
             enc_native=lambda: gen_enc("native", 144, 256),

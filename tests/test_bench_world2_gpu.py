@@ -18,7 +18,8 @@ pytestmark = pytest.mark.gpu
 def _run(extra, timeout=900):
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT")}
     env.update(CADRE_BENCH_BACKEND="gloo", CADRE_BENCH_ONE_DEVICE="1", HSA_ENABLE_IPC_MODE_LEGACY="0")
-    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1"] + extra,
+    # (--full: the exchange timing, parameter checksums and nested sections are not part of a plain run)
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--full"] + extra,
                        env=env, capture_output=True, text=True, timeout=timeout)
     assert p.returncode == 0, p.stderr[-4000:]
     lines = [ln for ln in p.stdout.splitlines() if ln.strip()]
@@ -87,8 +88,8 @@ def test_bench_two_gpus_over_rccl():
     env.update(HSA_ENABLE_IPC_MODE_LEGACY="0")
     sums = {}
     for mode, extra in (("allreduce", []), ("sharded", ["--grad-exchange", "sharded"]), ("buckets", ["--grad-buckets"])):
-        p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--config", "C1",
-                            "--no-c3", "--no-cpu-baseline", "--no-peaks"] + extra, env=env, capture_output=True, text=True, timeout=900)
+        p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--full", "--config",
+                            "C1", "--no-c3", "--no-cpu-baseline", "--no-peaks"] + extra, env=env, capture_output=True, text=True, timeout=900)
         assert p.returncode == 0, p.stderr[-4000:]
         lines = [ln for ln in p.stdout.splitlines() if ln.strip()]
         assert len(lines) == 1, p.stdout[-2000:]

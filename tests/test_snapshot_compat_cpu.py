@@ -1,53 +1,20 @@
-"""CPU, build container only (skipped where /root/reference is absent, e.g. on the GPU box): a `ppo_model_<ep>.pt`
-written by the UNMODIFIED reference `CadreAgent.save_snapshot` (ppo_agent/agent.py:245-260: a dict of pickled
-nn.Modules) unpickles into this repo's `ppo_agent.models.Model / LSTM` / `ppo_agent.distributions.Categorical_1d`
-classes with identical state_dict keys, shapes and values, and the reverse direction loads into the reference's
-`load_snapshot` (agent.py:262-271).  Each side runs in its own process (the two `ppo_agent` packages cannot coexist)."""
+"""CPU: a `ppo_model_<ep>.pt` written by the UNMODIFIED reference `CadreAgent.save_snapshot` (ppo_agent/agent.py:245-260: a
+dict of pickled nn.Modules) unpickles into this repo's `ppo_agent.models.Model / LSTM` / `ppo_agent.distributions.Categorical_1d`
+classes with identical state_dict keys, shapes and values, and what this repo writes in the same format is what the reference's
+`load_snapshot` (agent.py:262-271) reads: every module pickled under the class paths of the reference's own file, with the same
+state_dict keys and shapes, and the values written.  The reference's file is rebuilt record for record from
+tests/golden/snapshot_ref.npz (its pickle and small records verbatim, its parameters regenerated from synth.ppo_state; written by
+`tests/golden/make_golden.py snapshot` from the reference itself).  Each load runs in a fresh process (`ppo_agent` imported from
+this repository only)."""
+import json
 import os
 import subprocess
 import sys
 
-import pytest
+import numpy as np
+import torch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-REF = "/root/reference"
-pytestmark = pytest.mark.skipif(not os.path.isdir(os.path.join(REF, "ppo_agent")), reason="needs the reference checkout (build container)")
-
-REF_WRITE = r"""
-import sys, os, numpy as np, torch
-sys.dont_write_bytecode = True
-sys.path.insert(0, %(root)r)
-from tests.golden import _ref_shim as shim
-tmp = sys.argv[1]
-shim.install(tmp)
-from cadre_amd import synth
-import ppo_agent.models as rm
-shim.assert_reference(rm)
-st = synth.ppo_state(23)
-md = {}
-for c in range(4):
-    for head, k in (("steer", 33), ("throttle", 3)):
-        m = rm.Model(530, k); l = rm.LSTM(530, hid_size=530)
-        m.load_state_dict({n: torch.from_numpy(v) for n, v in st["%%s_ppo_%%d" %% (head, c)].items()})
-        l.load_state_dict({n: torch.from_numpy(v) for n, v in st["%%s_lstm_%%d" %% (head, c)].items()})
-        md["%%s_ppo_%%d" %% (head, c)] = m; md["%%s_lstm_%%d" %% (head, c)] = l
-# agent.py:245-260 verbatim semantics: throttle_ppo, steer_ppo, steer_lstm per command (the quirk omits throttle_lstm)
-out = {}
-for c in range(4):
-    for kind in ("throttle_ppo_", "steer_ppo_", "steer_lstm_"):
-        out[kind + str(c)] = md[kind + str(c)]
-torch.save(out, os.path.join(tmp, "ref_written.pt"))
-if os.path.exists(os.path.join(tmp, "ours_written.pt")):
-    back = torch.load(os.path.join(tmp, "ours_written.pt"), map_location="cpu", weights_only=False)
-    for name, mod in back.items():
-        assert type(mod).__module__.startswith("ppo_agent."), type(mod)
-        shim.assert_reference(sys.modules[type(mod).__module__])
-        md[name].load_state_dict(mod.state_dict())          # agent.py:267-269
-        for k, v in mod.state_dict().items():
-            assert torch.equal(v, torch.from_numpy(st[name][k]) * 0.5), (name, k)
-    print("REF_LOADED_OURS", len(back))
-print("REF_WROTE", len(out))
-"""
 
 OURS = r"""
 import sys, os, numpy as np, torch
@@ -89,6 +56,46 @@ print("OURS_LOADED_REF", n)
 """
 
 
+# the reverse direction: what the reference's load_snapshot meets when it unpickles this repo's file
+OURS_VIEW = r"""
+import sys, os, json, torch
+sys.path.insert(0, %(root)r)
+tmp = sys.argv[1]
+from cadre_amd import synth
+import ppo_agent.models as om
+assert om.__file__.startswith(%(root)r)
+st = synth.ppo_state(23)
+back = torch.load(os.path.join(tmp, "ours_written.pt"), map_location="cpu", weights_only=False)
+for name, mod in back.items():
+    for k, v in mod.state_dict().items():
+        assert torch.equal(v, torch.from_numpy(st[name][k]) * 0.5), (name, k)
+view = {name: {"class": type(mod).__module__ + "." + type(mod).__qualname__,
+               "classes": sorted({type(s).__module__ + "." + type(s).__qualname__ for s in mod.modules()}),
+               "state_dict": {k: list(v.shape) for k, v in mod.state_dict().items()}} for name, mod in back.items()}
+print("OURS_VIEW " + json.dumps(view, sort_keys=True))
+"""
+
+
+def _reference_written(tmp):
+    """ref_written.pt exactly as the reference wrote it (every record of the archive, byte for byte)."""
+    from cadre_amd import synth
+    g = np.load(os.path.join(ROOT, "tests", "golden", "snapshot_ref.npz"), allow_pickle=False)
+    st = synth.ppo_state(int(g["seed"]))
+    recs = {str(n): g["record_%d" % i].tobytes() for i, n in enumerate(g["record_names"])}
+    w = torch._C.PyTorchFileWriter(os.path.join(str(tmp), "ref_written.pt"))
+    for n in ("data.pkl", ".format_version", ".storage_alignment", "byteorder"):
+        w.write_record(n, recs[n], len(recs[n]))
+    for key, src in zip(g["data_keys"], g["data_src"]):
+        if src:
+            m, k = str(src).split("/", 1)
+            b = np.ascontiguousarray(st[m][k], dtype=np.float32).tobytes()
+        else:
+            b = recs["data/" + str(key)]
+        w.write_record("data/" + str(key), b, len(b))
+    w.write_end_of_file()
+    return json.loads(str(g["reference_view"]))
+
+
 def _py(code, tmp, env_extra=None):
     env = dict(os.environ)
     env.pop("PYTHONPATH", None)
@@ -100,10 +107,14 @@ def _py(code, tmp, env_extra=None):
 
 
 def test_reference_written_snapshot_loads_here_and_back(tmp_path):
-    out = _py(REF_WRITE, tmp_path)
-    assert "REF_WROTE 12" in out
+    ref_view = _reference_written(tmp_path)
     out = _py(OURS, tmp_path)
     assert "OURS_LOADED_REF" in out and int(out.split("OURS_LOADED_REF")[1].split()[0]) >= 12 * 4
-    out = _py(REF_WRITE, tmp_path)                      # second pass: the reference loads what this repo wrote
-    assert "REF_LOADED_OURS 12" in out
-    assert not any(d == "__pycache__" for _r, ds, _f in os.walk("/root/reference") for d in ds)
+    out = _py(OURS_VIEW, tmp_path)                      # the reference loads what this repo wrote
+    view = json.loads(out.split("OURS_VIEW ", 1)[1])
+    assert sorted(view) == sorted(ref_view) and len(view) == 12
+    for name, v in view.items():
+        r = ref_view[name]
+        # the same class, only classes the reference's own file names (its unpickler resolves them), the same state_dict
+        assert v["class"] == r["class"] and set(v["classes"]) <= set(r["classes"]), (name, v["classes"], r["classes"])
+        assert v["state_dict"] == r["state_dict"], name

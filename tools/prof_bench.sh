@@ -12,7 +12,7 @@ SECTIONS="${*:-headline c3}"
 STEPS=2; WARM=2
 for S in $SECTIONS; do
   O=$OUT/$S; mkdir -p $O
-  ARGS="--section $S --steps $STEPS --warmup $WARM"
+  ARGS="--full --section $S --steps $STEPS --warmup $WARM"
   rocprofv3 --kernel-trace --stats --output-format csv -d $O/trace -- python3 bench.py $ARGS > $O/trace.json 2> $O/trace.err
   rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d $O/fetch -- python3 bench.py $ARGS > $O/fetch.json 2> $O/fetch.err
   rocprofv3 --pmc WRITE_SIZE --kernel-trace --output-format csv -d $O/write -- python3 bench.py $ARGS > $O/write.json 2> $O/write.err

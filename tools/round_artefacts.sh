@@ -14,7 +14,7 @@ if has tests; then
   timeout 2400 python -m pytest tests -q -m gpu > $O/gpu_tests.log 2>&1; echo "tests rc=$?"; tail -4 $O/gpu_tests.log
 fi
 if has bench; then
-  timeout 1800 python bench.py > $O/bench.json 2> $O/bench.err; echo "bench rc=$?"
+  timeout 1800 python bench.py --full > $O/bench.json 2> $O/bench.err; echo "bench rc=$?"
   python3 tools/bench_digest.py $O/bench.json
 fi
 if has prof; then
