@@ -97,6 +97,9 @@ SYMBOLS = {
     "cadre_permute_minibatch": [vp, i32, i32, vp, vp, i64, vp, vp, vp, vp, i64, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, i64, i64, vp],
     "cadre_ppo_loss": [vp, i64, i64, vp, i64, i64, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, f32, f32, f32, f32, f32, vp, vp, vp, vp, vp, vp],
     "cadre_sample": [vp, i64, vp, i64, i32, i32, vp, vp, vp],
+    "cadre_act_windows": [vp, i64, i32, vp, i64, i32, vp, vp, vp, vp, i32, i32, vp, i64, i32, vp, i64, vp],
+    "cadre_sample_rows": [vp, i64, i64, vp, vp, i32, i32, vp, i32, i32, vp, vp, vp, vp],
+    "cadre_insert_rows": [vp, vp, i32, i32, i64, i64, i32, i32, i32, vp, i64, vp, vp, vp, vp, vp, vp],
     "cadre_categorical_eval": [vp, i64, vp, i32, i32, vp, vp, vp],
     "cadre_categorical_dist": [vp, i64, i32, i32, vp, vp, vp, vp],
     "cadre_clip_adam": [vp, vp, vp, vp, vp, i32, vp, f64, f64, f64, f64, f64, i32, vp],

@@ -12,6 +12,52 @@ from ..learner import PPOLearnerHIP
 from .models import LSTM, Model, _cfg, arena_of, create_model, get_vae_output
 
 
+def command_rows(commands, command_num):
+    """Rows of an act_batch pass sorted by command (stable: environments of one command keep their order).  Returns
+    pos int32 [N] (the sorted row of environment e) and seg int32 [2 * command_num][2]: (first row, count) of net
+    head * command_num + c — the row_seg the LSTM / MLP kernels take; a command without rows has count 0."""
+    cmd = np.asarray(commands, dtype=np.int64).reshape(-1)
+    if cmd.size < 1:
+        raise ValueError("command_rows: no environments")
+    if (cmd < 0).any() or (cmd >= command_num).any():
+        raise ValueError("command_rows: commands %s outside 0 .. %d" % (cmd.tolist(), command_num - 1))
+    counts = np.bincount(cmd, minlength=command_num)
+    first = np.concatenate([[0], np.cumsum(counts)[:-1]])
+    pos = np.empty(cmd.size, dtype=np.int32)
+    pos[np.argsort(cmd, kind="stable")] = np.arange(cmd.size, dtype=np.int32)
+    seg = np.tile(np.stack([first, counts], 1), (2, 1)).astype(np.int32)
+    return pos, seg
+
+
+def check_act_batch(obs_list, shifted, max_envs, device, vae_device, command_num):
+    """Arguments of CadreAgent.act_batch, checked before any device work; raises hip.CadreHipError."""
+    if vae_device != device:
+        raise hip.CadreHipError("act_batch: the encoder (vae_device %s) and the nets (device_num %s) must share one GPU; "
+                                "call act() per environment" % (vae_device, device))
+    N = len(obs_list)
+    if N < 1 or N > max_envs:
+        raise hip.CadreHipError("act_batch: %d environments; 1 .. model_cfg.max_envs = %d per call" % (N, max_envs))
+    if shifted is not None and len(shifted) != N:
+        raise hip.CadreHipError("act_batch: %d `shifted` hints for %d environments" % (len(shifted), N))
+    ref = obs_list[0]
+    S = ref["rgb"].shape[0]
+    want = (tuple(ref["rgb"].shape), tuple(ref["route_fig"].shape), (S, 3))
+    for e, td in enumerate(obs_list):
+        got = (tuple(td["rgb"].shape), tuple(td["route_fig"].shape), tuple(np.shape(td["measurements"])))
+        if got != want or td["rgb"].dtype != np.uint8 or td["route_fig"].dtype != np.uint8:
+            raise hip.CadreHipError("act_batch: observation %d has shapes rgb %s / route_fig %s / measurements %s (dtypes %s, "
+                                    "%s); environment 0 has %s / %s / %s, uint8" % ((e,) + got + (td["rgb"].dtype,
+                                                                                   td["route_fig"].dtype) + want))
+        c = int(td["command"])
+        if not 0 <= c < command_num:
+            raise hip.CadreHipError("act_batch: observation %d has command %d; 0 .. %d" % (e, c, command_num - 1))
+
+
+class ActBatch(list):
+    """act_batch's return value: the list of N act() tuples, plus the device buffers they are views of (feat [N][S][DP],
+    action i64 / logp / value f32 [N][2]) for RolloutStorage.insert_batch."""
+
+
 class CadreAgent(object):
     def __init__(self, rank, model_cfg, frame, STEER_CONTROL, THROTTLE_CONTROL, ent_coeff, value_coeff, clip_coeff,
                  clip):
@@ -42,6 +88,9 @@ class CadreAgent(object):
         import os
         self.act_graph = bool(_cfg(model_cfg, "act_graph", os.environ.get("CADRE_ACT_GRAPH", "0") != "0"))
         self._ag = None
+        # act_batch(): at most `max_envs` environments per call (sizes the device ring of their latent windows)
+        self.max_envs = int(_cfg(model_cfg, "max_envs", 32))
+        self._vec = None
 
     # ------------------------------------------------------------------ observation -> feature
     def pre_process(self, tick_data, first=0):
@@ -244,6 +293,123 @@ class CadreAgent(object):
         ctl_t._last_action, ctl_t._last_logp = a_t, lp_t
         # the reference discards the new hidden state and returns the zeros (agent.py:123-124,141)
         return ppo_feature, [a_s[0], a_t[0]], [lp_s, lp_t], [v_s, v_t], self.hidden_state
+
+    # ------------------------------------------------------------------ act for N environments
+    def act_batch(self, obs_list, shifted=None):
+        """`[self.act(o) for o in obs_list]` for N environments in ONE launch chain: one encoder pass over every fresh
+        frame (the newest frame of each window that shifted, all S frames of the others), cadre_act_windows (the LSTM
+        input rows of all windows, rows sorted by command), one LSTM + MLP pass over all 2C command nets
+        (learner._forward with row_seg) and cadre_sample_rows.  Each environment keeps its own sliding-window cache
+        (slot e of a device ring of latents); `shifted[e]` (optional) asserts that environment e's window moved by one
+        frame since the last call, which skips the host-side comparison of the frames.  Global-RNG consumption is the
+        loop's: one exponential_(1) draw per environment and head, env 0 steer, env 0 throttle, env 1 steer, ...
+        The route quirk (agent.py:51-54: the caller's route_fig normalised in place) is kept per environment.
+        Returns an ActBatch: N tuples in exactly act()'s format."""
+        check_act_batch(obs_list, shifted, self.max_envs, self.device, self.vae_device, self.command_num)
+        N = len(obs_list)
+        a, enc, dev = self.arena, self.vae_model, self.device
+        S, H, W = obs_list[0]["rgb"].shape[:3]
+        L, stream = hip.lib(), hip.stream()
+        vec = self._vec
+        if vec is None or vec["shape"] != (S, H, W) or vec["ring"].shape[0] < self.max_envs:
+            vec = self._vec = dict(shape=(S, H, W), ring=torch.zeros(self.max_envs, S, 512, device=dev),
+                                   cache=[None] * self.max_envs)
+        cache = vec["cache"]
+        commands = [int(td["command"]) for td in obs_list]
+        # window mode per environment, then the fresh frames of all of them in one host array
+        modes, firsts, rgbs, routes = [], [], [], []
+        nf = 0
+        for e, td in enumerate(obs_list):
+            c = cache[e]
+            if c is None or not self.latent_cache:
+                m = False
+            elif shifted is not None:
+                m = bool(shifted[e])
+            else:
+                m = self._window_shifted_vs(c, td)
+            f = S - 1 if m else 0
+            modes.append(1 if m else 0)
+            firsts.append(nf)
+            nf += S - f
+            rgbs.append(td["rgb"][f:])
+            routes.append(td["route_fig"][f:])
+        rgb_d = torch.from_numpy(np.concatenate(rgbs)).to(dev)
+        route_d = torch.from_numpy(np.concatenate(routes)).to(dev)
+        rn_d = torch.empty_like(route_d) if self.mutate_route else None
+        lat = torch.empty(nf, 512, device=dev)
+        for s0 in range(0, nf, enc.max_frames):             # (the encoder's workspace is sized for max_frames)
+            s1 = min(nf, s0 + enc.max_frames)
+            x = enc.preprocess(rgb_d[s0:s1], route_d[s0:s1], None if rn_d is None else rn_d[s0:s1])
+            enc.forward_nhwc(x, lat[s0:s1])
+        # small inputs: descriptors + sort (int32), measurements (f64), sampler noise (f32) — one copy each
+        pos, seg = command_rows(commands, self.command_num)
+        ints = np.concatenate([seg.reshape(-1), np.asarray(modes, np.int32), np.asarray(firsts, np.int32), pos,
+                               np.asarray(commands, np.int32)])
+        ints_d = torch.from_numpy(ints).to(dev)
+        nseg = seg.size
+        seg_d = ints_d[:nseg]
+        mode_d, first_d, pos_d, cmd_d = (ints_d[nseg + i * N:nseg + (i + 1) * N] for i in range(4))
+        meas = np.stack([np.asarray(td["measurements"], dtype=np.float64) for td in obs_list])
+        meas_d = torch.from_numpy(np.ascontiguousarray(meas)).to(dev)
+        nS, nT = a.n_out
+        q = torch.ones(N, 2, 64)
+        for e in range(N):                                  # act()'s order: steer draws first, environment after environment
+            q[e, 0, :nS] = torch.empty(1, nS).exponential_(1)[0]
+            q[e, 1, :nT] = torch.empty(1, nT).exponential_(1)[0]
+        q_d = q.to(dev)
+        # LSTM input rows (sorted by command) + the per-environment feature windows, the ring advanced
+        w = self.learner.workspace(N, a.Z, S)
+        feat = torch.empty(N, S, a.DP, device=dev)            # fresh: callers keep references
+        hip.check(L.cadre_act_windows(hip.ptr(vec["ring"]), vec["ring"].stride(0), vec["ring"].shape[0], hip.ptr(lat),
+                                      lat.stride(0), nf, hip.ptr(mode_d), hip.ptr(first_d), hip.ptr(meas_d), hip.ptr(pos_d),
+                                      N, S, hip.ptr(w["X"]), a.DP, a.DP, hip.ptr(feat), a.DP, stream), "cadre_act_windows")
+        w["h0"].zero_(); w["c0"].zero_()
+        # every net reads head block 0 of X (x_div = 2C): steer and throttle nets see the same window
+        self.learner._forward(w, N, (0, 1, a.Z), 2 * a.C, S=S, seg=seg_d, fused_mlp=True)
+        O3 = w["O3"]
+        action = torch.empty(N, 2, dtype=torch.int64, device=dev)
+        logp = torch.empty(N, 2, device=dev)
+        value = torch.empty(N, 2, device=dev)
+        hip.check(L.cadre_sample_rows(hip.ptr(O3), O3.stride(1), O3.stride(0), hip.ptr(pos_d), hip.ptr(cmd_d), N, a.C,
+                                      hip.ptr(q_d), nS, nT, hip.ptr(action), hip.ptr(logp), hip.ptr(value), stream),
+                  "cadre_sample_rows")
+        # route quirk + window caches (one host sync for the normalised route, as act() has)
+        rn_h = rn_d.cpu().numpy() if rn_d is not None else None
+        out = ActBatch()
+        for e, td in enumerate(obs_list):
+            route_np = td["route_fig"]
+            raw_rgb = td["rgb"].copy() if (self.latent_cache and shifted is None) else None
+            raw_route = route_np.copy() if self.latent_cache else None
+            if rn_h is not None:
+                if modes[e]:
+                    route_np[:-1] = cache[e]["route_norm"][1:]
+                    route_np[S - 1:] = rn_h[firsts[e]:firsts[e] + 1]
+                else:
+                    route_np[:] = rn_h[firsts[e]:firsts[e] + S]
+            if self.latent_cache:
+                cache[e] = dict(rgb=raw_rgb, route_raw=raw_route, route_norm=route_np.copy())
+            lp_s, lp_t = logp[e, 0:1].view(1, 1), logp[e, 1:2].view(1, 1)
+            out.append((feat[e, :, :self.lstm_input], [action[e, 0], action[e, 1]], [lp_s, lp_t],
+                        [value[e, 0:1].view(1, 1), value[e, 1:2].view(1, 1)], self.hidden_state))
+            ctl_s = self.model_dict["steer_ppo_%d" % commands[e]].control
+            ctl_t = self.model_dict["throttle_ppo_%d" % commands[e]].control
+            ctl_s._last_action, ctl_s._last_logp = action[e, 0:1], lp_s
+            ctl_t._last_action, ctl_t._last_logp = action[e, 1:2], lp_t
+        out.feat, out.action, out.logp, out.value = feat, action, logp, value
+        return out
+
+    @staticmethod
+    def _window_shifted_vs(c, tick_data):
+        """_window_shifted against one act_batch window cache (a cache written under a `shifted` hint holds no raw
+        frames: the window is then encoded in full)."""
+        if c["rgb"] is None:
+            return False
+        rgb, route = tick_data["rgb"], tick_data["route_fig"]
+        if rgb.shape != c["rgb"].shape or route.shape != c["route_raw"].shape:
+            return False
+        if not np.array_equal(rgb[:-1], c["rgb"][1:]):
+            return False
+        return np.array_equal(route[:-1], c["route_raw"][1:]) or np.array_equal(route[:-1], c["route_norm"][1:])
 
     def get_value(self, done, steer_batch, throttle_batch):
         """agent.py:143-164."""

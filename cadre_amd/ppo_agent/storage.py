@@ -18,6 +18,8 @@ def _rup(x, m):
 
 
 class RolloutStorage(object):
+    _insert_tables = {}          # insert_batch: device pointer tables of storage sets, keyed by the pointers
+
     def __init__(self, num_steps, mini_batch_num, feature_dims, seq_length, hidden_size, use_gae, gamma, tau):
         T = num_steps
         self.mini_batch_num = mini_batch_num
@@ -76,6 +78,59 @@ class RolloutStorage(object):
         self.masks[s].copy_(torch.as_tensor(masks).reshape(-1)[:1])
         self.command[s] = command
         self.step = (s + 1) % (self.num_steps + 1)
+
+    @staticmethod
+    def insert_batch(storages, outputs, rewards, masks, commands):
+        """`insert` (storage.py:45-58) of one env step of N environments into their 2N storages in ONE launch
+        (cadre_insert_rows): storages = [(steer_rollout, throttle_rollout), ...] per environment, outputs = what
+        CadreAgent.act_batch returned for them, rewards / masks = [N][2] (steer, throttle) host values, commands = the N
+        host-side commands.  The hidden state written is act()'s zeros.  The cursors (and their modulo-(T+1) drift) stay
+        host-side ints, exactly as `insert` keeps them."""
+        N = len(storages)
+        if N < 1 or len(outputs) != N or len(rewards) != N or len(masks) != N or len(commands) != N:
+            raise ValueError("insert_batch: %d storage pairs, %d outputs, %d rewards, %d masks, %d commands"
+                             % (N, len(outputs), len(rewards), len(masks), len(commands)))
+        flat = [s for pair in storages for s in pair]
+        if len(flat) != 2 * N:
+            raise ValueError("insert_batch: storages must be (steer, throttle) pairs")
+        s0 = flat[0]
+        geo = (s0.num_steps, s0.seq_length, s0._ldo, s0._ldh, s0.z_dims, s0.hid_size, s0.device)
+        if any((s.num_steps, s.seq_length, s._ldo, s._ldh, s.z_dims, s.hid_size, s.device) != geo for s in flat):
+            raise ValueError("insert_batch: every storage needs the same geometry and device")
+        if s0.device.type != "cuda":
+            raise hip.CadreHipError("RolloutStorage.insert_batch runs on the HIP device: call .to('cuda:N') first")
+        dev = s0.device
+        feat = getattr(outputs, "feat", None)
+        if feat is not None:
+            action, logp, value = outputs.action, outputs.logp, outputs.value
+        else:                                   # a plain list of act() tuples: one buffer per output kind
+            feat = torch.stack([o[0].reshape(s0.seq_length, -1) for o in outputs])
+            action = torch.stack([torch.stack([o[1][0].reshape(()), o[1][1].reshape(())]) for o in outputs]).to(torch.int64)
+            logp = torch.stack([torch.stack([o[2][0].reshape(()), o[2][1].reshape(())]) for o in outputs]).float()
+            value = torch.stack([torch.stack([o[3][0].reshape(()), o[3][1].reshape(())]) for o in outputs]).float()
+        feat, action, logp, value = (t.to(dev).contiguous() for t in (feat, action, logp, value))
+        if feat.dim() != 3 or feat.shape[0] != N or feat.shape[1] != s0.seq_length or feat.shape[2] < s0.z_dims:
+            raise ValueError("insert_batch: features of shape %s for %d environments x %d x %d"
+                             % (tuple(feat.shape), N, s0.seq_length, s0.z_dims))
+        ptrs = [[hip.ptr(s._obs), hip.ptr(s._hn), hip.ptr(s._cn), hip.ptr(s.action), hip.ptr(s.action_log_probs),
+                 hip.ptr(s.value_preds), hip.ptr(s.rewards), hip.ptr(s.masks), hip.ptr(s.command)] for s in flat]
+        key = tuple(p for row in ptrs for p in row)
+        tables = RolloutStorage._insert_tables
+        table = tables.get(key)
+        if table is None:
+            if len(tables) > 16:
+                tables.clear()
+            table = tables[key] = torch.tensor(ptrs, dtype=torch.int64).to(dev)
+        slots = [s.step for s in flat]
+        ints = torch.tensor(slots + [int(c) for c in commands], dtype=torch.int32).to(dev)
+        rm = torch.tensor([[float(rewards[e][h]), float(torch.as_tensor(masks[e][h]).reshape(-1)[0])]
+                           for e in range(N) for h in (0, 1)], dtype=torch.float32).to(dev)
+        hip.check(hip.lib().cadre_insert_rows(hip.ptr(table), hip.ptr(ints), 2 * N, s0.seq_length, s0._ldo, s0._ldh,
+                                              s0.z_dims, s0.hid_size, s0.num_steps, hip.ptr(feat), feat.stride(1),
+                                              hip.ptr(action), hip.ptr(logp), hip.ptr(value), hip.ptr(rm),
+                                              hip.ptr(ints[2 * N:]), hip.stream()), "cadre_insert_rows")
+        for s in flat:
+            s.step = (s.step + 1) % (s.num_steps + 1)
 
     def after_update(self, hidden_state):
         self.step = 0

@@ -150,3 +150,112 @@ def train(rank, train_cfg, agent_cfg, env_cfg, rollout_cfg, traffic_light=None, 
     if son_process_counter is not None:
         son_process_counter.increment()
     print("process {} finished.".format(rank))
+
+
+# ----------------------------------------------------------------------------- N environments in one process
+def learner_section_multi(agent, rollouts, dones, train_cfg, shared_grad_buffers, optimizer=None, losses_on_device=False):
+    """train.py:76-110 for N workers that share one agent (`num_processes = N` on one GPU, chief.py:13-21 semantics):
+    rollouts = [(steer_rollout, throttle_rollout), ...] per worker, dones[i] = worker i's last `done`.  Bootstrap values
+    of all workers in one pass (get_values), GAE + advantage normalisation per storage, then for each ppo_epoch and
+    minibatch ONE update over the N workers' minibatches (update_policy_from_storages: the losses and gradients are the
+    SUM of the per-worker ones) followed by the in-process chief_step: one optimiser step per barrier.
+    Sampler order: every epoch draws, from the global CPU generator, worker 0 steer, worker 0 throttle, worker 1 steer,
+    ... — one torch.randperm(T) each.  (N processes each draw from their own generator; one process cannot reproduce
+    that stream, so this is the documented order of the single-process form.)  Returns (value_loss_list,
+    policy_loss_list, ent_loss_list), or the [steps, 3] loss tensor with `losses_on_device`."""
+    use_adv_norm = train_cfg["use_adv_norm"]
+    nv = agent.get_values([(s.get_last(as_tensor=True), t.get_last(as_tensor=True)) for s, t in rollouts], dones)
+    advs = [(s.compute_returns(v_s.detach(), normalise=use_adv_norm), t.compute_returns(v_t.detach(), normalise=use_adv_norm))
+            for (s, t), (v_s, v_t) in zip(rollouts, nv)]
+    dev_losses = []
+    for _ in range(train_cfg["ppo_epoch"]):
+        idx = [(s.sample_indices(), t.sample_indices()) for s, t in rollouts]
+        for j in range(len(idx[0][0])):
+            batches = [(s, idx[i][0][j], advs[i][0], t, idx[i][1][j], advs[i][1]) for i, (s, t) in enumerate(rollouts)]
+            dev_losses.append(agent.update_policy_from_storages(batches, sync=False))
+            shared_grad_buffers.add_gradient(agent.model_dict)
+            chief_step(shared_grad_buffers, optimizer, train_cfg["max_grad_norm"], lr=_get(train_cfg, "lr"), zero_grads=False)
+    losses = torch.stack(dev_losses)
+    if losses_on_device:
+        return losses
+    vl, pl, el = [], [], []
+    for v, p, e in losses.tolist():
+        vl.append(v); pl.append(p); el.append(e)
+    return vl, pl, el
+
+
+def train_vec(rank, train_cfg, agent_cfg, env_cfg, rollout_cfg, num_envs, env_cls=None, logger=None,
+              shared_grad_buffers=None, optimizer=None, callback=None):
+    """`train()` for `num_envs` environments driven from ONE process with one agent: the vectorised-env form of the
+    reference's `num_processes` workers on a GPU.  Environment i is worker w = rank * num_envs + i: it gets
+    env_cfg[k][w] for the per-worker keys (port, routes, scenarios, town) and rank w, as train() does for its rank.
+    Every env step is one `act_batch` over all environments, N `env.step` calls, one `RolloutStorage.insert_batch` into
+    the 2N storages and a reset of the finished environments; every episode ends in `learner_section_multi` (see there
+    for the sampler order).  Logging and snapshots as in train() (rank 0).
+    `callback(event, **state)` (optional, for tests and tools): "start" before the first step, "rollout" after each
+    rollout (before its learner section; episode, dones), "update" after each learner section, its log line and its
+    snapshot (episode, losses; saving a snapshot builds nn.Modules, which draws from the global generator); every event
+    also passes agent, envs and rollouts."""
+    if env_cls is None:
+        from env_wrapper import EnvWrapper as env_cls        # needs the CARLA stack (reference env_wrapper.py)
+    if logger is None:
+        logger = _default_logger()
+    if num_envs < 1:
+        raise ValueError("train_vec: num_envs=%r" % (num_envs,))
+    envs = []
+    for i in range(num_envs):
+        w = rank * num_envs + i
+        cfg = type(env_cfg)(env_cfg)
+        cfg["rank"] = w
+        for k in ("port", "routes", "scenarios", "town"):
+            cfg[k] = env_cfg[k][w]
+        cfg["seq_length"] = rollout_cfg.seq_length
+        envs.append(env_cls(cfg))
+    model_dir = os.path.join(envs[0].work_dir, "models")
+    check_exist(model_dir)
+    num_steps = rollout_cfg.num_steps
+    hidden_size, _ = get_vae_output(agent_cfg.model_cfg)
+    agent_cfg.rank = rank
+    agent = CadreAgent(**agent_cfg)
+    device = torch.device("cuda:" + str(agent_cfg.model_cfg.device_num))
+    rollout_cfg.hidden_size = hidden_size
+    rollouts = []
+    for _ in range(num_envs):
+        pair = (RolloutStorage(**rollout_cfg), RolloutStorage(**rollout_cfg))
+        for s in pair:
+            s.to(device)
+        rollouts.append(pair)
+    if shared_grad_buffers is None:              # single-process use: the agent's own arena is the shared one
+        from .models import Shared_grad_buffers
+        shared_grad_buffers = Shared_grad_buffers(agent.model_dict, device)
+    obs = [env.reset() for env in envs]
+    dones = [False] * num_envs
+    state = lambda: dict(agent=agent, envs=envs, rollouts=rollouts)
+    if callback is not None:
+        callback("start", **state())
+    for episode in range(train_cfg.max_episode):
+        for _ in range(num_steps):
+            commands = [o["command"] for o in obs]
+            outs = agent.act_batch(obs)
+            rewards, masks = [], []
+            for i, (env, out) in enumerate(zip(envs, outs)):
+                obs[i], reward, dones[i], info = env.step(agent.convert_action(out[1]))
+                ad = info["action_done"]
+                rewards.append(reward)
+                masks.append([0.0 if ad[0] else 1.0, 0.0 if ad[1] else 1.0])
+            RolloutStorage.insert_batch(rollouts, outs, rewards, masks, commands)
+            for i, env in enumerate(envs):
+                if dones[i]:
+                    obs[i] = env.reset()
+        if callback is not None:
+            callback("rollout", episode=episode, dones=list(dones), **state())
+        vl, pl, el = learner_section_multi(agent, rollouts, dones, train_cfg, shared_grad_buffers, optimizer=optimizer)
+        if episode % train_cfg.log_interval == 0 and rank == 0 and logger is not None:
+            logger.log("Episode: {}, value loss: {:.4f}, policy loss: {:.4f}, entropy loss: {:.4f}".format(
+                episode, np.mean(vl), np.mean(pl), np.mean(el)))
+        if episode % train_cfg.save_interval == 0 and rank == 0:
+            agent.save_snapshot(os.path.join(model_dir, "ppo_model_{}.pt".format(episode)))
+        if callback is not None:
+            callback("update", episode=episode, losses=(vl, pl, el), **state())
+    print("process {} finished ({} environments).".format(rank, num_envs))
+    return agent

@@ -408,6 +408,35 @@ int cadre_ppo_loss(const float* logits, int64_t ldl, int64_t l_ns, const float* 
 int cadre_sample(const float* logits, int64_t ldl, const float* q, int64_t ldq, int32_t R,
                  int32_t n_out, int64_t* action, float* logp, void* stream);
 
+/* ---------------------------------------------------------------- act for N environments (csrc/act_batch.hip)
+ * CadreAgent.act_batch: agent.py:97-141 of N environments in one launch chain.  Rows of the LSTM / MLP pass are sorted
+ * by command: environment e is row pos[e] (0 <= pos[e] < N).
+ * cadre_act_windows: the LSTM input rows of every environment's window.  ring [n_ring][S][512] (slot stride
+ * ring_env_str floats) holds environment e's last window of latents at slot e; fresh [F][ld_fresh] the latents encoded
+ * this step.  mode[e] 1: the window shifted by one frame (rows 1..S-1 of the ring, then fresh row first[e]); 0: S fresh
+ * rows first[e] .. first[e] + S - 1.  meas f64 [N][S][3].  Writes X[s][pos[e]][0..DP) = latent | the measurements as
+ * f32, repeated 6 times at columns 512..529 (cadre_append_measurements) | zeros, the same rows in environment order into
+ * feat [N][S][ldf] (may be NULL), and the new window into the ring. */
+int cadre_act_windows(float* ring, int64_t ring_env_str, int32_t n_ring, const float* fresh, int64_t ld_fresh, int32_t F,
+                      const int32_t* mode, const int32_t* first, const double* meas, const int32_t* pos, int32_t N,
+                      int32_t S, float* X, int64_t ldx, int32_t DP, float* feat, int64_t ldf, void* stream);
+/* cadre_sample for every (environment, head) pair in one launch (one wave each, the same arithmetic): environment e
+ * with command cmd[e] (0 <= cmd[e] < C) reads the actor tower z = 2 * (head * C + cmd[e]) and the critic z + 1 of
+ * O3 [2 Z][z_str] at row pos[e] (row pitch ldo), and q [N][2][64].  action i64 / logp / value f32 [N][2] are written
+ * in ENVIRONMENT order (the sort is undone). */
+int cadre_sample_rows(const float* O3, int64_t ldo, int64_t z_str, const int32_t* pos, const int32_t* cmd, int32_t N,
+                      int32_t C, const float* q, int32_t K_steer, int32_t K_throttle, int64_t* action, float* logp,
+                      float* value, void* stream);
+/* RolloutStorage.insert (storage.py:45-58) for n_dst = 2 N storages in one launch.  dst_table: device array of n_dst
+ * records of nine pointers (obs [T+1][S][ldo], hn, cn [T+1][ldh], action i64, action_log_probs, value_preds,
+ * rewards, masks f32, command i32 [T+1]); storage k = 2 e + head is written at cursor slot[k] (0 <= slot[k] <= T,
+ * the cursors stay on the host): obs <- feat[e] ([S][ldf], D columns), action / log-prob / value <- entry k of the
+ * [N][2] outputs of cadre_sample_rows, reward / mask <- rm [n_dst][2], command <- cmd[e], and the zero hidden state
+ * into hn / cn[slot + 1] (Hd columns) while slot < T. */
+int cadre_insert_rows(const void* dst_table, const int32_t* slot, int32_t n_dst, int32_t S, int64_t ldo, int64_t ldh,
+                      int32_t D, int32_t Hd, int32_t T, const float* feat, int64_t ldf, const int64_t* action,
+                      const float* logp, const float* value, const float* rm, const int32_t* cmd, void* stream);
+
 /* Model.evaluate_actions forward (models.py:199-208): per row log-prob of `actions` and entropy
  * of Categorical(logits=raw logits) */
 int cadre_categorical_eval(const float* logits, int64_t ldl, const int64_t* actions, int32_t R,
