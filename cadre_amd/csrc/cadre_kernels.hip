@@ -1487,20 +1487,34 @@ extern "C" int cadre_permute_minibatch(const int32_t* pos, int32_t B, int32_t S,
 // One wave per row (lane = action index): the log-softmax / entropy reductions are wave shuffles, 16 rows per
 // workgroup, B/16 x 2 workgroups.  The three loss sums stay deterministic: every workgroup publishes its partial sums
 // (agent-scope stores), takes a ticket, and the workgroup that arrives last adds all partials in index order.
-__global__ __launch_bounds__(256) void ppo_loss_kernel(const float* logits, int64_t ldl, int64_t l_ns,
-                                                       const float* values, int64_t ldv, int64_t v_ns,
-                                                       const int64_t* actions, const int32_t* commands,
-                                                       const float* old_values, const float* returns,
-                                                       const float* old_logp, const float* adv, int B, int C,
-                                                       int n_steer, int n_throttle, float clip, float value_coeff,
-                                                       float clip_coeff, float ent_coeff, float inv_b,
-                                                       float* losses, float* dlogits, float* dvalues, float* scratch,
-                                                       const int32_t* poison) {
+// Update diagnostics of cadre_ppo_loss_stats (the STATS instantiation of the same body): per head the sums of
+// (r - 1) - log r, -log r, [|r - 1| > clip], [|v - v_old| > clip], r and the maximum of |log r|, published per workgroup
+// beside the loss partials and combined by the same last arriver in the same fixed order.
+#define PPO_NSTAT 6
+struct ppo_stats_t {
+  float* row;           // [2 heads][F] stats row of this step
+  int32_t F;
+  float* part;          // [2 * nblk][PPO_NSTAT] per-workgroup partials
+  float target_kl;      // > 0: KL gate armed
+  int32_t* stop;        // sticky gate flag (may be NULL when the gate is off)
+};
+
+template <bool STATS>
+__device__ __forceinline__ void ppo_loss_body(const float* logits, int64_t ldl, int64_t l_ns,
+                                              const float* values, int64_t ldv, int64_t v_ns,
+                                              const int64_t* actions, const int32_t* commands,
+                                              const float* old_values, const float* returns,
+                                              const float* old_logp, const float* adv, int B, int C,
+                                              int n_steer, int n_throttle, float clip, float value_coeff,
+                                              float clip_coeff, float ent_coeff, float inv_b,
+                                              float* losses, float* dlogits, float* dvalues, float* scratch,
+                                              const int32_t* poison, const ppo_stats_t& so) {
   const int hd = blockIdx.y;                       // 0 steer, 1 throttle
   const int K = hd == 0 ? n_steer : n_throttle;
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  __shared__ float red[3][4];
+  __shared__ float red[STATS ? 3 + PPO_NSTAT : 3][4];
   float s_act = 0.f, s_val = 0.f, s_ent = 0.f;     // lane 0 of each wave
+  float s_kl = 0.f, s_okl = 0.f, s_cf = 0.f, s_vcf = 0.f, s_r = 0.f, m_lr = 0.f;   // (STATS only)
   for (int i = 0; i < 4; ++i) {
     const int b = blockIdx.x * 16 + wave * 4 + i;
     if (b >= B) break;
@@ -1543,6 +1557,15 @@ __global__ __launch_bounds__(256) void ppo_loss_kernel(const float* logits, int6
     s_act += -fminf(s1, s2);
     s_val += fmaxf(vl, vlc);
     s_ent += H;
+    if constexpr (STATS) {
+      const float lr = lp - old_logp[row];          // log r (the exponent of `ratio` above)
+      s_kl += (ratio - 1.f) - lr;                   // k3 estimator, >= 0
+      s_okl += -lr;
+      s_cf += fabsf(ratio - 1.f) > clip ? 1.f : 0.f;
+      s_vcf += fabsf(dv) > clip ? 1.f : 0.f;
+      s_r += ratio;
+      m_lr = fmaxf(m_lr, fabsf(lr));
+    }
     // ---- backward of total = vc*0.5*mean(max) + cc*mean(-min) - ec*mean(H)
     const bool in_ratio = ratio >= 1.f - clip && ratio <= 1.f + clip;
     float dmin_dr;                                 // d min(s1,s2) / d ratio (torch ties split 0.5/0.5)
@@ -1563,6 +1586,12 @@ __global__ __launch_bounds__(256) void ppo_loss_kernel(const float* logits, int6
           on ? dlp * ((lane == a ? 1.f : 0.f) - pk) + dH * (-pk * (lg + H)) : 0.f;
   }
   if (lane == 0) { red[0][wave] = s_val; red[1][wave] = s_act; red[2][wave] = s_ent; }
+  if constexpr (STATS) {
+    if (lane == 0) {
+      red[3][wave] = s_kl; red[4][wave] = s_okl; red[5][wave] = s_cf;
+      red[6][wave] = s_vcf; red[7][wave] = s_r; red[8][wave] = m_lr;
+    }
+  }
   __syncthreads();
   if (threadIdx.x == 0) {
     const int nblk = gridDim.x, me = hd * nblk + blockIdx.x, total = 2 * nblk;
@@ -1573,6 +1602,13 @@ __global__ __launch_bounds__(256) void ppo_loss_kernel(const float* logits, int6
     __hip_atomic_store(part + 3 * me + 0, tv, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     __hip_atomic_store(part + 3 * me + 1, ta, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     __hip_atomic_store(part + 3 * me + 2, te, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if constexpr (STATS) {
+      for (int k = 0; k < PPO_NSTAT; ++k) {
+        const float* rk = red[3 + k];
+        const float t = k == 5 ? fmaxf(fmaxf(rk[0], rk[1]), fmaxf(rk[2], rk[3])) : (rk[0] + rk[1]) + (rk[2] + rk[3]);
+        __hip_atomic_store(so.part + PPO_NSTAT * me + k, t, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      }
+    }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     const unsigned ticket = __hip_atomic_fetch_add(reinterpret_cast<unsigned*>(scratch), 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     if (ticket == (unsigned)(total - 1)) {          // last arriver: every partial has been published
@@ -1587,10 +1623,60 @@ __global__ __launch_bounds__(256) void ppo_loss_kernel(const float* logits, int6
       losses[0] = value_coeff * 0.5f * sv * inv_b + bad;
       losses[1] = clip_coeff * sa * inv_b + bad;
       losses[2] = ent_coeff * sn * inv_b + bad;
+      if constexpr (STATS) {
+        // per head, partials in workgroup order; means over inv_b (the losses' denominator)
+        float kl[2];
+        for (int h = 0; h < 2; ++h) {
+          float t[PPO_NSTAT] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+          for (int w = h * nblk; w < (h + 1) * nblk; ++w)
+            for (int k = 0; k < PPO_NSTAT; ++k) {
+              const float x = __hip_atomic_load(so.part + PPO_NSTAT * w + k, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+              t[k] = k == 5 ? fmaxf(t[k], x) : t[k] + x;
+            }
+          float* o = so.row + h * so.F;
+          for (int k = 0; k < 5; ++k) o[k] = t[k] * inv_b;
+          o[5] = t[5];
+          kl[h] = t[0] * inv_b;
+        }
+        int32_t stopped = so.stop ? __hip_atomic_load(so.stop, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0;
+        if (so.stop && so.target_kl > 0.f && fmaxf(kl[0], kl[1]) > 1.5f * so.target_kl) stopped = 1;
+        if (so.stop) __hip_atomic_store(so.stop, stopped, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        so.row[6] = stopped ? 0.f : 1.f;            // applied: the optimiser step of this minibatch runs
+        so.row[so.F + 6] = so.row[6];
+      }
       // the counter goes back to zero for the next launch on this scratch (stream-ordered): no clearing launch per step
       __hip_atomic_store(reinterpret_cast<unsigned*>(scratch), 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     }
   }
+}
+
+__global__ __launch_bounds__(256) void ppo_loss_kernel(const float* logits, int64_t ldl, int64_t l_ns,
+                                                       const float* values, int64_t ldv, int64_t v_ns,
+                                                       const int64_t* actions, const int32_t* commands,
+                                                       const float* old_values, const float* returns,
+                                                       const float* old_logp, const float* adv, int B, int C,
+                                                       int n_steer, int n_throttle, float clip, float value_coeff,
+                                                       float clip_coeff, float ent_coeff, float inv_b,
+                                                       float* losses, float* dlogits, float* dvalues, float* scratch,
+                                                       const int32_t* poison) {
+  const ppo_stats_t none{nullptr, 0, nullptr, 0.f, nullptr};
+  ppo_loss_body<false>(logits, ldl, l_ns, values, ldv, v_ns, actions, commands, old_values, returns, old_logp, adv, B, C,
+                       n_steer, n_throttle, clip, value_coeff, clip_coeff, ent_coeff, inv_b, losses, dlogits, dvalues,
+                       scratch, poison, none);
+}
+
+__global__ __launch_bounds__(256) void ppo_loss_stats_kernel(const float* logits, int64_t ldl, int64_t l_ns,
+                                                             const float* values, int64_t ldv, int64_t v_ns,
+                                                             const int64_t* actions, const int32_t* commands,
+                                                             const float* old_values, const float* returns,
+                                                             const float* old_logp, const float* adv, int B, int C,
+                                                             int n_steer, int n_throttle, float clip, float value_coeff,
+                                                             float clip_coeff, float ent_coeff, float inv_b,
+                                                             float* losses, float* dlogits, float* dvalues, float* scratch,
+                                                             const int32_t* poison, ppo_stats_t so) {
+  ppo_loss_body<true>(logits, ldl, l_ns, values, ldv, v_ns, actions, commands, old_values, returns, old_logp, adv, B, C,
+                      n_steer, n_throttle, clip, value_coeff, clip_coeff, ent_coeff, inv_b, losses, dlogits, dvalues,
+                      scratch, poison, so);
 }
 
 __global__ void zero_f32_kernel(float* p, int n) {
@@ -1613,6 +1699,26 @@ extern "C" int cadre_ppo_loss(const float* logits, int64_t ldl, int64_t l_ns, co
                      actions, commands,
                      old_values, returns, old_logp, adv, B, C, n_out_steer, n_out_throttle, clip, value_coeff,
                      clip_coeff, ent_coeff, inv_b, losses, dlogits, dvalues, scratch, poison);
+  return (int)hipGetLastError();
+}
+
+extern "C" int cadre_ppo_loss_stats(const float* logits, int64_t ldl, int64_t l_ns, const float* values, int64_t ldv,
+                                    int64_t v_ns, const int64_t* actions, const int32_t* commands, const float* old_values,
+                                    const float* returns, const float* old_logp, const float* adv, int32_t B, int32_t C,
+                                    int32_t n_out_steer, int32_t n_out_throttle, float clip, float value_coeff,
+                                    float clip_coeff, float ent_coeff, float inv_b, float* losses, float* dlogits,
+                                    float* dvalues, float* scratch, const int32_t* poison, float* stats_row, int32_t F,
+                                    float* stats_scratch, float target_kl, int32_t* stop, void* stream) {
+  FAIL_IF(!logits || !values || !actions || !commands || !old_values || !returns || !old_logp || !adv || !losses ||
+              !dlogits || !dvalues || !scratch || B < 1 || C < 1 || n_out_steer < 1 || n_out_steer > MAX_NOUT || n_out_throttle < 1 ||
+              n_out_throttle > MAX_NOUT || ldl < n_out_steer || ldl < n_out_throttle || ldl > 64,
+          "cadre_ppo_loss_stats: bad argument");
+  FAIL_IF(!stats_row || F < CADRE_PPO_STATS_FIELDS || !stats_scratch || !(target_kl >= 0.f) || (target_kl > 0.f && !stop),
+          "cadre_ppo_loss_stats: bad stats argument (F >= CADRE_PPO_STATS_FIELDS, target_kl >= 0, a stop flag with target_kl > 0)");
+  const ppo_stats_t so{stats_row, F, stats_scratch, target_kl, stop};
+  hipLaunchKernelGGL(ppo_loss_stats_kernel, dim3((B + 15) / 16, 2), dim3(256), 0, ST(stream), logits, ldl, l_ns, values, ldv,
+                     v_ns, actions, commands, old_values, returns, old_logp, adv, B, C, n_out_steer, n_out_throttle, clip,
+                     value_coeff, clip_coeff, ent_coeff, inv_b, losses, dlogits, dvalues, scratch, poison, so);
   return (int)hipGetLastError();
 }
 
@@ -1795,7 +1901,21 @@ __global__ void adam_prep_kernel(double* norms2, int n_models, int32_t* step_dev
   }
 }
 
-__global__ void adam_dev_kernel(float* p, const float* g, float* m, float* v, const int64_t* seg_off,
+// (gated: the norms are still cleared for the norm pass, which runs either way; the step count and the bias corrections stay)
+__global__ void adam_prep_kernel_gated(double* norms2, int n_models, int32_t* step_dev, double lr, double beta1, double beta2,
+                                       const int32_t* stop) {
+  const int i = threadIdx.x;
+  if (i < n_models) norms2[i] = 0.0;
+  if (i == 0 && *stop == 0) {
+    const int step = ++(*step_dev);
+    const double bc1 = 1.0 - pow(beta1, (double)step);
+    const double bc2 = 1.0 - pow(beta2, (double)step);
+    norms2[n_models] = lr / bc1;
+    norms2[n_models + 1] = sqrt(bc2);
+  }
+}
+
+__device__ __forceinline__ void adam_dev_kernel_body(float* p, const float* g, float* m, float* v, const int64_t* seg_off,
                                 const double* norms2, int n_models, float max_norm, float w1, float beta2, float w2,
                                 float eps, int64_t rlo, int64_t rhi) {
   const int mdl = blockIdx.y;
@@ -1834,6 +1954,20 @@ __global__ void adam_dev_kernel(float* p, const float* g, float* m, float* v, co
   }
 }
 
+__global__ void adam_dev_kernel(float* p, const float* g, float* m, float* v, const int64_t* seg_off,
+                                const double* norms2, int n_models, float max_norm, float w1, float beta2, float w2,
+                                float eps, int64_t rlo, int64_t rhi) {
+  adam_dev_kernel_body(p, g, m, v, seg_off, norms2, n_models, max_norm, w1, beta2, w2, eps, rlo, rhi);
+}
+
+// (gated twin: nothing is written while *stop is set — the KL gate of cadre_ppo_loss_stats fired this round)
+__global__ void adam_dev_kernel_gated(float* p, const float* g, float* m, float* v, const int64_t* seg_off,
+                                const double* norms2, int n_models, float max_norm, float w1, float beta2, float w2,
+                                float eps, int64_t rlo, int64_t rhi, const int32_t* stop) {
+  if (*stop) return;
+  adam_dev_kernel_body(p, g, m, v, seg_off, norms2, n_models, max_norm, w1, beta2, w2, eps, rlo, rhi);
+}
+
 // ---- Adam with the recurrent weights' fragment-order copies written in the same pass (round 4).  The update's LSTM kernels
 // read W_hh of the 8 nets in MFMA fragment order (ppo_update.hip: cadre_pack_lstm_weights: forward [slice][gate][k-block]
 // [lane][4], backward the transpose); packing them was its own launch after every optimiser step — 37 MB read twice and 76 MB
@@ -1861,7 +1995,7 @@ struct whh_pack_t {
 //                  the backward layout are the absolute 16-row groups this kernel walks: ONE contiguous KiB per tile.
 // Rows past 4 D and hidden units past D are never written: the copies are allocated zeroed and nothing else touches those
 // elements (cadre_pack_lstm_weights writes the same zeros).
-__global__ __launch_bounds__(256) void adam_whh_pack_kernel(float* p, const float* g, float* m, float* v, const double* norms2,
+__device__ __forceinline__ void adam_whh_pack_kernel_body(float* p, const float* g, float* m, float* v, const double* norms2,
                                                             int n_models, float max_norm, float w1, float beta2, float w2, float eps,
                                                             whh_pack_t k) {
   constexpr int TW = 2;                                    // tiles per wave and pass: 8 x 16-byte loads in flight per lane
@@ -1942,8 +2076,22 @@ __global__ __launch_bounds__(256) void adam_whh_pack_kernel(float* p, const floa
   }
 }
 
+__global__ __launch_bounds__(256) void adam_whh_pack_kernel(float* p, const float* g, float* m, float* v, const double* norms2,
+                                                            int n_models, float max_norm, float w1, float beta2, float w2, float eps,
+                                                            whh_pack_t k) {
+  adam_whh_pack_kernel_body(p, g, m, v, norms2, n_models, max_norm, w1, beta2, w2, eps, k);
+}
+
+// (gated twin: nothing is written while *stop is set — the KL gate of cadre_ppo_loss_stats fired this round)
+__global__ __launch_bounds__(256) void adam_whh_pack_kernel_gated(float* p, const float* g, float* m, float* v, const double* norms2,
+                                                            int n_models, float max_norm, float w1, float beta2, float w2, float eps,
+                                                            whh_pack_t k, const int32_t* stop) {
+  if (*stop) return;
+  adam_whh_pack_kernel_body(p, g, m, v, norms2, n_models, max_norm, w1, beta2, w2, eps, k);
+}
+
 // adam_dev_kernel on everything but the W_hh regions of the LSTM models (those: adam_whh_pack_kernel)
-__global__ void adam_dev_skip_kernel(float* p, const float* g, float* m, float* v, const int64_t* seg_off, const double* norms2,
+__device__ __forceinline__ void adam_dev_skip_kernel_body(float* p, const float* g, float* m, float* v, const int64_t* seg_off, const double* norms2,
                                      int n_models, float max_norm, float w1, float beta2, float w2, float eps, int n_lstm,
                                      int64_t o_whh, int64_t whh_len) {
   const int mdl = blockIdx.y;
@@ -1973,6 +2121,20 @@ __global__ void adam_dev_skip_kernel(float* p, const float* g, float* m, float* 
       p4[i] = pp; m4[i] = mm; v4[i] = vv;
     }
   }
+}
+
+__global__ void adam_dev_skip_kernel(float* p, const float* g, float* m, float* v, const int64_t* seg_off, const double* norms2,
+                                     int n_models, float max_norm, float w1, float beta2, float w2, float eps, int n_lstm,
+                                     int64_t o_whh, int64_t whh_len) {
+  adam_dev_skip_kernel_body(p, g, m, v, seg_off, norms2, n_models, max_norm, w1, beta2, w2, eps, n_lstm, o_whh, whh_len);
+}
+
+// (gated twin: nothing is written while *stop is set — the KL gate of cadre_ppo_loss_stats fired this round)
+__global__ void adam_dev_skip_kernel_gated(float* p, const float* g, float* m, float* v, const int64_t* seg_off, const double* norms2,
+                                     int n_models, float max_norm, float w1, float beta2, float w2, float eps, int n_lstm,
+                                     int64_t o_whh, int64_t whh_len, const int32_t* stop) {
+  if (*stop) return;
+  adam_dev_skip_kernel_body(p, g, m, v, seg_off, norms2, n_models, max_norm, w1, beta2, w2, eps, n_lstm, o_whh, whh_len);
 }
 
 extern "C" int cadre_clip_adam_pack_graph(float* params, const float* grads, float* exp_avg, float* exp_avg_sq,
@@ -2014,6 +2176,110 @@ extern "C" int cadre_clip_adam_graph(float* params, const float* grads, float* e
   hipLaunchKernelGGL(adam_dev_kernel, grid2, dim3(256), 0, ST(stream), params, grads, exp_avg, exp_avg_sq, seg_off,
                      norms2, n_models, (float)max_norm, (float)(1.0 - beta1), (float)beta2, (float)(1.0 - beta2),
                      (float)eps, (int64_t)0, all);
+  return (int)hipGetLastError();
+}
+
+// Gated twins of the two graph entry points (the KL gate of cadre_ppo_loss_stats): while *stop is set, no parameter, moment,
+// weight copy or step count is written; the norm pass still runs (cadre_grad_norms reports it).  Clear flag: the same
+// kernels' code on the same arguments as the ungated entry points, bit for bit.
+extern "C" int cadre_clip_adam_graph_gated(float* params, const float* grads, float* exp_avg, float* exp_avg_sq,
+                                           const int64_t* seg_off, int32_t n_models, double* norms2, double max_norm,
+                                           double lr, double beta1, double beta2, double eps, int32_t* step_dev,
+                                           const int32_t* stop, void* stream) {
+  FAIL_IF(!params || !grads || !exp_avg || !exp_avg_sq || !seg_off || !norms2 || !step_dev || !stop || n_models < 1 ||
+              n_models > 254,
+          "cadre_clip_adam_graph_gated: bad argument");
+  hipLaunchKernelGGL(adam_prep_kernel_gated, dim3(1), dim3(256), 0, ST(stream), norms2, n_models, step_dev, lr, beta1, beta2, stop);
+  dim3 grid(64, n_models), grid2(256, n_models);
+  const int64_t all = (int64_t)1 << 62;
+  hipLaunchKernelGGL(sqnorm_kernel, grid, dim3(256), 0, ST(stream), grads, seg_off, norms2, (int64_t)0, all);
+  hipLaunchKernelGGL(adam_dev_kernel_gated, grid2, dim3(256), 0, ST(stream), params, grads, exp_avg, exp_avg_sq, seg_off,
+                     norms2, n_models, (float)max_norm, (float)(1.0 - beta1), (float)beta2, (float)(1.0 - beta2),
+                     (float)eps, (int64_t)0, all, stop);
+  return (int)hipGetLastError();
+}
+
+extern "C" int cadre_clip_adam_pack_graph_gated(float* params, const float* grads, float* exp_avg, float* exp_avg_sq,
+                                                const int64_t* seg_off, int32_t n_models, double* norms2, double max_norm,
+                                                double lr, double beta1, double beta2, double eps, int32_t* step_dev,
+                                                int32_t n_lstm, int64_t lstm_str, int64_t o_whh, int32_t H4, int32_t ldw,
+                                                int32_t D, float* fwd, float* bwd, int64_t p_str, const int32_t* stop,
+                                                void* stream) {
+  FAIL_IF(!params || !grads || !exp_avg || !exp_avg_sq || !seg_off || !norms2 || !step_dev || !fwd || !bwd || !stop ||
+              n_models < 1 || n_models > 254 || n_lstm < 1 || n_lstm > n_models,
+          "cadre_clip_adam_pack_graph_gated: bad argument");
+  FAIL_IF(ldw != 544 || D < 1 || D > ldw || H4 != 4 * D || (H4 & 3) || (o_whh & 3) || (lstm_str & 3) || (p_str & 3) ||
+              o_whh + (int64_t)H4 * ldw > lstm_str || p_str < (int64_t)((D + 15) / 16) * 4 * 34 * 256 ||
+              (((uintptr_t)params | (uintptr_t)fwd | (uintptr_t)bwd) & 15),
+          "cadre_clip_adam_pack_graph_gated: built for W_hh [4 D][544] inside an LSTM block, 16-byte aligned (see cadre_pack_lstm_weights)");
+  hipLaunchKernelGGL(adam_prep_kernel_gated, dim3(1), dim3(256), 0, ST(stream), norms2, n_models, step_dev, lr, beta1, beta2, stop);
+  const int64_t all = (int64_t)1 << 62;
+  hipLaunchKernelGGL(sqnorm_kernel, dim3(64, n_models), dim3(256), 0, ST(stream), grads, seg_off, norms2, (int64_t)0, all);
+  const float w1 = (float)(1.0 - beta1), b2 = (float)beta2, w2 = (float)(1.0 - beta2);
+  hipLaunchKernelGGL(adam_dev_skip_kernel_gated, dim3(256, n_models), dim3(256), 0, ST(stream), params, grads, exp_avg, exp_avg_sq,
+                     seg_off, norms2, n_models, (float)max_norm, w1, b2, w2, (float)eps, n_lstm, o_whh, (int64_t)H4 * ldw, stop);
+  whh_pack_t k{n_lstm, lstm_str, o_whh, H4, ldw, D, fwd, bwd, p_str};
+  const int blocks = (((H4 + 15) / 16) * (ldw / 16) + 7) / 8;
+  hipLaunchKernelGGL(adam_whh_pack_kernel_gated, dim3(blocks, n_lstm), dim3(256), 0, ST(stream), params, grads, exp_avg, exp_avg_sq,
+                     norms2, n_models, (float)max_norm, w1, b2, w2, (float)eps, k, stop);
+  return (int)hipGetLastError();
+}
+
+// Per-model gradient norms of the step into its stats row: model m = kind * Z + head * C + c (kind 0 LSTM, 1 MLP towers;
+// Z = 2 C) goes to row[head * F + CADRE_PPO_STATS_FIELDS + kind * C + c].  sqrt(norms2[m]): the pre-clip total norm.
+__global__ void grad_norms_kernel(const double* norms2, int C, float* row, int F) {
+  const int m = threadIdx.x, Z = 2 * C;
+  if (m >= 2 * Z) return;
+  const int kind = m / Z, g = m - kind * Z, head = g / C, c = g - head * C;
+  row[head * F + CADRE_PPO_STATS_FIELDS + kind * C + c] = (float)sqrt(norms2[m]);
+}
+
+extern "C" int cadre_grad_norms(const double* norms2, int32_t C, float* stats_row, int32_t F, void* stream) {
+  FAIL_IF(!norms2 || !stats_row || C < 1 || C > 63 || F < CADRE_PPO_STATS_FIELDS + 2 * C, "cadre_grad_norms: bad argument");
+  hipLaunchKernelGGL(grad_norms_kernel, dim3(1), dim3(256), 0, ST(stream), norms2, C, stats_row, F);
+  return (int)hipGetLastError();
+}
+
+// Explained variance 1 - Var(R - V) / Var(R) over rows 0 .. T-1 of each storage (population variances), one workgroup
+// per storage, two passes (means, then squared deviations).  fp64 sums in a fixed order: per thread over strided rows,
+// then the wave tree, then waves 0..3 in order.  (Constant returns: the mean of equal fp32 values is exact in fp64, every
+// deviation is 0 and the result is NaN.)
+struct ev_src_t { const float* returns; const float* values; int64_t T; };
+
+__device__ __forceinline__ void block_sum2_d(double& a, double& b, double (*part)[4]) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  a = wave_sum_d(a); b = wave_sum_d(b);
+  __syncthreads();                                   // (part may still be read from the previous call)
+  if (lane == 0) { part[0][wave] = a; part[1][wave] = b; }
+  __syncthreads();
+  a = (part[0][0] + part[0][1]) + (part[0][2] + part[0][3]);
+  b = (part[1][0] + part[1][1]) + (part[1][2] + part[1][3]);
+}
+
+__global__ __launch_bounds__(256) void explained_variance_kernel(const ev_src_t* src, double* out) {
+  const ev_src_t e = src[blockIdx.x];
+  const int T = (int)e.T;
+  __shared__ double part[2][4];
+  double sr = 0.0, sd = 0.0;                         // sum R, sum (R - V)
+  for (int i = threadIdx.x; i < T; i += 256) {
+    const double r = e.returns[i];
+    sr += r; sd += r - (double)e.values[i];
+  }
+  block_sum2_d(sr, sd, part);
+  const double mr = sr / T, md = sd / T;
+  double qr = 0.0, qd = 0.0;                         // sum (R - mean R)^2, sum (d - mean d)^2
+  for (int i = threadIdx.x; i < T; i += 256) {
+    const double r = e.returns[i], d = r - (double)e.values[i];
+    qr += (r - mr) * (r - mr); qd += (d - md) * (d - md);
+  }
+  block_sum2_d(qr, qd, part);
+  if (threadIdx.x == 0) out[blockIdx.x] = qr == 0.0 ? __builtin_nan("") : 1.0 - (qd / T) / (qr / T);
+}
+
+extern "C" int cadre_explained_variance(const void* src_table, int32_t n_src, double* out, void* stream) {
+  FAIL_IF(!src_table || !out || n_src < 1 || n_src > 65535, "cadre_explained_variance: bad argument");
+  // (the rows per storage are read from the device table: T < 1 yields NaN, never a read)
+  hipLaunchKernelGGL(explained_variance_kernel, dim3(n_src), dim3(256), 0, ST(stream), (const ev_src_t*)src_table, out);
   return (int)hipGetLastError();
 }
 

@@ -96,6 +96,10 @@ SYMBOLS = {
     "cadre_sort_rows_by_command": [vp, i32, i32, vp, vp, vp],
     "cadre_permute_minibatch": [vp, i32, i32, vp, vp, i64, vp, vp, vp, vp, i64, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, i64, i64, vp],
     "cadre_ppo_loss": [vp, i64, i64, vp, i64, i64, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, f32, f32, f32, f32, f32, vp, vp, vp, vp, vp, vp],
+    "cadre_ppo_loss_stats": [vp, i64, i64, vp, i64, i64, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, f32, f32, f32, f32, f32, vp, vp, vp,
+                             vp, vp, vp, i32, vp, f32, vp, vp],
+    "cadre_grad_norms": [vp, i32, vp, i32, vp],
+    "cadre_explained_variance": [vp, i32, vp, vp],
     "cadre_sample": [vp, i64, vp, i64, i32, i32, vp, vp, vp],
     "cadre_act_windows": [vp, i64, i32, vp, i64, i32, vp, vp, vp, vp, i32, i32, vp, i64, i32, vp, i64, vp],
     "cadre_sample_rows": [vp, i64, i64, vp, vp, i32, i32, vp, i32, i32, vp, vp, vp, vp],
@@ -105,6 +109,9 @@ SYMBOLS = {
     "cadre_clip_adam": [vp, vp, vp, vp, vp, i32, vp, f64, f64, f64, f64, f64, i32, vp],
     "cadre_clip_adam_graph": [vp, vp, vp, vp, vp, i32, vp, f64, f64, f64, f64, f64, vp, vp],
     "cadre_clip_adam_pack_graph": [vp, vp, vp, vp, vp, i32, vp, f64, f64, f64, f64, f64, vp, i32, i64, i64, i32, i32, i32, vp, vp, i64, vp],
+    "cadre_clip_adam_graph_gated": [vp, vp, vp, vp, vp, i32, vp, f64, f64, f64, f64, f64, vp, vp, vp],
+    "cadre_clip_adam_pack_graph_gated": [vp, vp, vp, vp, vp, i32, vp, f64, f64, f64, f64, f64, vp, i32, i64, i64, i32, i32, i32, vp, vp,
+                                         i64, vp, vp],
     "cadre_clip_adam_norms": [vp, vp, i32, vp, f64, f64, f64, vp, i64, i64, vp],
     "cadre_clip_adam_apply": [vp, vp, vp, vp, vp, i32, vp, f64, f64, f64, f64, i64, i64, vp],
 }
@@ -157,6 +164,8 @@ def lib():
         _lib = L
     return _lib
 
+
+PPO_STATS_FIELDS = 8  # CADRE_PPO_STATS_FIELDS (include/cadre_hip.h): loss diagnostics per head before the gradient norms
 
 N_CALLS = 0          # C-ABI calls checked so far (one kernel launch each, cadre_clip_adam_graph three): launch census
 

@@ -55,7 +55,43 @@ class PPOLearnerHIP:
         self._adam_fresh = None    # _pkey() right after a fused optimiser step of THIS learner: the copies are current
         self._skip_pack = False
         self._mlp_offs = None
+        # update diagnostics and the target_kl gate (opt-in, set per learner section by set_update_modes): the loss launch
+        # becomes cadre_ppo_loss_stats, the optimiser step its gated twin.  Both modes are part of the hipGraph keys; with
+        # both off every key, launch and bit is what it was without them.
+        self.stats = False
+        self.target_kl = None
+        self._stop = None          # device int32: the gate's sticky flag for the current round
+        self._norm_row = None      # stats row that receives the next optimiser step's per-model gradient norms
         hip.lib()
+
+    # ------------------------------------------------------------------ diagnostics / KL gate
+    def stats_fields(self):
+        """F of a stats row [2 heads][F]: hip.PPO_STATS_FIELDS loss diagnostics, then the head's 2 C gradient norms."""
+        return hip.PPO_STATS_FIELDS + 2 * self.a.C
+
+    def set_update_modes(self, stats=False, target_kl=None):
+        """stats: the update writes its diagnostics (update(..., stats_row=)); target_kl (> 0): arm the KL gate and clear
+        its flag — the round starts with the optimiser enabled.  set_update_modes() returns to the plain update."""
+        if target_kl is not None:
+            target_kl = float(target_kl)
+            if not target_kl > 0.0:
+                raise ValueError("target_kl must be > 0 (got %r)" % (target_kl,))
+            if self._stop is None:
+                self._stop = torch.zeros(1, dtype=torch.int32, device=self.a.device)
+            else:
+                self._stop.zero_()
+        self.stats = bool(stats)
+        self.target_kl = target_kl
+        self._norm_row = None
+
+    def _loss_stats(self):
+        return self.stats or self.target_kl is not None
+
+    def _mode_key(self):
+        """hipGraph key suffix of the update modes: () when both are off (today's graphs)."""
+        if not self._loss_stats():
+            return ()
+        return (("stats", self.target_kl),)
 
     # ------------------------------------------------------------------ workspace
     def workspace(self, B, Z=None, S=None):
@@ -189,7 +225,7 @@ class PPOLearnerHIP:
                      a_z=(1, 0, cs * B * hid), b_z=(1, 0, zs), c_z=(1, 0, cs * B * NP), s_z=(1, 0, zs), seg=sg)
 
     # ------------------------------------------------------------------ update_policy
-    def update(self, B, inv_b, sorted_rows=False, mlp_grads_ready=None):
+    def update(self, B, inv_b, sorted_rows=False, mlp_grads_ready=None, stats_row=None):
         """Forward + loss + backward for the packed minibatch in workspace(B).  Gradients of all 16
         nets are written (not accumulated) into arena.grads.  Returns the device tensor
         losses[3] = (value_loss*vc, action_loss*cc, ent_loss*ec) (agent.py:226-237).
@@ -200,8 +236,13 @@ class PPOLearnerHIP:
         bucket's all-reduce there, beside the kernels that follow (Shared_grad_buffers.reduce_bucket_async):
           after the MLP-tower backward            arena[P0:]            (6 MB)   — beside the backward through time
           after the steer nets' weight gradients  arena[:4 size_L]      (37 MB)  — beside the throttle nets' lstm_dw
-        the throttle nets' bucket arena[4 size_L:P0] is final when the step ends (the chief's all_reduce takes it)."""
+        the throttle nets' bucket arena[4 size_L:P0] is final when the step ends (the chief's all_reduce takes it).
+        `stats_row` (device float32 [2][stats_fields()], needs set_update_modes(stats=True) or a target_kl): the step's
+        diagnostics are copied there after the launch sequence (one device-to-device copy), and the next clip_adam writes its
+        per-model gradient norms into the same row."""
         a = self.a
+        if stats_row is not None and not self._loss_stats():
+            raise hip.CadreHipError("update(stats_row=...) needs set_update_modes(stats=True) (or a target_kl)")
         # The packed W_hh copies are current iff this learner's own fused optimiser step produced the parameters that are
         # in the arena now (a chief in another process, a broadcast or a checkpoint load change them behind our back: then
         # the update's graph carries the packing launch, as in round 3).
@@ -209,7 +250,7 @@ class PPOLearnerHIP:
         try:
             if mlp_grads_ready is None:
                 self._run("all", B, inv_b, sorted_rows)
-                return self.workspace(B)["losses"]
+                return self._stats_out(B, stats_row)
             half = (a.Z // 2) * a.size_L
             for part, rng in (("front", (a.P0, a.total)), ("mid", (0, half)), ("back", None)):
                 self._run(part, B, inv_b, sorted_rows)
@@ -220,9 +261,22 @@ class PPOLearnerHIP:
                         mlp_grads_ready(*rng)
                     elif part == "front":                    # (a round-3 style hook without arguments: the MLP bucket only)
                         mlp_grads_ready()
-            return self.workspace(B)["losses"]
+            return self._stats_out(B, stats_row)
         finally:
             self._skip_pack = False                          # (act / get_value outside an update always check the copies)
+
+    def _stats_out(self, B, stats_row):
+        w = self.workspace(B)
+        if stats_row is not None:
+            stats_row.copy_(w["stats"])
+            self._norm_row = stats_row
+        return w["losses"]
+
+    def _stats_ws(self, w, B):
+        if "stats" not in w:
+            w["stats"] = torch.zeros(2, self.stats_fields(), device=self.a.device)
+            w["stats_scratch"] = torch.zeros(12 * ((B + 15) // 16), device=self.a.device)
+        return w["stats"], w["stats_scratch"]
 
     @staticmethod
     def _hook_takes_range(hook):
@@ -238,7 +292,7 @@ class PPOLearnerHIP:
     def _run(self, part, B, inv_b, sorted_rows):
         if not self.use_graphs:
             return self._update_body(B, inv_b, sorted_rows, part)
-        key = (part, B, inv_b, sorted_rows, self._skip_pack)
+        key = (part, B, inv_b, sorted_rows, self._skip_pack) + self._mode_key()
         g = self._graphs.get(key)
         if g is None:
             n0 = hip.N_CALLS
@@ -290,6 +344,18 @@ class PPOLearnerHIP:
         O3, dO3 = w["O3"], w["dO3"]
         if front:
             self._forward(w, B, (0, 1, Z), C, seg=seg, fused_mlp=True)
+        if front and self._loss_stats():
+            srow, sscr = self._stats_ws(w, B)
+            tkl = 0.0 if self.target_kl is None else self.target_kl
+            hip.check(L.cadre_ppo_loss_stats(hip.ptr(O3), NP, 2 * B * NP, hip.ptr(O3[1]), NP, 2 * B * NP,
+                                             hip.ptr(w["actions"]), hip.ptr(w["commands"]), hip.ptr(w["old_values"]),
+                                             hip.ptr(w["returns"]), hip.ptr(w["old_logp"]), hip.ptr(w["adv"]), B, C,
+                                             a.n_out[0], a.n_out[1], self.clip, self.vc, self.cc, self.ec, inv_b,
+                                             hip.ptr(w["losses"]), hip.ptr(dO3), hip.ptr(dO3[1]), hip.ptr(w["loss_scratch"]),
+                                             hip.ptr(w["sync"][Z * S:]), hip.ptr(srow), srow.shape[1], hip.ptr(sscr), tkl,
+                                             hip.ptr(self._stop) if self.target_kl is not None else None, st),
+                      "cadre_ppo_loss_stats")
+        elif front:
             hip.check(L.cadre_ppo_loss(hip.ptr(O3), NP, 2 * B * NP, hip.ptr(O3[1]), NP, 2 * B * NP,
                                        hip.ptr(w["actions"]), hip.ptr(w["commands"]), hip.ptr(w["old_values"]),
                                        hip.ptr(w["returns"]), hip.ptr(w["old_logp"]), hip.ptr(w["adv"]), B, C,
@@ -366,14 +432,26 @@ class PPOLearnerHIP:
         captured into a hipGraph per hyper-parameter set."""
         a = self.a
         a.ensure_adam()
-        a.step += 1
+        a.step += 1                 # (with the KL gate armed: steps attempted — the learner section reconciles it at its sync)
         fused = self.fused_pack
-        key = ("adam", float(lr), float(max_grad_norm), float(betas[0]), float(betas[1]), float(eps), fused)
+        gated = self.target_kl is not None
+        key = ("adam", float(lr), float(max_grad_norm), float(betas[0]), float(betas[1]), float(eps), fused) + (("gated",) if gated else ())
         if fused:
             self._alloc_wp()
 
         def body():
-            if fused:
+            if gated and fused:
+                hip.check(hip.lib().cadre_clip_adam_pack_graph_gated(
+                    hip.ptr(a.params), hip.ptr(a.grads), hip.ptr(a.exp_avg), hip.ptr(a.exp_avg_sq), hip.ptr(a.seg_off),
+                    2 * a.Z, hip.ptr(a.norms2), key[2], key[1], key[3], key[4], key[5], hip.ptr(a.step_dev),
+                    a.Z, a.size_L, a.o_whh, a.H4, a.DP, a.D, hip.ptr(self._wp[0]), hip.ptr(self._wp[1]), self._wp.stride(1),
+                    hip.ptr(self._stop), hip.stream()), "cadre_clip_adam_pack_graph_gated")
+            elif gated:
+                hip.check(hip.lib().cadre_clip_adam_graph_gated(
+                    hip.ptr(a.params), hip.ptr(a.grads), hip.ptr(a.exp_avg), hip.ptr(a.exp_avg_sq), hip.ptr(a.seg_off),
+                    2 * a.Z, hip.ptr(a.norms2), key[2], key[1], key[3], key[4], key[5], hip.ptr(a.step_dev),
+                    hip.ptr(self._stop), hip.stream()), "cadre_clip_adam_graph_gated")
+            elif fused:
                 hip.check(hip.lib().cadre_clip_adam_pack_graph(
                     hip.ptr(a.params), hip.ptr(a.grads), hip.ptr(a.exp_avg), hip.ptr(a.exp_avg_sq), hip.ptr(a.seg_off),
                     2 * a.Z, hip.ptr(a.norms2), key[2], key[1], key[3], key[4], key[5], hip.ptr(a.step_dev),
@@ -388,6 +466,7 @@ class PPOLearnerHIP:
         def done():
             self._adam_fresh = self._pkey() if fused else None      # (the copies now match the stepped parameters)
             self._wp_key = self._adam_fresh if fused else self._wp_key
+            self._write_norms()
         if not self.use_graphs:
             body()
             return done()
@@ -411,6 +490,8 @@ class PPOLearnerHIP:
         `all_reduce_norms(norms2[:n_models])` (SUM of 16 doubles over the ranks) -> clip + Adam on the shard.
         The Adam moments exist for the shard only (1/N of the state and of the pass's HBM traffic)."""
         a = self.a
+        if self.target_kl is not None:
+            raise hip.CadreHipError("target_kl: the KL gate is not available for the sharded optimiser step (several ranks)")
         if getattr(a, "_shard", None) != (lo, hi):
             if a.step:
                 raise hip.CadreHipError("the optimiser shard changed after %d steps (Adam state is per shard)" % a.step)
@@ -427,6 +508,15 @@ class PPOLearnerHIP:
                                           hip.ptr(a.seg_off), nm, hip.ptr(a.norms2), float(max_grad_norm),
                                           float(betas[0]), float(betas[1]), float(eps), lo, hi, st),
                   "cadre_clip_adam_apply")
+        self._write_norms()
+
+    def _write_norms(self):
+        """The per-model gradient norms of the optimiser step just enqueued into the pending stats row (one launch after
+        the step's graph; nothing read on the host)."""
+        row, self._norm_row = self._norm_row, None
+        if row is not None:
+            hip.check(hip.lib().cadre_grad_norms(hip.ptr(self.a.norms2), self.a.C, hip.ptr(row), row.shape[-1], hip.stream()),
+                      "cadre_grad_norms")
 
     # ------------------------------------------------------------------ inference (act / get_value)
     def infer(self, feats, commands, h0=None, c0=None):

@@ -465,23 +465,24 @@ class CadreAgent(object):
         w["old_logp"][hd].copy_(old_lp.reshape(-1))
         w["adv"][hd].copy_(adv.reshape(-1))
 
-    def update_policy(self, steer_samples, throttle_samples, workers=1):
+    def update_policy(self, steer_samples, throttle_samples, workers=1, stats_row=None):
         """agent.py:166-237: fused forward + loss + explicit backward; `.grad` of every parameter in
         model_dict (views of the gradient arena) holds d total_loss afterwards.  With `workers` > 1
         the sample tuples are the row-concatenation of that many equal-size worker minibatches and
-        the losses are the SUM of per-worker means."""
+        the losses are the SUM of per-worker means.  `stats_row`: device float32
+        [2][learner.stats_fields()] that receives the step's diagnostics (learner.set_update_modes(stats=True))."""
         B = steer_samples[1].shape[0]
         if throttle_samples[1].shape[0] != B:
             raise ValueError("steer/throttle minibatches differ in size")
         w = self.learner.workspace(B)
         self._pack(w, 0, steer_samples)
         self._pack(w, 1, throttle_samples)
-        losses = self.learner.update(B, float(workers) / B)
+        losses = self.learner.update(B, float(workers) / B, stats_row=stats_row)
         self.arena.attach_grads(self.model_dict)
         v, a, e = losses.tolist()
         return v, a, e
 
-    def update_policy_from_storages(self, batches, sync=True, mlp_grads_ready=None):
+    def update_policy_from_storages(self, batches, sync=True, mlp_grads_ready=None, stats_row=None):
         """Fast path of the learner section: `batches` = [(steer_storage, steer_idx, steer_adv,
         throttle_storage, throttle_idx, throttle_adv), ...] one entry per worker (equal sizes).
         Same math as feed_forward_generator -> update_policy, but the minibatch gather writes
@@ -489,7 +490,7 @@ class CadreAgent(object):
         unless `sync` (one host sync per round instead of one per minibatch).  `mlp_grads_ready`
         (callable, optional) is invoked between the MLP-tower backward and the LSTM backward, when the
         gradients of arena[P0:] are final (Shared_grad_buffers.reduce_bucket_async starts their all-reduce
-        there, beside the LSTM backward)."""
+        there, beside the LSTM backward).  `stats_row`: as in update_policy."""
         nW = len(batches)
         Bw = batches[0][1].numel()
         B = nW * Bw
@@ -518,7 +519,7 @@ class CadreAgent(object):
                         hip.ptr(w["actions" + u][hd]), hip.ptr(w["commands" + u][hd]), hip.ptr(w["old_values" + u][hd]),
                         hip.ptr(w["returns" + u][hd]), hip.ptr(w["old_logp" + u][hd]), hip.ptr(w["adv" + u][hd]), st),
                         "cadre_gather_minibatch")
-            return self._finish_update(w, B, nW, srt, sync, mlp_grads_ready)
+            return self._finish_update(w, B, nW, srt, sync, mlp_grads_ready, stats_row=stats_row)
         # ONE gather launch for all workers and both heads: a device table of the storages' pointers (built once per set
         # of storages / advantage tensors) and one host-to-device copy of the 2*nW index vectors
         pairs = [(stor, adv) for (ss, si, sa, ts, ti, ta) in batches for (stor, adv) in ((ss, sa), (ts, ta))]
@@ -562,16 +563,16 @@ class CadreAgent(object):
                 hip.ptr(w["actions"]), hip.ptr(w["commands"]), hip.ptr(w["old_values"]),
                 hip.ptr(w["returns"]), hip.ptr(w["old_logp"]), hip.ptr(w["adv"]), hip.ptr(w["pos"]), hip.ptr(w["seg"]), st),
                 "cadre_gather_sorted_multi")
-            return self._finish_update(w, B, nW, srt, sync, mlp_grads_ready, placed=True)
+            return self._finish_update(w, B, nW, srt, sync, mlp_grads_ready, placed=True, stats_row=stats_row)
         hip.check(L.cadre_gather_minibatch_multi(
             hip.ptr(table), 2 * nW, s0._ldo, s0.seq_length, s0._ldh, hip.ptr(stage[1]), Bw, a.D, a.D, B,
             hip.ptr(w[Xk]), w[Xk].stride(0), a.DP, hip.ptr(w[hk]), hip.ptr(w[ck]), w[hk].stride(0), a.DP,
             hip.ptr(w["actions" + u]), hip.ptr(w["commands" + u]), hip.ptr(w["old_values" + u]),
             hip.ptr(w["returns" + u]), hip.ptr(w["old_logp" + u]), hip.ptr(w["adv" + u]), st),
             "cadre_gather_minibatch_multi")
-        return self._finish_update(w, B, nW, srt, sync, mlp_grads_ready)
+        return self._finish_update(w, B, nW, srt, sync, mlp_grads_ready, stats_row=stats_row)
 
-    def _finish_update(self, w, B, nW, srt, sync, mlp_grads_ready=None, placed=False):
+    def _finish_update(self, w, B, nW, srt, sync, mlp_grads_ready=None, placed=False, stats_row=None):
         """Row sort by command (sorted mode; placed: the gather already put every row at its sorted position), the fused update
         and the loss hand-back."""
         L, st, a = hip.lib(), hip.stream(), self.arena
@@ -586,7 +587,7 @@ class CadreAgent(object):
                 hip.ptr(w["actions"]), hip.ptr(w["commands"]), hip.ptr(w["old_values"]),
                 hip.ptr(w["returns"]), hip.ptr(w["old_logp"]), hip.ptr(w["adv"]), 2, w["X"].stride(0), w["h0"].stride(0), st),
                 "cadre_permute_minibatch")
-        losses = self.learner.update(B, float(nW) / B, sorted_rows=srt, mlp_grads_ready=mlp_grads_ready)
+        losses = self.learner.update(B, float(nW) / B, sorted_rows=srt, mlp_grads_ready=mlp_grads_ready, stats_row=stats_row)
         self.arena.attach_grads(self.model_dict)
         if sync:
             return tuple(losses.tolist())

@@ -139,9 +139,11 @@ class RolloutStorage(object):
             self.hn[0].copy_(hn.reshape(-1))
             self.cn[0].copy_(cn.reshape(-1))
 
-    def compute_returns(self, next_value, normalise=True):
+    def compute_returns(self, next_value, normalise=True, explained_variance=None):
         """storage.py:68-76 (GAE branch) + the caller-side advantage lines train.py:82-88.
-        `self.advantages` holds (ret[:-1]-V[:-1]) normalised with the unbiased std when `normalise`."""
+        `self.advantages` holds (ret[:-1]-V[:-1]) normalised with the unbiased std when `normalise`.
+        `explained_variance` (optional device float64 tensor of one element): receives 1 - Var(R - V) / Var(R) of the
+        value head over the T GAE rows, computed on the device after the GAE launch (RolloutStorage.explained_variance)."""
         if not self.use_gae:
             raise NotImplementedError("use_gae=False branch (storage.py:77-86) is dead in the reference config")
         if not self.returns.is_cuda:
@@ -153,7 +155,29 @@ class RolloutStorage(object):
         hip.check(hip.lib().cadre_gae(hip.ptr(self.rewards), hip.ptr(self.value_preds), hip.ptr(self.masks),
                                       hip.ptr(self._next), hip.ptr(self.returns), hip.ptr(self.advantages), 1,
                                       self.num_steps, g32, gt32, 1 if normalise else 0, hip.stream()), "cadre_gae")
+        if explained_variance is not None:
+            RolloutStorage.explained_variance([self], explained_variance)
         return self.advantages
+
+    _ev_tables = {}
+
+    @staticmethod
+    def explained_variance(storages, out):
+        """Explained variance of the value head, 1 - Var(R - V) / Var(R) (population variances, fp64) over rows 0..T-1 of
+        every storage after compute_returns, in ONE launch (cadre_explained_variance): out = device float64 [len(storages)];
+        NaN where the returns are constant.  Nothing is read back on the host."""
+        if not storages or out.dtype != torch.float64 or out.numel() < len(storages) or not out.is_contiguous():
+            raise ValueError("explained_variance: %d storages into %s %s" % (len(storages), out.dtype, tuple(out.shape)))
+        rows = [[hip.ptr(s.returns), hip.ptr(s.value_preds), s.num_steps] for s in storages]
+        key = tuple(v for r in rows for v in r)
+        table = RolloutStorage._ev_tables.get(key)
+        if table is None:
+            if len(RolloutStorage._ev_tables) > 16:
+                RolloutStorage._ev_tables.clear()
+            table = RolloutStorage._ev_tables[key] = torch.tensor(rows, dtype=torch.int64).to(out.device)
+        hip.check(hip.lib().cadre_explained_variance(hip.ptr(table), len(storages), hip.ptr(out), hip.stream()),
+                  "cadre_explained_variance")
+        return out
 
     def get_last(self, as_tensor=False):
         """storage.py:88-91: (obs[-1], command[-1].item()).  `.item()` on a device tensor is a host sync — in the learner

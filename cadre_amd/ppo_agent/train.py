@@ -6,6 +6,7 @@ import os
 import numpy as np
 import torch
 
+from .. import hip
 from .agent import CadreAgent
 from .chief import chief_step
 from .models import arena_of, get_vae_output
@@ -30,9 +31,99 @@ def _default_logger():
         return None
 
 
+# ----------------------------------------------------------------------------- update diagnostics and the KL early stop
+STAT_FIELDS = ("approx_kl", "old_approx_kl", "clip_fraction", "value_clip_fraction", "ratio_mean", "max_abs_log_ratio")
+
+
+def _target_kl(train_cfg, shared_grad_buffers, in_process_chief=True):
+    """train_cfg["target_kl"] (absent / None: no gate).  The gate is a device flag of THIS rank: ranks would disagree on it,
+    so it is refused with several ranks; a chief in another process does not see it either."""
+    tkl = _get(train_cfg, "target_kl")
+    if tkl is None:
+        return None
+    tkl = float(tkl)
+    if not tkl > 0.0:
+        raise ValueError("train_cfg.target_kl must be > 0 (got %r)" % (tkl,))
+    if shared_grad_buffers is not None and shared_grad_buffers.dist_world() > 1:
+        raise hip.CadreHipError("train_cfg.target_kl needs a single rank (world size %d): the KL gate is per rank and ranks "
+                                "would disagree on it; the diagnostics (log_stats) work at any world size"
+                                % shared_grad_buffers.dist_world())
+    if not in_process_chief:
+        raise hip.CadreHipError("train_cfg.target_kl needs the in-process chief (the gate lives on this process's device)")
+    return tkl
+
+
+class _SectionStats:
+    """Device side of a section's diagnostics: one stats row per minibatch step, the explained variance of every storage,
+    and the host-side dict filled after the section's single sync."""
+
+    def __init__(self, agent, n_steps, n_storages):
+        lrn = agent.learner
+        self.agent, self.F = agent, lrn.stats_fields()
+        dev = agent.arena.device
+        self.rows = torch.zeros(n_steps, 2, self.F, device=dev)
+        self.ev = torch.zeros(n_storages, dtype=torch.float64, device=dev)
+        self.step0 = agent.arena.step
+        self.i = 0
+
+    def next_row(self):
+        r = self.rows[self.i]
+        self.i += 1
+        return r
+
+    def finish(self, stats, gated, losses=None):
+        """One device->host copy of (losses,) rows and explained variances; the host step count follows the device's."""
+        parts = ([losses.double().reshape(-1)] if losses is not None else []) + [self.rows.double().reshape(-1), self.ev]
+        host = torch.cat(parts).cpu()
+        nl = 0 if losses is None else losses.numel()
+        tab = host[nl:nl + self.rows.numel()].view(self.rows.shape)
+        ev = host[nl + self.rows.numel():].view(-1, 2)
+        applied = [bool(r[0, 6] != 0) for r in tab]
+        n_applied = sum(applied)
+        a, lrn = self.agent.arena, self.agent.learner
+        if gated:
+            a.step = self.step0 + n_applied          # = step_dev: skipped steps did not count
+            if n_applied < len(applied):             # (parameters frozen mid-round: re-derive every cached copy of them)
+                lrn._wp_key = None
+                lrn._adam_fresh = None
+        if stats is not None:
+            C, names = a.C, a.model_names()
+            rows = []
+            for r in tab.tolist():
+                d = {f: (r[0][k], r[1][k]) for k, f in enumerate(STAT_FIELDS)}
+                d["applied"] = r[0][6] != 0
+                # model m = kind * 2C + head * C + c (arena segment order) -> row[head][FIELDS + kind * C + c]
+                d["grad_norm"] = [r[(m % (2 * C)) // C][hip.PPO_STATS_FIELDS + (m // (2 * C)) * C + m % C]
+                                  for m in range(len(names))]
+                rows.append(d)
+            stats.clear()
+            stats.update(rows=rows, model_names=names, explained_variance=[tuple(e) for e in ev.tolist()],
+                         updates_applied=n_applied, steps=len(applied),
+                         stopped_at_step=None if n_applied == len(applied) else applied.index(False))
+        return None if losses is None else host[:nl].view(losses.shape)
+
+
+def _steps_per_epoch(storage):
+    T = storage.num_steps
+    return len(range(0, T, T // storage.mini_batch_num))
+
+
+def stats_line(episode, stats):
+    """The `log_stats` line of train() / train_vec(): means over the section's steps, explained variance averaged over
+    the workers."""
+    rows = stats["rows"]
+    mean = lambda f, h: float(np.mean([r[f][h] for r in rows]))
+    ev = np.array(stats["explained_variance"], dtype=np.float64)
+    return ("Episode: {}, approx kl: {:.6f}/{:.6f}, clip fraction: {:.4f}/{:.4f}, explained variance: {:.4f}/{:.4f}, "
+            "updates applied: {}/{}, max grad norm: {:.4f}").format(
+        episode, mean("approx_kl", 0), mean("approx_kl", 1), mean("clip_fraction", 0), mean("clip_fraction", 1),
+        float(np.mean(ev[:, 0])), float(np.mean(ev[:, 1])), stats["updates_applied"], stats["steps"],
+        max(max(r["grad_norm"]) for r in rows))
+
+
 def learner_section(agent, steer_rollout, throttle_rollout, done, train_cfg, shared_grad_buffers,
                     optimizer=None, traffic_light=None, counter=None, shared_model_list=None, in_process_chief=True,
-                    fused_gather=True, losses_on_device=False, step_events=None):
+                    fused_gather=True, losses_on_device=False, step_events=None, stats=None):
     """train.py:76-110.  Returns (value_loss_list, policy_loss_list, ent_loss_list).
     With `in_process_chief` (one process per GPU) the optimiser step runs right after the gradient
     all-reduce instead of waiting on a separate chief process.  `fused_gather` uses the storage ->
@@ -42,11 +133,52 @@ def learner_section(agent, steer_rollout, throttle_rollout, done, train_cfg, sha
     `.item()` (storage.py:88-91) would wait for every kernel enqueued so far — the whole encoder pass — before the host
     may enqueue the rest of the section (0.5-1.1 ms of idle GPU per round).  `losses_on_device` (needs fused_gather):
     return the [steps, 3] loss tensor instead of the three lists, so the caller chooses when to wait; `step_events`:
-    a list that receives one timing event before every minibatch step and one after the last."""
+    a list that receives one timing event before every minibatch step and one after the last.
+    `stats` (a dict): the update diagnostics of the section, filled after its one host sync (with `losses_on_device` the
+    section then syncs once for them): "rows" (per minibatch step: approx_kl, old_approx_kl, clip_fraction,
+    value_clip_fraction, ratio_mean, max_abs_log_ratio as (steer, throttle) pairs, "applied", and "grad_norm", the
+    pre-clip norm of every model in "model_names" order), "explained_variance" [(steer, throttle)], "updates_applied",
+    "steps" and "stopped_at_step" (None unless the KL gate fired).
+    train_cfg["target_kl"] (optional, single rank only): KL early stop.  When the approx KL of a minibatch exceeds
+    1.5 * target_kl in either head, the optimiser step of that minibatch and of every later one of this section is skipped
+    on the device (the Stable-Baselines3 rule).  The sampler still draws every epoch's permutations, so the global CPU
+    generator — and every later act() sample — does not depend on the KL outcome; forward and backward still run for
+    skipped steps (their losses are returned); only the optimiser work is gated, and the Adam step count equals the
+    number of applied steps."""
+    tkl = _target_kl(train_cfg, shared_grad_buffers, in_process_chief)
     use_adv_norm = train_cfg["use_adv_norm"]
+    sec = None
+    if stats is not None or tkl is not None:
+        sec = _SectionStats(agent, train_cfg["ppo_epoch"] * _steps_per_epoch(steer_rollout), 2)
+        agent.learner.set_update_modes(stats=True, target_kl=tkl)
+    try:
+        out = _learner_section(agent, steer_rollout, throttle_rollout, done, train_cfg, shared_grad_buffers, optimizer,
+                               traffic_light, counter, shared_model_list, in_process_chief, fused_gather, losses_on_device,
+                               step_events, use_adv_norm, sec)
+    finally:
+        if sec is not None:
+            agent.learner.set_update_modes()
+    if sec is None:
+        return out
+    if losses_on_device:
+        sec.finish(stats, tkl is not None)
+        return out
+    dev_losses, (vl, pl, el) = out
+    host = sec.finish(stats, tkl is not None, losses=torch.stack(dev_losses) if dev_losses else None)
+    if host is not None:
+        for v, p, e in host.tolist():
+            vl.append(v); pl.append(p); el.append(e)
+    return vl, pl, el
+
+
+def _learner_section(agent, steer_rollout, throttle_rollout, done, train_cfg, shared_grad_buffers, optimizer, traffic_light,
+                     counter, shared_model_list, in_process_chief, fused_gather, losses_on_device, step_events, use_adv_norm,
+                     sec):
     nv_s, nv_t = agent.get_value(done, steer_rollout.get_last(as_tensor=True), throttle_rollout.get_last(as_tensor=True))
-    steer_adv = steer_rollout.compute_returns(nv_s.detach(), normalise=use_adv_norm)
-    throttle_adv = throttle_rollout.compute_returns(nv_t.detach(), normalise=use_adv_norm)
+    steer_adv = steer_rollout.compute_returns(nv_s.detach(), normalise=use_adv_norm,
+                                              explained_variance=None if sec is None else sec.ev[0:1])
+    throttle_adv = throttle_rollout.compute_returns(nv_t.detach(), normalise=use_adv_norm,
+                                                    explained_variance=None if sec is None else sec.ev[1:2])
     dev_losses = []
     vl, pl, el = [], [], []
     # several ranks, CADRE_GRAD_BUCKETS=1: gradient buckets leave as soon as they are final, beside the rest of the backward
@@ -63,11 +195,13 @@ def learner_section(agent, steer_rollout, throttle_rollout, done, train_cfg, sha
         for kind, a, b in steps:
             if step_events is not None:
                 step_events.append(torch.cuda.Event(enable_timing=True)); step_events[-1].record()
+            row = None if sec is None else sec.next_row()
             if kind == "idx":
                 dev_losses.append(agent.update_policy_from_storages(
-                    [(steer_rollout, a, steer_adv, throttle_rollout, b, throttle_adv)], sync=False, mlp_grads_ready=hook))
+                    [(steer_rollout, a, steer_adv, throttle_rollout, b, throttle_adv)], sync=False, mlp_grads_ready=hook,
+                    stats_row=row))
             else:
-                v, p, e = agent.update_policy(a, b)
+                v, p, e = agent.update_policy(a, b, stats_row=row)
                 vl.append(v); pl.append(p); el.append(e)
             if in_process_chief:
                 shared_grad_buffers.add_gradient(agent.model_dict)
@@ -88,6 +222,8 @@ def learner_section(agent, steer_rollout, throttle_rollout, done, train_cfg, sha
         if not dev_losses:
             raise ValueError("losses_on_device needs fused_gather=True")
         return torch.stack(dev_losses)
+    if sec is not None:                              # (the caller syncs once for the losses and the diagnostics together)
+        return dev_losses, (vl, pl, el)
     if dev_losses:
         for v, p, e in torch.stack(dev_losses).tolist():
             vl.append(v); pl.append(p); el.append(e)
@@ -121,6 +257,7 @@ def train(rank, train_cfg, agent_cfg, env_cfg, rollout_cfg, traffic_light=None, 
         shared_grad_buffers = Shared_grad_buffers(agent.model_dict, device)
     obs = env.reset()
     done = False
+    log_stats = bool(_get(train_cfg, "log_stats", False))
     for episode in range(train_cfg.max_episode):
         for _ in range(num_steps):
             command = obs["command"]
@@ -138,13 +275,16 @@ def train(rank, train_cfg, agent_cfg, env_cfg, rollout_cfg, traffic_light=None, 
                 obs = env.reset()
         if recorder is not None:
             recorder.end_episode()
+        stats = {} if log_stats else None
         vl, pl, el = learner_section(agent, steer_rollout, throttle_rollout, done, train_cfg, shared_grad_buffers,
                                      traffic_light=traffic_light, counter=counter,
                                      shared_model_list=shared_model_list,
-                                     in_process_chief=traffic_light is None)   # no chief process -> step in-process
+                                     in_process_chief=traffic_light is None, stats=stats)   # no chief process -> step in-process
         if episode % train_cfg.log_interval == 0 and rank == 0 and logger is not None:
             logger.log("Episode: {}, value loss: {:.4f}, policy loss: {:.4f}, entropy loss: {:.4f}".format(
                 episode, np.mean(vl), np.mean(pl), np.mean(el)))
+            if log_stats:
+                logger.log(stats_line(episode, stats))
         if episode % train_cfg.save_interval == 0 and rank == 0:
             agent.save_snapshot(os.path.join(model_dir, "ppo_model_{}.pt".format(episode)))
     if son_process_counter is not None:
@@ -153,7 +293,8 @@ def train(rank, train_cfg, agent_cfg, env_cfg, rollout_cfg, traffic_light=None, 
 
 
 # ----------------------------------------------------------------------------- N environments in one process
-def learner_section_multi(agent, rollouts, dones, train_cfg, shared_grad_buffers, optimizer=None, losses_on_device=False):
+def learner_section_multi(agent, rollouts, dones, train_cfg, shared_grad_buffers, optimizer=None, losses_on_device=False,
+                          stats=None):
     """train.py:76-110 for N workers that share one agent (`num_processes = N` on one GPU, chief.py:13-21 semantics):
     rollouts = [(steer_rollout, throttle_rollout), ...] per worker, dones[i] = worker i's last `done`.  Bootstrap values
     of all workers in one pass (get_values), GAE + advantage normalisation per storage, then for each ppo_epoch and
@@ -162,20 +303,39 @@ def learner_section_multi(agent, rollouts, dones, train_cfg, shared_grad_buffers
     Sampler order: every epoch draws, from the global CPU generator, worker 0 steer, worker 0 throttle, worker 1 steer,
     ... — one torch.randperm(T) each.  (N processes each draw from their own generator; one process cannot reproduce
     that stream, so this is the documented order of the single-process form.)  Returns (value_loss_list,
-    policy_loss_list, ent_loss_list), or the [steps, 3] loss tensor with `losses_on_device`."""
+    policy_loss_list, ent_loss_list), or the [steps, 3] loss tensor with `losses_on_device`.
+    `stats` and train_cfg["target_kl"]: as in learner_section ("explained_variance" holds one (steer, throttle) pair per
+    worker, all 2N storages in one launch after their GAE).  The diagnostics of a step are taken over the N workers'
+    minibatches with the losses' denominator: like the losses, they are the SUM of the per-worker means."""
+    tkl = _target_kl(train_cfg, shared_grad_buffers)
     use_adv_norm = train_cfg["use_adv_norm"]
     nv = agent.get_values([(s.get_last(as_tensor=True), t.get_last(as_tensor=True)) for s, t in rollouts], dones)
     advs = [(s.compute_returns(v_s.detach(), normalise=use_adv_norm), t.compute_returns(v_t.detach(), normalise=use_adv_norm))
             for (s, t), (v_s, v_t) in zip(rollouts, nv)]
+    sec = None
+    if stats is not None or tkl is not None:
+        sec = _SectionStats(agent, train_cfg["ppo_epoch"] * _steps_per_epoch(rollouts[0][0]), 2 * len(rollouts))
+        RolloutStorage.explained_variance([x for pair in rollouts for x in pair], sec.ev)
+        agent.learner.set_update_modes(stats=True, target_kl=tkl)
     dev_losses = []
-    for _ in range(train_cfg["ppo_epoch"]):
-        idx = [(s.sample_indices(), t.sample_indices()) for s, t in rollouts]
-        for j in range(len(idx[0][0])):
-            batches = [(s, idx[i][0][j], advs[i][0], t, idx[i][1][j], advs[i][1]) for i, (s, t) in enumerate(rollouts)]
-            dev_losses.append(agent.update_policy_from_storages(batches, sync=False))
-            shared_grad_buffers.add_gradient(agent.model_dict)
-            chief_step(shared_grad_buffers, optimizer, train_cfg["max_grad_norm"], lr=_get(train_cfg, "lr"), zero_grads=False)
+    try:
+        for _ in range(train_cfg["ppo_epoch"]):
+            idx = [(s.sample_indices(), t.sample_indices()) for s, t in rollouts]
+            for j in range(len(idx[0][0])):
+                batches = [(s, idx[i][0][j], advs[i][0], t, idx[i][1][j], advs[i][1]) for i, (s, t) in enumerate(rollouts)]
+                dev_losses.append(agent.update_policy_from_storages(batches, sync=False,
+                                                                    stats_row=None if sec is None else sec.next_row()))
+                shared_grad_buffers.add_gradient(agent.model_dict)
+                chief_step(shared_grad_buffers, optimizer, train_cfg["max_grad_norm"], lr=_get(train_cfg, "lr"), zero_grads=False)
+    finally:
+        if sec is not None:
+            agent.learner.set_update_modes()
     losses = torch.stack(dev_losses)
+    if sec is not None and not losses_on_device:
+        host = sec.finish(stats, tkl is not None, losses=losses)
+        return tuple(list(c) for c in zip(*host.tolist()))
+    if sec is not None:
+        sec.finish(stats, tkl is not None)
     if losses_on_device:
         return losses
     vl, pl, el = [], [], []
@@ -230,6 +390,7 @@ def train_vec(rank, train_cfg, agent_cfg, env_cfg, rollout_cfg, num_envs, env_cl
         shared_grad_buffers = Shared_grad_buffers(agent.model_dict, device)
     obs = [env.reset() for env in envs]
     dones = [False] * num_envs
+    log_stats = bool(_get(train_cfg, "log_stats", False))
     state = lambda: dict(agent=agent, envs=envs, rollouts=rollouts)
     if callback is not None:
         callback("start", **state())
@@ -249,10 +410,14 @@ def train_vec(rank, train_cfg, agent_cfg, env_cfg, rollout_cfg, num_envs, env_cl
                     obs[i] = env.reset()
         if callback is not None:
             callback("rollout", episode=episode, dones=list(dones), **state())
-        vl, pl, el = learner_section_multi(agent, rollouts, dones, train_cfg, shared_grad_buffers, optimizer=optimizer)
+        stats = {} if log_stats else None
+        vl, pl, el = learner_section_multi(agent, rollouts, dones, train_cfg, shared_grad_buffers, optimizer=optimizer,
+                                           stats=stats)
         if episode % train_cfg.log_interval == 0 and rank == 0 and logger is not None:
             logger.log("Episode: {}, value loss: {:.4f}, policy loss: {:.4f}, entropy loss: {:.4f}".format(
                 episode, np.mean(vl), np.mean(pl), np.mean(el)))
+            if log_stats:
+                logger.log(stats_line(episode, stats))
         if episode % train_cfg.save_interval == 0 and rank == 0:
             agent.save_snapshot(os.path.join(model_dir, "ppo_model_{}.pt".format(episode)))
         if callback is not None:

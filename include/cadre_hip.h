@@ -402,6 +402,32 @@ int cadre_ppo_loss(const float* logits, int64_t ldl, int64_t l_ns, const float* 
                    int32_t n_out_throttle, float clip, float value_coeff, float clip_coeff,
                    float ent_coeff, float inv_b, float* losses, float* dlogits, float* dvalues,
                    float* scratch, const int32_t* poison, void* stream);
+/* cadre_ppo_loss with PPO update diagnostics and the KL gate (opt-in; the same loss kernel body compiled with its stats
+ * reductions, losses / dlogits / dvalues bit-identical to cadre_ppo_loss).  Per head hd, with log r = lp - old_logp and
+ * every mean taken with inv_b (the losses' denominator), the launch writes stats_row[hd * F + k]:
+ *   k = 0 approx_kl = mean((r - 1) - log r)   1 old_approx_kl = mean(-log r)   2 clip_fraction = mean(|r - 1| > clip)
+ *   3 value_clip_fraction = mean(|v - v_old| > clip)   4 ratio_mean   5 max |log r|   6 applied (1.0 / 0.0)
+ * (k = 7 is not written; F >= CADRE_PPO_STATS_FIELDS).  The sums are combined by the loss kernel's last arriving workgroup
+ * in workgroup order: two launches on the same inputs give the same bits.  stats_scratch: 12 * ceil(B / 16) floats.
+ * target_kl > 0 arms the gate: when max(approx_kl steer, throttle) > 1.5 * target_kl, *stop is set to 1; *stop is
+ * sticky (only the caller clears it) and `applied` = (*stop == 0) after the check.  target_kl == 0: no check; stop may
+ * then be NULL (applied = 1) or a flag that is only read. */
+#define CADRE_PPO_STATS_FIELDS 8
+int cadre_ppo_loss_stats(const float* logits, int64_t ldl, int64_t l_ns, const float* values, int64_t ldv,
+                         int64_t v_ns, const int64_t* actions, const int32_t* commands, const float* old_values,
+                         const float* returns, const float* old_logp, const float* adv, int32_t B, int32_t C,
+                         int32_t n_out_steer, int32_t n_out_throttle, float clip, float value_coeff, float clip_coeff,
+                         float ent_coeff, float inv_b, float* losses, float* dlogits, float* dvalues, float* scratch,
+                         const int32_t* poison, float* stats_row, int32_t F, float* stats_scratch, float target_kl,
+                         int32_t* stop, void* stream);
+/* Per-model pre-clip gradient norms sqrt(norms2[m]) (what clip_grad_norm_ returns) of the optimiser step that just ran on
+ * norms2, into a stats row [2][F]: model m = kind * 2C + head * C + c (the arena's segment order: 2C LSTM blocks, then 2C
+ * MLP-tower pairs) goes to stats_row[head * F + CADRE_PPO_STATS_FIELDS + kind * C + c].  F >= CADRE_PPO_STATS_FIELDS + 2 C. */
+int cadre_grad_norms(const double* norms2, int32_t C, float* stats_row, int32_t F, void* stream);
+/* Explained variance of the value head per storage: src_table = device array of n_src records {const float* returns,
+ * const float* value_preds, int64_t T}; out[i] = 1 - Var(R - V) / Var(R) over rows 0 .. T-1 (population variances,
+ * fp64, fixed summation order), NaN where Var(R) == 0. */
+int cadre_explained_variance(const void* src_table, int32_t n_src, double* out, void* stream);
 /* Model.act sampling (models.py:184-189, distributions.py:96-99) == argmax(p/q), q supplied
  * by the host from the torch CPU generator.  logits [R][ldl] raw; outputs action i64 [R],
  * log_prob f32 [R] of the sampled action. */
@@ -478,6 +504,20 @@ int cadre_clip_adam_pack_graph(float* params, const float* grads, float* exp_avg
                                double beta1, double beta2, double eps, int32_t* step_dev, int32_t n_lstm,
                                int64_t lstm_str, int64_t o_whh, int32_t H4, int32_t ldw, int32_t D, float* fwd,
                                float* bwd, int64_t p_str, void* stream);
+
+/* Gated twins of cadre_clip_adam_graph / cadre_clip_adam_pack_graph (the target_kl early stop): `stop` is the device flag of
+ * cadre_ppo_loss_stats.  While *stop != 0 the step writes no parameter, exp_avg, exp_avg_sq or weight copy and leaves
+ * *step_dev as it is; the per-model square norms are still computed into norms2.  With *stop == 0 the result is bit-identical
+ * to the ungated entry point. */
+int cadre_clip_adam_graph_gated(float* params, const float* grads, float* exp_avg, float* exp_avg_sq,
+                                const int64_t* seg_off, int32_t n_models, double* norms2, double max_norm,
+                                double lr, double beta1, double beta2, double eps, int32_t* step_dev,
+                                const int32_t* stop, void* stream);
+int cadre_clip_adam_pack_graph_gated(float* params, const float* grads, float* exp_avg, float* exp_avg_sq,
+                                     const int64_t* seg_off, int32_t n_models, double* norms2, double max_norm, double lr,
+                                     double beta1, double beta2, double eps, int32_t* step_dev, int32_t n_lstm,
+                                     int64_t lstm_str, int64_t o_whh, int32_t H4, int32_t ldw, int32_t D, float* fwd,
+                                     float* bwd, int64_t p_str, const int32_t* stop, void* stream);
 
 /* Data-parallel ranks with a reduce-scattered gradient arena (reference semantics chief.py:13-21: SUM
  * over workers, per-model clip, Adam): this rank owns arena elements [rlo, rhi) (multiples of 4).
