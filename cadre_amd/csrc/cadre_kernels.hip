@@ -1499,7 +1499,10 @@ struct ppo_stats_t {
   int32_t* stop;        // sticky gate flag (may be NULL when the gate is off)
 };
 
-template <bool STATS>
+// HP: the four PPO scalars come from the device hyper-parameter block (include/cadre_hip.h: CADRE_HP_*), read once into
+// registers before the row loop; the by-value arguments are then ignored.  With STATS the last arriver also runs the
+// KL-adaptive learning-rate controller on hp[CADRE_HP_LR] (after the gate check: a stopped round leaves lr alone).
+template <bool STATS, bool HP>
 __device__ __forceinline__ void ppo_loss_body(const float* logits, int64_t ldl, int64_t l_ns,
                                               const float* values, int64_t ldv, int64_t v_ns,
                                               const int64_t* actions, const int32_t* commands,
@@ -1508,7 +1511,13 @@ __device__ __forceinline__ void ppo_loss_body(const float* logits, int64_t ldl, 
                                               int n_steer, int n_throttle, float clip, float value_coeff,
                                               float clip_coeff, float ent_coeff, float inv_b,
                                               float* losses, float* dlogits, float* dvalues, float* scratch,
-                                              const int32_t* poison, const ppo_stats_t& so) {
+                                              const int32_t* poison, const ppo_stats_t& so, double* hp) {
+  if constexpr (HP) {
+    clip = (float)hp[CADRE_HP_CLIP];
+    value_coeff = (float)hp[CADRE_HP_VALUE_COEFF];
+    clip_coeff = (float)hp[CADRE_HP_CLIP_COEFF];
+    ent_coeff = (float)hp[CADRE_HP_ENT_COEFF];
+  }
   const int hd = blockIdx.y;                       // 0 steer, 1 throttle
   const int K = hd == 0 ? n_steer : n_throttle;
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -1643,6 +1652,17 @@ __device__ __forceinline__ void ppo_loss_body(const float* logits, int64_t ldl, 
         if (so.stop) __hip_atomic_store(so.stop, stopped, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         so.row[6] = stopped ? 0.f : 1.f;            // applied: the optimiser step of this minibatch runs
         so.row[so.F + 6] = so.row[6];
+        if constexpr (HP) {
+          // KL-adaptive lr (the rsl_rl / RL-Games rule), all in double; the optimiser step of THIS minibatch reads the result
+          const double desired = hp[CADRE_HP_DESIRED_KL];
+          if (desired > 0.0 && !stopped) {
+            const double k = fmax((double)kl[0], (double)kl[1]);
+            double lr = hp[CADRE_HP_LR];
+            if (k > 2.0 * desired) lr = fmax(hp[CADRE_HP_LR_MIN], lr / hp[CADRE_HP_LR_FACTOR]);
+            else if (k > 0.0 && k < desired / 2.0) lr = fmin(hp[CADRE_HP_LR_MAX], lr * hp[CADRE_HP_LR_FACTOR]);
+            hp[CADRE_HP_LR] = lr;
+          }
+        }
       }
       // the counter goes back to zero for the next launch on this scratch (stream-ordered): no clearing launch per step
       __hip_atomic_store(reinterpret_cast<unsigned*>(scratch), 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -1660,9 +1680,9 @@ __global__ __launch_bounds__(256) void ppo_loss_kernel(const float* logits, int6
                                                        float* losses, float* dlogits, float* dvalues, float* scratch,
                                                        const int32_t* poison) {
   const ppo_stats_t none{nullptr, 0, nullptr, 0.f, nullptr};
-  ppo_loss_body<false>(logits, ldl, l_ns, values, ldv, v_ns, actions, commands, old_values, returns, old_logp, adv, B, C,
-                       n_steer, n_throttle, clip, value_coeff, clip_coeff, ent_coeff, inv_b, losses, dlogits, dvalues,
-                       scratch, poison, none);
+  ppo_loss_body<false, false>(logits, ldl, l_ns, values, ldv, v_ns, actions, commands, old_values, returns, old_logp, adv, B, C,
+                              n_steer, n_throttle, clip, value_coeff, clip_coeff, ent_coeff, inv_b, losses, dlogits, dvalues,
+                              scratch, poison, none, nullptr);
 }
 
 __global__ __launch_bounds__(256) void ppo_loss_stats_kernel(const float* logits, int64_t ldl, int64_t l_ns,
@@ -1674,9 +1694,35 @@ __global__ __launch_bounds__(256) void ppo_loss_stats_kernel(const float* logits
                                                              float clip_coeff, float ent_coeff, float inv_b,
                                                              float* losses, float* dlogits, float* dvalues, float* scratch,
                                                              const int32_t* poison, ppo_stats_t so) {
-  ppo_loss_body<true>(logits, ldl, l_ns, values, ldv, v_ns, actions, commands, old_values, returns, old_logp, adv, B, C,
-                      n_steer, n_throttle, clip, value_coeff, clip_coeff, ent_coeff, inv_b, losses, dlogits, dvalues,
-                      scratch, poison, so);
+  ppo_loss_body<true, false>(logits, ldl, l_ns, values, ldv, v_ns, actions, commands, old_values, returns, old_logp, adv, B, C,
+                             n_steer, n_throttle, clip, value_coeff, clip_coeff, ent_coeff, inv_b, losses, dlogits, dvalues,
+                             scratch, poison, so, nullptr);
+}
+
+// (the same bodies with the four scalars read from the hyper-parameter block)
+__global__ __launch_bounds__(256) void ppo_loss_hp_kernel(const float* logits, int64_t ldl, int64_t l_ns,
+                                                          const float* values, int64_t ldv, int64_t v_ns,
+                                                          const int64_t* actions, const int32_t* commands,
+                                                          const float* old_values, const float* returns,
+                                                          const float* old_logp, const float* adv, int B, int C,
+                                                          int n_steer, int n_throttle, double* hp, float inv_b,
+                                                          float* losses, float* dlogits, float* dvalues, float* scratch,
+                                                          const int32_t* poison) {
+  const ppo_stats_t none{nullptr, 0, nullptr, 0.f, nullptr};
+  ppo_loss_body<false, true>(logits, ldl, l_ns, values, ldv, v_ns, actions, commands, old_values, returns, old_logp, adv, B, C,
+                             n_steer, n_throttle, 0.f, 0.f, 0.f, 0.f, inv_b, losses, dlogits, dvalues, scratch, poison, none, hp);
+}
+
+__global__ __launch_bounds__(256) void ppo_loss_stats_hp_kernel(const float* logits, int64_t ldl, int64_t l_ns,
+                                                                const float* values, int64_t ldv, int64_t v_ns,
+                                                                const int64_t* actions, const int32_t* commands,
+                                                                const float* old_values, const float* returns,
+                                                                const float* old_logp, const float* adv, int B, int C,
+                                                                int n_steer, int n_throttle, double* hp, float inv_b,
+                                                                float* losses, float* dlogits, float* dvalues, float* scratch,
+                                                                const int32_t* poison, ppo_stats_t so) {
+  ppo_loss_body<true, true>(logits, ldl, l_ns, values, ldv, v_ns, actions, commands, old_values, returns, old_logp, adv, B, C,
+                            n_steer, n_throttle, 0.f, 0.f, 0.f, 0.f, inv_b, losses, dlogits, dvalues, scratch, poison, so, hp);
 }
 
 __global__ void zero_f32_kernel(float* p, int n) {
@@ -1719,6 +1765,46 @@ extern "C" int cadre_ppo_loss_stats(const float* logits, int64_t ldl, int64_t l_
   hipLaunchKernelGGL(ppo_loss_stats_kernel, dim3((B + 15) / 16, 2), dim3(256), 0, ST(stream), logits, ldl, l_ns, values, ldv,
                      v_ns, actions, commands, old_values, returns, old_logp, adv, B, C, n_out_steer, n_out_throttle, clip,
                      value_coeff, clip_coeff, ent_coeff, inv_b, losses, dlogits, dvalues, scratch, poison, so);
+  return (int)hipGetLastError();
+}
+
+// Hyper-parameter block variants: clip / value_coeff / clip_coeff / ent_coeff are (float)hp[CADRE_HP_*] at run time, so a
+// captured launch follows the block's values.  hp: device double[CADRE_HP_FIELDS], 8-byte aligned.
+#define BAD_HP(hp) (!(hp) || ((uintptr_t)(hp) & 7))
+
+extern "C" int cadre_ppo_loss_hp(const float* logits, int64_t ldl, int64_t l_ns, const float* values, int64_t ldv,
+                                 int64_t v_ns, const int64_t* actions, const int32_t* commands, const float* old_values,
+                                 const float* returns, const float* old_logp, const float* adv, int32_t B, int32_t C,
+                                 int32_t n_out_steer, int32_t n_out_throttle, double* hp, float inv_b, float* losses,
+                                 float* dlogits, float* dvalues, float* scratch, const int32_t* poison, void* stream) {
+  FAIL_IF(!logits || !values || !actions || !commands || !old_values || !returns || !old_logp || !adv || !losses ||
+              !dlogits || !dvalues || !scratch || B < 1 || C < 1 || n_out_steer < 1 || n_out_steer > MAX_NOUT || n_out_throttle < 1 ||
+              n_out_throttle > MAX_NOUT || ldl < n_out_steer || ldl < n_out_throttle || ldl > 64,
+          "cadre_ppo_loss_hp: bad argument");
+  FAIL_IF(BAD_HP(hp), "cadre_ppo_loss_hp: bad hyper-parameter block (device double[CADRE_HP_FIELDS], 8-byte aligned)");
+  hipLaunchKernelGGL(ppo_loss_hp_kernel, dim3((B + 15) / 16, 2), dim3(256), 0, ST(stream), logits, ldl, l_ns, values, ldv, v_ns,
+                     actions, commands, old_values, returns, old_logp, adv, B, C, n_out_steer, n_out_throttle, hp, inv_b,
+                     losses, dlogits, dvalues, scratch, poison);
+  return (int)hipGetLastError();
+}
+
+extern "C" int cadre_ppo_loss_stats_hp(const float* logits, int64_t ldl, int64_t l_ns, const float* values, int64_t ldv,
+                                       int64_t v_ns, const int64_t* actions, const int32_t* commands, const float* old_values,
+                                       const float* returns, const float* old_logp, const float* adv, int32_t B, int32_t C,
+                                       int32_t n_out_steer, int32_t n_out_throttle, double* hp, float inv_b, float* losses,
+                                       float* dlogits, float* dvalues, float* scratch, const int32_t* poison, float* stats_row,
+                                       int32_t F, float* stats_scratch, float target_kl, int32_t* stop, void* stream) {
+  FAIL_IF(!logits || !values || !actions || !commands || !old_values || !returns || !old_logp || !adv || !losses ||
+              !dlogits || !dvalues || !scratch || B < 1 || C < 1 || n_out_steer < 1 || n_out_steer > MAX_NOUT || n_out_throttle < 1 ||
+              n_out_throttle > MAX_NOUT || ldl < n_out_steer || ldl < n_out_throttle || ldl > 64,
+          "cadre_ppo_loss_stats_hp: bad argument");
+  FAIL_IF(!stats_row || F < CADRE_PPO_STATS_FIELDS || !stats_scratch || !(target_kl >= 0.f) || (target_kl > 0.f && !stop),
+          "cadre_ppo_loss_stats_hp: bad stats argument (F >= CADRE_PPO_STATS_FIELDS, target_kl >= 0, a stop flag with target_kl > 0)");
+  FAIL_IF(BAD_HP(hp), "cadre_ppo_loss_stats_hp: bad hyper-parameter block (device double[CADRE_HP_FIELDS], 8-byte aligned)");
+  const ppo_stats_t so{stats_row, F, stats_scratch, target_kl, stop};
+  hipLaunchKernelGGL(ppo_loss_stats_hp_kernel, dim3((B + 15) / 16, 2), dim3(256), 0, ST(stream), logits, ldl, l_ns, values, ldv,
+                     v_ns, actions, commands, old_values, returns, old_logp, adv, B, C, n_out_steer, n_out_throttle, hp, inv_b,
+                     losses, dlogits, dvalues, scratch, poison, so);
   return (int)hipGetLastError();
 }
 
@@ -1915,6 +2001,21 @@ __global__ void adam_prep_kernel_gated(double* norms2, int n_models, int32_t* st
   }
 }
 
+// (hyper-parameter block: lr is hp[CADRE_HP_LR] at run time — the only place lr enters the step; stop may be NULL)
+__global__ void adam_prep_kernel_hp(double* norms2, int n_models, int32_t* step_dev, const double* hp, double beta1, double beta2,
+                                    const int32_t* stop) {
+  const int i = threadIdx.x;
+  if (i < n_models) norms2[i] = 0.0;
+  if (i == 0 && (!stop || *stop == 0)) {
+    const double lr = hp[CADRE_HP_LR];
+    const int step = ++(*step_dev);
+    const double bc1 = 1.0 - pow(beta1, (double)step);
+    const double bc2 = 1.0 - pow(beta2, (double)step);
+    norms2[n_models] = lr / bc1;
+    norms2[n_models + 1] = sqrt(bc2);
+  }
+}
+
 __device__ __forceinline__ void adam_dev_kernel_body(float* p, const float* g, float* m, float* v, const int64_t* seg_off,
                                 const double* norms2, int n_models, float max_norm, float w1, float beta2, float w2,
                                 float eps, int64_t rlo, int64_t rhi) {
@@ -1966,6 +2067,15 @@ __global__ void adam_dev_kernel_gated(float* p, const float* g, float* m, float*
                                 float eps, int64_t rlo, int64_t rhi, const int32_t* stop) {
   if (*stop) return;
   adam_dev_kernel_body(p, g, m, v, seg_off, norms2, n_models, max_norm, w1, beta2, w2, eps, rlo, rhi);
+}
+
+// (hyper-parameter block twin: max_norm is (float)hp[CADRE_HP_MAX_GRAD_NORM]; GATED: nothing is written while *stop is set)
+template <bool GATED>
+__global__ void adam_dev_kernel_hp(float* p, const float* g, float* m, float* v, const int64_t* seg_off,
+                                   const double* norms2, int n_models, const double* hp, float w1, float beta2, float w2,
+                                   float eps, int64_t rlo, int64_t rhi, const int32_t* stop) {
+  if constexpr (GATED) { if (*stop) return; }
+  adam_dev_kernel_body(p, g, m, v, seg_off, norms2, n_models, (float)hp[CADRE_HP_MAX_GRAD_NORM], w1, beta2, w2, eps, rlo, rhi);
 }
 
 // ---- Adam with the recurrent weights' fragment-order copies written in the same pass (round 4).  The update's LSTM kernels
@@ -2090,6 +2200,14 @@ __global__ __launch_bounds__(256) void adam_whh_pack_kernel_gated(float* p, cons
   adam_whh_pack_kernel_body(p, g, m, v, norms2, n_models, max_norm, w1, beta2, w2, eps, k);
 }
 
+template <bool GATED>
+__global__ __launch_bounds__(256) void adam_whh_pack_kernel_hp(float* p, const float* g, float* m, float* v, const double* norms2,
+                                                               int n_models, const double* hp, float w1, float beta2, float w2,
+                                                               float eps, whh_pack_t k, const int32_t* stop) {
+  if constexpr (GATED) { if (*stop) return; }
+  adam_whh_pack_kernel_body(p, g, m, v, norms2, n_models, (float)hp[CADRE_HP_MAX_GRAD_NORM], w1, beta2, w2, eps, k);
+}
+
 // adam_dev_kernel on everything but the W_hh regions of the LSTM models (those: adam_whh_pack_kernel)
 __device__ __forceinline__ void adam_dev_skip_kernel_body(float* p, const float* g, float* m, float* v, const int64_t* seg_off, const double* norms2,
                                      int n_models, float max_norm, float w1, float beta2, float w2, float eps, int n_lstm,
@@ -2135,6 +2253,15 @@ __global__ void adam_dev_skip_kernel_gated(float* p, const float* g, float* m, f
                                      int64_t o_whh, int64_t whh_len, const int32_t* stop) {
   if (*stop) return;
   adam_dev_skip_kernel_body(p, g, m, v, seg_off, norms2, n_models, max_norm, w1, beta2, w2, eps, n_lstm, o_whh, whh_len);
+}
+
+template <bool GATED>
+__global__ void adam_dev_skip_kernel_hp(float* p, const float* g, float* m, float* v, const int64_t* seg_off, const double* norms2,
+                                        int n_models, const double* hp, float w1, float beta2, float w2, float eps, int n_lstm,
+                                        int64_t o_whh, int64_t whh_len, const int32_t* stop) {
+  if constexpr (GATED) { if (*stop) return; }
+  adam_dev_skip_kernel_body(p, g, m, v, seg_off, norms2, n_models, (float)hp[CADRE_HP_MAX_GRAD_NORM], w1, beta2, w2, eps, n_lstm,
+                            o_whh, whh_len);
 }
 
 extern "C" int cadre_clip_adam_pack_graph(float* params, const float* grads, float* exp_avg, float* exp_avg_sq,
@@ -2225,6 +2352,96 @@ extern "C" int cadre_clip_adam_pack_graph_gated(float* params, const float* grad
   return (int)hipGetLastError();
 }
 
+// Hyper-parameter block forms of the four graph entry points: lr = hp[CADRE_HP_LR] (read by the prep kernel) and
+// max_norm = hp[CADRE_HP_MAX_GRAD_NORM] (read by the Adam kernels) at run time.  Same kernels' bodies on the same values as
+// the by-value entry points: bit-identical results for equal values.
+template <bool GATED>
+static int clip_adam_graph_hp(const char* who, float* params, const float* grads, float* exp_avg, float* exp_avg_sq,
+                              const int64_t* seg_off, int32_t n_models, double* norms2, const double* hp, double beta1,
+                              double beta2, double eps, int32_t* step_dev, const int32_t* stop, void* stream) {
+  if (!params || !grads || !exp_avg || !exp_avg_sq || !seg_off || !norms2 || !step_dev || (GATED && !stop) || n_models < 1 ||
+      n_models > 254 || BAD_HP(hp)) {
+    snprintf(g_cadre_err, sizeof(g_cadre_err), "%s: bad argument (hp: device double[CADRE_HP_FIELDS], 8-byte aligned)", who);
+    return -1;
+  }
+  hipLaunchKernelGGL(adam_prep_kernel_hp, dim3(1), dim3(256), 0, ST(stream), norms2, n_models, step_dev, hp, beta1, beta2,
+                     GATED ? stop : nullptr);
+  dim3 grid(64, n_models), grid2(256, n_models);
+  const int64_t all = (int64_t)1 << 62;
+  hipLaunchKernelGGL(sqnorm_kernel, grid, dim3(256), 0, ST(stream), grads, seg_off, norms2, (int64_t)0, all);
+  hipLaunchKernelGGL(adam_dev_kernel_hp<GATED>, grid2, dim3(256), 0, ST(stream), params, grads, exp_avg, exp_avg_sq, seg_off,
+                     norms2, n_models, hp, (float)(1.0 - beta1), (float)beta2, (float)(1.0 - beta2), (float)eps, (int64_t)0, all,
+                     stop);
+  return (int)hipGetLastError();
+}
+
+template <bool GATED>
+static int clip_adam_pack_graph_hp(const char* who, float* params, const float* grads, float* exp_avg, float* exp_avg_sq,
+                                   const int64_t* seg_off, int32_t n_models, double* norms2, const double* hp, double beta1,
+                                   double beta2, double eps, int32_t* step_dev, int32_t n_lstm, int64_t lstm_str, int64_t o_whh,
+                                   int32_t H4, int32_t ldw, int32_t D, float* fwd, float* bwd, int64_t p_str, const int32_t* stop,
+                                   void* stream) {
+  if (!params || !grads || !exp_avg || !exp_avg_sq || !seg_off || !norms2 || !step_dev || !fwd || !bwd || (GATED && !stop) ||
+      n_models < 1 || n_models > 254 || n_lstm < 1 || n_lstm > n_models || BAD_HP(hp)) {
+    snprintf(g_cadre_err, sizeof(g_cadre_err), "%s: bad argument (hp: device double[CADRE_HP_FIELDS], 8-byte aligned)", who);
+    return -1;
+  }
+  if (ldw != 544 || D < 1 || D > ldw || H4 != 4 * D || (H4 & 3) || (o_whh & 3) || (lstm_str & 3) || (p_str & 3) ||
+      o_whh + (int64_t)H4 * ldw > lstm_str || p_str < (int64_t)((D + 15) / 16) * 4 * 34 * 256 ||
+      (((uintptr_t)params | (uintptr_t)fwd | (uintptr_t)bwd) & 15)) {
+    snprintf(g_cadre_err, sizeof(g_cadre_err),
+             "%s: built for W_hh [4 D][544] inside an LSTM block, 16-byte aligned (see cadre_pack_lstm_weights)", who);
+    return -1;
+  }
+  hipLaunchKernelGGL(adam_prep_kernel_hp, dim3(1), dim3(256), 0, ST(stream), norms2, n_models, step_dev, hp, beta1, beta2,
+                     GATED ? stop : nullptr);
+  const int64_t all = (int64_t)1 << 62;
+  hipLaunchKernelGGL(sqnorm_kernel, dim3(64, n_models), dim3(256), 0, ST(stream), grads, seg_off, norms2, (int64_t)0, all);
+  const float w1 = (float)(1.0 - beta1), b2 = (float)beta2, w2 = (float)(1.0 - beta2);
+  hipLaunchKernelGGL(adam_dev_skip_kernel_hp<GATED>, dim3(256, n_models), dim3(256), 0, ST(stream), params, grads, exp_avg,
+                     exp_avg_sq, seg_off, norms2, n_models, hp, w1, b2, w2, (float)eps, n_lstm, o_whh, (int64_t)H4 * ldw, stop);
+  whh_pack_t k{n_lstm, lstm_str, o_whh, H4, ldw, D, fwd, bwd, p_str};
+  const int blocks = (((H4 + 15) / 16) * (ldw / 16) + 7) / 8;
+  hipLaunchKernelGGL(adam_whh_pack_kernel_hp<GATED>, dim3(blocks, n_lstm), dim3(256), 0, ST(stream), params, grads, exp_avg,
+                     exp_avg_sq, norms2, n_models, hp, w1, b2, w2, (float)eps, k, stop);
+  return (int)hipGetLastError();
+}
+
+extern "C" int cadre_clip_adam_graph_hp(float* params, const float* grads, float* exp_avg, float* exp_avg_sq,
+                                        const int64_t* seg_off, int32_t n_models, double* norms2, const double* hp,
+                                        double beta1, double beta2, double eps, int32_t* step_dev, void* stream) {
+  return clip_adam_graph_hp<false>("cadre_clip_adam_graph_hp", params, grads, exp_avg, exp_avg_sq, seg_off, n_models, norms2, hp,
+                                   beta1, beta2, eps, step_dev, nullptr, stream);
+}
+
+extern "C" int cadre_clip_adam_graph_hp_gated(float* params, const float* grads, float* exp_avg, float* exp_avg_sq,
+                                              const int64_t* seg_off, int32_t n_models, double* norms2, const double* hp,
+                                              double beta1, double beta2, double eps, int32_t* step_dev, const int32_t* stop,
+                                              void* stream) {
+  return clip_adam_graph_hp<true>("cadre_clip_adam_graph_hp_gated", params, grads, exp_avg, exp_avg_sq, seg_off, n_models, norms2,
+                                  hp, beta1, beta2, eps, step_dev, stop, stream);
+}
+
+extern "C" int cadre_clip_adam_pack_graph_hp(float* params, const float* grads, float* exp_avg, float* exp_avg_sq,
+                                             const int64_t* seg_off, int32_t n_models, double* norms2, const double* hp,
+                                             double beta1, double beta2, double eps, int32_t* step_dev, int32_t n_lstm,
+                                             int64_t lstm_str, int64_t o_whh, int32_t H4, int32_t ldw, int32_t D, float* fwd,
+                                             float* bwd, int64_t p_str, void* stream) {
+  return clip_adam_pack_graph_hp<false>("cadre_clip_adam_pack_graph_hp", params, grads, exp_avg, exp_avg_sq, seg_off, n_models,
+                                        norms2, hp, beta1, beta2, eps, step_dev, n_lstm, lstm_str, o_whh, H4, ldw, D, fwd, bwd,
+                                        p_str, nullptr, stream);
+}
+
+extern "C" int cadre_clip_adam_pack_graph_hp_gated(float* params, const float* grads, float* exp_avg, float* exp_avg_sq,
+                                                   const int64_t* seg_off, int32_t n_models, double* norms2, const double* hp,
+                                                   double beta1, double beta2, double eps, int32_t* step_dev, int32_t n_lstm,
+                                                   int64_t lstm_str, int64_t o_whh, int32_t H4, int32_t ldw, int32_t D,
+                                                   float* fwd, float* bwd, int64_t p_str, const int32_t* stop, void* stream) {
+  return clip_adam_pack_graph_hp<true>("cadre_clip_adam_pack_graph_hp_gated", params, grads, exp_avg, exp_avg_sq, seg_off,
+                                       n_models, norms2, hp, beta1, beta2, eps, step_dev, n_lstm, lstm_str, o_whh, H4, ldw, D, fwd,
+                                       bwd, p_str, stop, stream);
+}
+
 // Per-model gradient norms of the step into its stats row: model m = kind * Z + head * C + c (kind 0 LSTM, 1 MLP towers;
 // Z = 2 C) goes to row[head * F + CADRE_PPO_STATS_FIELDS + kind * C + c].  sqrt(norms2[m]): the pre-clip total norm.
 __global__ void grad_norms_kernel(const double* norms2, int C, float* row, int F) {
@@ -2237,6 +2454,23 @@ __global__ void grad_norms_kernel(const double* norms2, int C, float* row, int F
 extern "C" int cadre_grad_norms(const double* norms2, int32_t C, float* stats_row, int32_t F, void* stream) {
   FAIL_IF(!norms2 || !stats_row || C < 1 || C > 63 || F < CADRE_PPO_STATS_FIELDS + 2 * C, "cadre_grad_norms: bad argument");
   hipLaunchKernelGGL(grad_norms_kernel, dim3(1), dim3(256), 0, ST(stream), norms2, C, stats_row, F);
+  return (int)hipGetLastError();
+}
+
+// cadre_grad_norms that also reports the learning rate the step used: row[CADRE_PPO_STATS_LR] of head 0 = (float)hp[LR]
+// (the launch follows the optimiser step and precedes the next loss launch, so the block still holds the step's value).
+__global__ void grad_norms_hp_kernel(const double* norms2, int C, float* row, int F, const double* hp) {
+  const int m = threadIdx.x, Z = 2 * C;
+  if (m == 255) row[CADRE_PPO_STATS_LR] = (float)hp[CADRE_HP_LR];
+  if (m >= 2 * Z) return;
+  const int kind = m / Z, g = m - kind * Z, head = g / C, c = g - head * C;
+  row[head * F + CADRE_PPO_STATS_FIELDS + kind * C + c] = (float)sqrt(norms2[m]);
+}
+
+extern "C" int cadre_grad_norms_hp(const double* norms2, int32_t C, float* stats_row, int32_t F, const double* hp, void* stream) {
+  FAIL_IF(!norms2 || !stats_row || C < 1 || C > 63 || F < CADRE_PPO_STATS_FIELDS + 2 * C || BAD_HP(hp),
+          "cadre_grad_norms_hp: bad argument");
+  hipLaunchKernelGGL(grad_norms_hp_kernel, dim3(1), dim3(256), 0, ST(stream), norms2, C, stats_row, F, hp);
   return (int)hipGetLastError();
 }
 
@@ -2307,6 +2541,30 @@ extern "C" int cadre_clip_adam_apply(float* params, const float* grads, float* e
   hipLaunchKernelGGL(adam_dev_kernel, dim3(256, n_models), dim3(256), 0, ST(stream), params, grads, exp_avg - rlo,
                      exp_avg_sq - rlo, seg_off, norms2, n_models, (float)max_norm, (float)(1.0 - beta1), (float)beta2,
                      (float)(1.0 - beta2), (float)eps, rlo, rhi);
+  return (int)hipGetLastError();
+}
+
+extern "C" int cadre_clip_adam_norms_hp(const float* grads, const int64_t* seg_off, int32_t n_models, double* norms2,
+                                        const double* hp, double beta1, double beta2, int32_t* step_dev, int64_t rlo,
+                                        int64_t rhi, void* stream) {
+  FAIL_IF(!grads || !seg_off || !norms2 || !step_dev || n_models < 1 || n_models > 254 || rlo < 0 || rhi <= rlo ||
+              (rlo & 3) || (rhi & 3) || BAD_HP(hp),
+          "cadre_clip_adam_norms_hp: bad argument (shard bounds must be multiples of 4 elements; hp 8-byte aligned)");
+  hipLaunchKernelGGL(adam_prep_kernel_hp, dim3(1), dim3(256), 0, ST(stream), norms2, n_models, step_dev, hp, beta1, beta2,
+                     (const int32_t*)nullptr);
+  hipLaunchKernelGGL(sqnorm_kernel, dim3(64, n_models), dim3(256), 0, ST(stream), grads, seg_off, norms2, rlo, rhi);
+  return (int)hipGetLastError();
+}
+
+extern "C" int cadre_clip_adam_apply_hp(float* params, const float* grads, float* exp_avg, float* exp_avg_sq,
+                                        const int64_t* seg_off, int32_t n_models, const double* norms2, const double* hp,
+                                        double beta1, double beta2, double eps, int64_t rlo, int64_t rhi, void* stream) {
+  FAIL_IF(!params || !grads || !exp_avg || !exp_avg_sq || !seg_off || !norms2 || n_models < 1 || n_models > 254 ||
+              rlo < 0 || rhi <= rlo || (rlo & 3) || (rhi & 3) || BAD_HP(hp),
+          "cadre_clip_adam_apply_hp: bad argument (shard bounds must be multiples of 4 elements; hp 8-byte aligned)");
+  hipLaunchKernelGGL(adam_dev_kernel_hp<false>, dim3(256, n_models), dim3(256), 0, ST(stream), params, grads, exp_avg - rlo,
+                     exp_avg_sq - rlo, seg_off, norms2, n_models, hp, (float)(1.0 - beta1), (float)beta2, (float)(1.0 - beta2),
+                     (float)eps, rlo, rhi, (const int32_t*)nullptr);
   return (int)hipGetLastError();
 }
 

@@ -99,6 +99,10 @@ SYMBOLS = {
     "cadre_ppo_loss_stats": [vp, i64, i64, vp, i64, i64, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, f32, f32, f32, f32, f32, vp, vp, vp,
                              vp, vp, vp, i32, vp, f32, vp, vp],
     "cadre_grad_norms": [vp, i32, vp, i32, vp],
+    "cadre_ppo_loss_hp": [vp, i64, i64, vp, i64, i64, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, vp, f32, vp, vp, vp, vp, vp, vp],
+    "cadre_ppo_loss_stats_hp": [vp, i64, i64, vp, i64, i64, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, vp, f32, vp, vp, vp, vp, vp,
+                                vp, i32, vp, f32, vp, vp],
+    "cadre_grad_norms_hp": [vp, i32, vp, i32, vp, vp],
     "cadre_explained_variance": [vp, i32, vp, vp],
     "cadre_sample": [vp, i64, vp, i64, i32, i32, vp, vp, vp],
     "cadre_act_windows": [vp, i64, i32, vp, i64, i32, vp, vp, vp, vp, i32, i32, vp, i64, i32, vp, i64, vp],
@@ -114,6 +118,13 @@ SYMBOLS = {
                                          i64, vp, vp],
     "cadre_clip_adam_norms": [vp, vp, i32, vp, f64, f64, f64, vp, i64, i64, vp],
     "cadre_clip_adam_apply": [vp, vp, vp, vp, vp, i32, vp, f64, f64, f64, f64, i64, i64, vp],
+    "cadre_clip_adam_graph_hp": [vp, vp, vp, vp, vp, i32, vp, vp, f64, f64, f64, vp, vp],
+    "cadre_clip_adam_graph_hp_gated": [vp, vp, vp, vp, vp, i32, vp, vp, f64, f64, f64, vp, vp, vp],
+    "cadre_clip_adam_pack_graph_hp": [vp, vp, vp, vp, vp, i32, vp, vp, f64, f64, f64, vp, i32, i64, i64, i32, i32, i32, vp, vp, i64, vp],
+    "cadre_clip_adam_pack_graph_hp_gated": [vp, vp, vp, vp, vp, i32, vp, vp, f64, f64, f64, vp, i32, i64, i64, i32, i32, i32, vp, vp,
+                                            i64, vp, vp],
+    "cadre_clip_adam_norms_hp": [vp, vp, i32, vp, vp, f64, f64, vp, i64, i64, vp],
+    "cadre_clip_adam_apply_hp": [vp, vp, vp, vp, vp, i32, vp, vp, f64, f64, f64, i64, i64, vp],
 }
 # entry points of the A/B build only (include/cadre_hip_ab.h; CADRE_BUILD_AB=1 python -m cadre_amd.build, then
 # CADRE_HIP_LIB=.../libcadre_hip_ab.so): bound when the loaded library has them
@@ -164,6 +175,11 @@ def lib():
         _lib = L
     return _lib
 
+
+# the hyper-parameter block of the `_hp` entry points (CADRE_HP_* of include/cadre_hip.h): field name -> index
+HP_FIELDS = 16
+HP = dict(lr=0, clip=1, value_coeff=2, clip_coeff=3, ent_coeff=4, max_grad_norm=5, desired_kl=6, lr_min=7, lr_max=8, lr_factor=9)
+PPO_STATS_LR = 7      # CADRE_PPO_STATS_LR: field of head 0 of a stats row that cadre_grad_norms_hp fills with the step's lr
 
 PPO_STATS_FIELDS = 8  # CADRE_PPO_STATS_FIELDS (include/cadre_hip.h): loss diagnostics per head before the gradient norms
 

@@ -13,13 +13,40 @@ on one stream, replayed as a hipGraph.
 """
 import os
 
+import numpy as np
 import torch
 
 from . import hip
 
+_UPDATE_PARTS = ("all", "front", "mid", "back")
+
+
+def _hyper_property(attr, field):
+    """clip / vc / cc / ec: the captured update graphs hold these BY VALUE.  In device-hyper mode an assignment goes to the
+    block (set_hyper); otherwise a changed value drops the captured update graphs, so the next step runs — and is then
+    re-captured — with the new value instead of silently replaying the old one."""
+    def get(self):
+        return getattr(self, attr)
+
+    def set_(self, value):
+        value = float(value)
+        old = getattr(self, attr, None)
+        setattr(self, attr, value)
+        if old is None or value == old:
+            return
+        if self._hp_on:
+            self.set_hyper(**{field: value})
+        else:
+            self._drop_update_graphs()
+    return property(get, set_)
+
 
 class PPOLearnerHIP:
     SORT_MIN_B = 64
+    clip = _hyper_property("_clip", "clip")
+    vc = _hyper_property("_vc", "value_coeff")
+    cc = _hyper_property("_cc", "clip_coeff")
+    ec = _hyper_property("_ec", "ent_coeff")
 
     def sorted_rows(self, B):
         """Row-sorted update (rows of a minibatch grouped by command; every kernel of the step then works on exactly
@@ -30,10 +57,17 @@ class PPOLearnerHIP:
 
     def __init__(self, arena, clip=0.1, value_coeff=0.1, clip_coeff=1.0, ent_coeff=0.01, seq_length=8):
         self.a = arena
-        self.clip, self.vc, self.cc, self.ec = float(clip), float(value_coeff), float(clip_coeff), float(ent_coeff)
-        self.S = seq_length
         self._ws = {}
         self._graphs = {}
+        # device-resident hyper-parameters (opt-in, set_device_hyper): the kernels read lr, clip, the loss coefficients and
+        # max_grad_norm from a block in device memory, so the captured graphs stay static whatever the values do
+        self._hp_on = False
+        self._hp = None            # device float64 [hip.HP_FIELDS]; allocated once (captured graphs hold its address)
+        self._hp_host = None       # host mirror (numpy float64): what the block holds, except lr while the controller moves it
+        self._adaptive = None      # (desired_kl, factor, lr_min, lr_max) while the KL-adaptive learning rate is on
+        self._hp_moved = False     # clip or a loss coefficient changed in device-hyper mode: by-value update graphs are stale
+        self.clip, self.vc, self.cc, self.ec = float(clip), float(value_coeff), float(clip_coeff), float(ent_coeff)
+        self.S = seq_length
         self._wp = None            # recurrent weights in MFMA fragment order (forward, backward), re-packed per optimiser step
         self._wp_key = None
         self.pack_outside_capture = False      # act() graphs: the copies are refreshed eagerly before each replay
@@ -85,13 +119,170 @@ class PPOLearnerHIP:
         self._norm_row = None
 
     def _loss_stats(self):
-        return self.stats or self.target_kl is not None
+        return self.stats or self.target_kl is not None or self._adaptive is not None
 
     def _mode_key(self):
-        """hipGraph key suffix of the update modes: () when both are off (today's graphs)."""
-        if not self._loss_stats():
-            return ()
-        return (("stats", self.target_kl),)
+        """hipGraph key suffix of the update modes: () when all are off (today's graphs).  Device-hyper mode is a mode
+        (("hp",)); the VALUES in the block are not part of any key."""
+        key = (("stats", self.target_kl),) if self._loss_stats() else ()
+        return key + ((("hp",),) if self._hp_on else ())
+
+    # ------------------------------------------------------------------ device-resident hyper-parameters
+    def _drop_update_graphs(self, hp=False):
+        """Forget the captured update graphs of the by-value (hp=False) or the device-hyper (hp=True) mode; the optimiser
+        graphs are keyed on their values and stay.  Waits for the device first: a graph may still be replaying."""
+        def mine(k):
+            k = k[1:] if k and k[0] == "warm" else k
+            return bool(k) and k[0] in _UPDATE_PARTS and (("hp",) in k) == hp
+        drop = [k for k in self._graphs if mine(k)]
+        if drop:
+            torch.cuda.synchronize()
+            for k in drop:
+                del self._graphs[k]
+
+    @property
+    def device_hyper(self):
+        return self._hp_on
+
+    def set_device_hyper(self, on=True):
+        """on: lr, clip, value_coeff, clip_coeff, ent_coeff and max_grad_norm live in a block of device memory (hip.HP) that
+        the loss and optimiser kernels read when they RUN (the `_hp` entry points); set_hyper() changes them with one
+        asynchronous copy, and captured graphs are replayed unchanged.  The block starts from the learner's current clip and
+        coefficients, lr 3e-4 and max_grad_norm 250 (clip_adam's defaults; clip_adam(lr=, max_grad_norm=) updates them).
+        With equal values every result is bit-identical to the by-value mode.  off: back to by-value arguments."""
+        on = bool(on)
+        if on == self._hp_on:
+            return
+        if not on:
+            if self._adaptive is not None:
+                self.set_adaptive_lr(None)
+            self._hp_on = False
+            if self._hp_moved:                 # (the by-value graphs were captured before the loss scalars moved)
+                self._drop_update_graphs()
+                self._hp_moved = False
+            return
+        if self._hp is None:
+            self._hp = torch.zeros(hip.HP_FIELDS, dtype=torch.float64, device=self.a.device)
+            self._hp_host = np.zeros(hip.HP_FIELDS, dtype=np.float64)
+            # two pinned staging buffers, used in turn: one is rewritten only after the copy that last read it has finished
+            self._hp_stage = [torch.zeros(hip.HP_FIELDS, dtype=torch.float64).pin_memory() for _ in range(2)]
+            self._hp_events = [None, None]
+            self._hp_i = 0
+            self._hp_host[hip.HP["lr"]], self._hp_host[hip.HP["max_grad_norm"]] = 3e-4, 250.0
+        m = self._hp_host
+        m[hip.HP["clip"]], m[hip.HP["value_coeff"]] = self._clip, self._vc
+        m[hip.HP["clip_coeff"]], m[hip.HP["ent_coeff"]] = self._cc, self._ec
+        if np.isnan(m[hip.HP["lr"]]):
+            m[hip.HP["lr"]] = 3e-4
+        self._hp_on = True
+        self._hp_upload(0, hip.HP_FIELDS)
+
+    def _hp_upload(self, lo, hi):
+        """Fields [lo, hi) of the mirror into the block: one asynchronous host-to-device copy on the current stream."""
+        if torch.cuda.is_current_stream_capturing():
+            raise hip.CadreHipError("set_hyper inside a stream capture: the copy would be baked into the graph")
+        i = self._hp_i
+        self._hp_i ^= 1
+        if self._hp_events[i] is not None:
+            self._hp_events[i].synchronize()   # (the upload before the last one: finished long ago in practice)
+        stage = self._hp_stage[i]
+        stage.numpy()[lo:hi] = self._hp_host[lo:hi]
+        self._hp[lo:hi].copy_(stage[lo:hi], non_blocking=True)
+        ev = torch.cuda.Event()
+        ev.record()
+        self._hp_events[i] = ev
+
+    def hyper(self, name):
+        """The host mirror's value of a block field (hip.HP).  "lr" is the last value SET while the KL-adaptive controller
+        moves it on the device (the value each step used is in the step's stats row), NaN after set_adaptive_lr(None) until
+        the next clip_adam / set_hyper supplies one."""
+        self._need_hp("hyper")
+        return float(self._hp_host[hip.HP[name]])
+
+    def _need_hp(self, what):
+        if not self._hp_on:
+            raise hip.CadreHipError("%s needs device-hyper mode: call set_device_hyper() first" % what)
+
+    def set_hyper(self, lr=None, clip=None, ent_coeff=None, value_coeff=None, clip_coeff=None, max_grad_norm=None):
+        """New values for the given block fields: the mirror is updated and ONE asynchronous host-to-device copy (of the
+        span of fields that changed) is enqueued on the current stream — no synchronisation, no new graph.  Steps enqueued
+        afterwards use the new values.  An explicit lr also resets the KL-adaptive controller's current value."""
+        self._need_hp("set_hyper")
+        new = dict(lr=lr, clip=clip, ent_coeff=ent_coeff, value_coeff=value_coeff, clip_coeff=clip_coeff,
+                   max_grad_norm=max_grad_norm)
+        idx = []
+        for name, v in new.items():
+            if v is None:
+                continue
+            v = float(v)
+            if not np.isfinite(v):
+                raise ValueError("set_hyper: %s=%r" % (name, v))
+            i = hip.HP[name]
+            if v != self._hp_host[i]:             # (a NaN mirror entry — lr after the controller — always differs)
+                self._hp_host[i] = v
+                idx.append(i)
+        # the learner's by-value attributes follow (set_device_hyper(False) continues from them)
+        m = self._hp_host
+        self._clip, self._vc = float(m[hip.HP["clip"]]), float(m[hip.HP["value_coeff"]])
+        self._cc, self._ec = float(m[hip.HP["clip_coeff"]]), float(m[hip.HP["ent_coeff"]])
+        if any(hip.HP["clip"] <= i <= hip.HP["ent_coeff"] for i in idx):
+            self._hp_moved = True
+        if idx:
+            # (fields between two changed ones equal the block's already — lr, which the controller moves, is field 0: it is
+            #  inside the span only when it is itself being set)
+            self._hp_upload(min(idx), max(idx) + 1)
+
+    def set_adaptive_lr(self, desired_kl, factor=1.5, lr_min=1e-5, lr_max=1e-2, lr=None):
+        """KL-adaptive learning rate, on the device (switches to device-hyper mode and implies the stats loss kernel): after
+        a minibatch's loss and before its optimiser step, with kl = max(approx_kl steer, approx_kl throttle) of that
+        minibatch,  kl > 2 desired_kl: lr = max(lr_min, lr / factor);  0 < kl < desired_kl / 2: lr = min(lr_max, lr * factor)
+        (float64; the rsl_rl / RL-Games rule).  The target_kl gate is checked first: once it has fired, lr stays.  `lr`: the
+        starting value (None: the block's current one — the adapted value carries over).  While the controller is on,
+        clip_adam's `lr` argument is ignored.  set_adaptive_lr(None) switches it off; the next clip_adam(lr=) then sets lr.
+        Refused with several ranks (each rank would move its own lr) and by the sharded optimiser step."""
+        if desired_kl is None:
+            if self._adaptive is not None:
+                self._adaptive = None
+                self._hp_host[hip.HP["desired_kl"]] = 0.0
+                self._hp_host[hip.HP["lr"]] = float("nan")      # (the device holds the adapted value: unknown here)
+                self._hp_upload(hip.HP["desired_kl"], hip.HP["desired_kl"] + 1)
+            return
+        desired_kl, factor, lr_min, lr_max = float(desired_kl), float(factor), float(lr_min), float(lr_max)
+        if not (desired_kl > 0.0 and np.isfinite(desired_kl)):
+            raise ValueError("adaptive lr: desired_kl must be > 0 (got %r)" % (desired_kl,))
+        if not (factor > 1.0 and np.isfinite(factor)):
+            raise ValueError("adaptive lr: factor must be > 1 (got %r)" % (factor,))
+        if not (0.0 < lr_min <= lr_max and np.isfinite(lr_max)):
+            raise ValueError("adaptive lr: need 0 < lr_min <= lr_max (got %r, %r)" % (lr_min, lr_max))
+        if lr is not None and not (float(lr) > 0.0 and np.isfinite(float(lr))):
+            raise ValueError("adaptive lr: lr must be > 0 (got %r)" % (lr,))
+        import torch.distributed as dist
+        if dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1:
+            raise hip.CadreHipError("adaptive lr needs a single rank (world size %d): the controller is per rank and every "
+                                    "rank would move its own lr" % dist.get_world_size())
+        if getattr(self.a, "_shard", None) is not None:
+            raise hip.CadreHipError("adaptive lr is not available for the sharded optimiser step (several ranks)")
+        self.set_device_hyper(True)
+        m = self._hp_host
+        lo = hip.HP["desired_kl"]
+        if lr is not None:                         # (None: whatever the block holds carries over)
+            m[hip.HP["lr"]] = float(lr)
+            lo = 0
+        m[hip.HP["desired_kl"]], m[hip.HP["lr_factor"]] = desired_kl, factor
+        m[hip.HP["lr_min"]], m[hip.HP["lr_max"]] = lr_min, lr_max
+        self._adaptive = (desired_kl, factor, lr_min, lr_max)
+        self._hp_upload(lo, hip.HP["lr_factor"] + 1)
+
+    def _sync_hyper(self, lr, max_grad_norm):
+        """Device-hyper mode: the optimiser step's lr / max_grad_norm arguments against the mirror; a difference becomes one
+        set_hyper (a torch lr scheduler on the chief's optimizer just works, at replay speed)."""
+        upd = {}
+        if float(max_grad_norm) != self._hp_host[hip.HP["max_grad_norm"]]:
+            upd["max_grad_norm"] = max_grad_norm
+        if self._adaptive is None and float(lr) != self._hp_host[hip.HP["lr"]]:
+            upd["lr"] = lr
+        if upd:
+            self.set_hyper(**upd)
 
     # ------------------------------------------------------------------ workspace
     def workspace(self, B, Z=None, S=None):
@@ -344,7 +535,22 @@ class PPOLearnerHIP:
         O3, dO3 = w["O3"], w["dO3"]
         if front:
             self._forward(w, B, (0, 1, Z), C, seg=seg, fused_mlp=True)
-        if front and self._loss_stats():
+        if front and self._hp_on:
+            loss_args = (hip.ptr(O3), NP, 2 * B * NP, hip.ptr(O3[1]), NP, 2 * B * NP,
+                         hip.ptr(w["actions"]), hip.ptr(w["commands"]), hip.ptr(w["old_values"]),
+                         hip.ptr(w["returns"]), hip.ptr(w["old_logp"]), hip.ptr(w["adv"]), B, C,
+                         a.n_out[0], a.n_out[1], hip.ptr(self._hp), inv_b,
+                         hip.ptr(w["losses"]), hip.ptr(dO3), hip.ptr(dO3[1]), hip.ptr(w["loss_scratch"]),
+                         hip.ptr(w["sync"][Z * S:]))
+            if self._loss_stats():
+                srow, sscr = self._stats_ws(w, B)
+                tkl = 0.0 if self.target_kl is None else self.target_kl
+                hip.check(L.cadre_ppo_loss_stats_hp(*loss_args, hip.ptr(srow), srow.shape[1], hip.ptr(sscr), tkl,
+                                                    hip.ptr(self._stop) if self.target_kl is not None else None, st),
+                          "cadre_ppo_loss_stats_hp")
+            else:
+                hip.check(L.cadre_ppo_loss_hp(*loss_args, st), "cadre_ppo_loss_hp")
+        elif front and self._loss_stats():
             srow, sscr = self._stats_ws(w, B)
             tkl = 0.0 if self.target_kl is None else self.target_kl
             hip.check(L.cadre_ppo_loss_stats(hip.ptr(O3), NP, 2 * B * NP, hip.ptr(O3[1]), NP, 2 * B * NP,
@@ -435,12 +641,29 @@ class PPOLearnerHIP:
         a.step += 1                 # (with the KL gate armed: steps attempted — the learner section reconciles it at its sync)
         fused = self.fused_pack
         gated = self.target_kl is not None
-        key = ("adam", float(lr), float(max_grad_norm), float(betas[0]), float(betas[1]), float(eps), fused) + (("gated",) if gated else ())
+        hp = self._hp_on
+        if hp:      # lr and max_grad_norm live in the block: a new value is a copy, not a new graph
+            self._sync_hyper(lr, max_grad_norm)
+            key = ("adam", "hp", float(betas[0]), float(betas[1]), float(eps), fused) + (("gated",) if gated else ())
+        else:
+            key = ("adam", float(lr), float(max_grad_norm), float(betas[0]), float(betas[1]), float(eps), fused) + (("gated",) if gated else ())
         if fused:
             self._alloc_wp()
 
+        def body_hp():
+            L = hip.lib()
+            head = (hip.ptr(a.params), hip.ptr(a.grads), hip.ptr(a.exp_avg), hip.ptr(a.exp_avg_sq), hip.ptr(a.seg_off),
+                    2 * a.Z, hip.ptr(a.norms2), hip.ptr(self._hp), key[2], key[3], key[4], hip.ptr(a.step_dev))
+            pack = (a.Z, a.size_L, a.o_whh, a.H4, a.DP, a.D, hip.ptr(self._wp[0]), hip.ptr(self._wp[1]),
+                    self._wp.stride(1)) if fused else ()
+            tail = ((hip.ptr(self._stop),) if gated else ()) + (hip.stream(),)
+            name = "cadre_clip_adam_%sgraph_hp%s" % ("pack_" if fused else "", "_gated" if gated else "")
+            hip.check(getattr(L, name)(*(head + pack + tail)), name)
+
         def body():
-            if gated and fused:
+            if hp:
+                body_hp()
+            elif gated and fused:
                 hip.check(hip.lib().cadre_clip_adam_pack_graph_gated(
                     hip.ptr(a.params), hip.ptr(a.grads), hip.ptr(a.exp_avg), hip.ptr(a.exp_avg_sq), hip.ptr(a.seg_off),
                     2 * a.Z, hip.ptr(a.norms2), key[2], key[1], key[3], key[4], key[5], hip.ptr(a.step_dev),
@@ -492,6 +715,9 @@ class PPOLearnerHIP:
         a = self.a
         if self.target_kl is not None:
             raise hip.CadreHipError("target_kl: the KL gate is not available for the sharded optimiser step (several ranks)")
+        if self._adaptive is not None:
+            raise hip.CadreHipError("adaptive lr is not available for the sharded optimiser step (several ranks: each rank "
+                                    "would move its own lr)")
         if getattr(a, "_shard", None) != (lo, hi):
             if a.step:
                 raise hip.CadreHipError("the optimiser shard changed after %d steps (Adam state is per shard)" % a.step)
@@ -500,6 +726,17 @@ class PPOLearnerHIP:
             a.exp_avg_sq = torch.zeros(hi - lo, device=a.device)
         a.step += 1
         L, st, nm = hip.lib(), hip.stream(), 2 * a.Z
+        if self._hp_on:
+            self._sync_hyper(lr, max_grad_norm)
+            hip.check(L.cadre_clip_adam_norms_hp(hip.ptr(a.grads), hip.ptr(a.seg_off), nm, hip.ptr(a.norms2), hip.ptr(self._hp),
+                                                 float(betas[0]), float(betas[1]), hip.ptr(a.step_dev), lo, hi, st),
+                      "cadre_clip_adam_norms_hp")
+            all_reduce_norms(a.norms2[:nm])
+            hip.check(L.cadre_clip_adam_apply_hp(hip.ptr(a.params), hip.ptr(a.grads), hip.ptr(a.exp_avg), hip.ptr(a.exp_avg_sq),
+                                                 hip.ptr(a.seg_off), nm, hip.ptr(a.norms2), hip.ptr(self._hp),
+                                                 float(betas[0]), float(betas[1]), float(eps), lo, hi, st),
+                      "cadre_clip_adam_apply_hp")
+            return self._write_norms()
         hip.check(L.cadre_clip_adam_norms(hip.ptr(a.grads), hip.ptr(a.seg_off), nm, hip.ptr(a.norms2), float(lr),
                                           float(betas[0]), float(betas[1]), hip.ptr(a.step_dev), lo, hi, st),
                   "cadre_clip_adam_norms")
@@ -514,7 +751,10 @@ class PPOLearnerHIP:
         """The per-model gradient norms of the optimiser step just enqueued into the pending stats row (one launch after
         the step's graph; nothing read on the host)."""
         row, self._norm_row = self._norm_row, None
-        if row is not None:
+        if row is not None and self._hp_on:      # (also the learning rate the step used: field hip.PPO_STATS_LR of head 0)
+            hip.check(hip.lib().cadre_grad_norms_hp(hip.ptr(self.a.norms2), self.a.C, hip.ptr(row), row.shape[-1],
+                                                    hip.ptr(self._hp), hip.stream()), "cadre_grad_norms_hp")
+        elif row is not None:
             hip.check(hip.lib().cadre_grad_norms(hip.ptr(self.a.norms2), self.a.C, hip.ptr(row), row.shape[-1], hip.stream()),
                       "cadre_grad_norms")
 

@@ -25,7 +25,10 @@ def chief_step(shared_grad_buffers, optimizer, max_grad_norm, lr=None, zero_grad
     `zero_grads=True` is the reference's `shared_grad_buffers.reset()` (models.py:255-258): the gradient arena is
     cleared.  A caller whose NEXT writer of the arena is the fused `update_policy` — which writes every element, it
     does not accumulate — may pass False and save the 80 MB fill (`learner_section` does; the stand-alone modules'
-    autograd path and foreign arenas ACCUMULATE into `p.grad` / the arena and need the fill)."""
+    autograd path and foreign arenas ACCUMULATE into `p.grad` / the arena and need the fill).
+    With the learner in device-hyper mode (PPOLearnerHIP.set_device_hyper) `lr` and `max_grad_norm` are values in device
+    memory, not graph keys: an optimizer whose lr a torch scheduler moves costs one small copy per change and the
+    captured step is replayed.  While the KL-adaptive learning rate is on, the lr read here is ignored."""
     arena = shared_grad_buffers.arena
     if optimizer is not None:
         lr, betas, eps = _hyper(optimizer)

@@ -53,6 +53,112 @@ def _target_kl(train_cfg, shared_grad_buffers, in_process_chief=True):
     return tkl
 
 
+# ----------------------------------------------------------------------------- hyper-parameter schedules, KL-adaptive lr
+SCHEDULED = ("lr", "clip", "ent_coeff")
+
+
+def schedule_value(spec, episode, max_episode):
+    """Value of a schedule at `episode` (0 .. max_episode - 1), in float64 on the host.  spec: a number (constant),
+    ("linear", start, end): start + (end - start) * episode / max_episode, or a callable f(episode / max_episode)."""
+    if isinstance(max_episode, bool) or not isinstance(max_episode, (int, np.integer)) or max_episode < 1:
+        raise ValueError("schedule: max_episode must be a positive integer (got %r)" % (max_episode,))
+    if isinstance(episode, bool) or not isinstance(episode, (int, np.integer)) or not 0 <= episode < max_episode:
+        raise ValueError("schedule: episode %r outside 0 .. %d" % (episode, max_episode - 1))
+    frac = float(episode) / float(max_episode)
+    if callable(spec):
+        v = spec(frac)
+    elif isinstance(spec, (tuple, list)):
+        if len(spec) != 3 or spec[0] != "linear":
+            raise ValueError("schedule: expected (\"linear\", start, end), got %r" % (spec,))
+        try:
+            start, end = float(spec[1]), float(spec[2])
+        except (TypeError, ValueError):
+            raise ValueError("schedule: start / end of %r are not numbers" % (spec,))
+        v = start + (end - start) * float(episode) / float(max_episode)
+    elif isinstance(spec, bool) or not isinstance(spec, (int, float, np.integer, np.floating)):
+        raise ValueError("schedule: expected a number, (\"linear\", start, end) or a callable, got %r" % (spec,))
+    else:
+        v = spec
+    try:
+        v = float(v)
+    except (TypeError, ValueError):
+        raise ValueError("schedule: %r gave %r, not a number" % (spec, v))
+    if not np.isfinite(v):
+        raise ValueError("schedule: %r gave %r at episode %d" % (spec, v, episode))
+    return v
+
+
+def _schedules(train_cfg):
+    sch = _get(train_cfg, "schedules")
+    if sch is None:
+        return {}
+    sch = dict(sch)
+    unknown = sorted(set(sch) - set(SCHEDULED))
+    if unknown:
+        raise ValueError("train_cfg.schedules: unknown keys %r (known: %r)" % (unknown, SCHEDULED))
+    return sch
+
+
+def _adaptive_lr(train_cfg, shared_grad_buffers, in_process_chief=True):
+    """train_cfg["adaptive_lr"] = {"desired_kl", "factor", "min", "max"} (absent / None: nothing) as the keyword arguments of
+    PPOLearnerHIP.set_adaptive_lr.  The controller is a device value of THIS rank: like target_kl it is refused with
+    several ranks and with a chief in another process; it excludes a schedule for lr."""
+    cfg = _get(train_cfg, "adaptive_lr")
+    if cfg is None:
+        return None
+    cfg = dict(cfg)
+    unknown = sorted(set(cfg) - {"desired_kl", "factor", "min", "max"})
+    if unknown or "desired_kl" not in cfg:
+        raise ValueError("train_cfg.adaptive_lr: needs desired_kl, optional factor / min / max (got %r)" % (sorted(cfg),))
+    if "lr" in _schedules(train_cfg):
+        raise ValueError("train_cfg.adaptive_lr excludes train_cfg.schedules[\"lr\"]: one of them owns the learning rate")
+    kw = dict(desired_kl=float(cfg["desired_kl"]), factor=float(cfg.get("factor", 1.5)), lr_min=float(cfg.get("min", 1e-5)),
+              lr_max=float(cfg.get("max", 1e-2)))
+    if not kw["desired_kl"] > 0.0 or not kw["factor"] > 1.0 or not 0.0 < kw["lr_min"] <= kw["lr_max"]:
+        raise ValueError("train_cfg.adaptive_lr: need desired_kl > 0, factor > 1, 0 < min <= max (got %r)" % (cfg,))
+    if shared_grad_buffers is not None and shared_grad_buffers.dist_world() > 1:
+        raise hip.CadreHipError("train_cfg.adaptive_lr needs a single rank (world size %d): the controller is per rank and "
+                                "every rank would move its own lr" % shared_grad_buffers.dist_world())
+    if not in_process_chief:
+        raise hip.CadreHipError("train_cfg.adaptive_lr needs the in-process chief (the learning rate lives on this process's device)")
+    return kw
+
+
+def apply_schedules(agent, train_cfg, episode, max_episode=None):
+    """train_cfg["schedules"] at `episode`: the learner goes to device-hyper mode and gets the episode's values in one
+    set_hyper (an asynchronous copy; the captured graphs are replayed as they are).  Returns the values set."""
+    sch = _schedules(train_cfg)
+    if not sch:
+        return {}
+    max_episode = _get(train_cfg, "max_episode") if max_episode is None else max_episode
+    vals = {k: schedule_value(spec, episode, max_episode) for k, spec in sch.items()}
+    agent.learner.set_device_hyper(True)
+    agent.learner.set_hyper(**vals)
+    return vals
+
+
+def _section_hyper(agent, train_cfg, shared_grad_buffers, in_process_chief, optimizer):
+    """Before a learner section: arm the KL-adaptive lr from train_cfg (the adapted lr carries over from the section before
+    when the settings are the same).  Returns the lr the section hands to chief_step: the scheduled one when
+    train_cfg.schedules owns lr, else train_cfg.lr."""
+    alr = _adaptive_lr(train_cfg, shared_grad_buffers, in_process_chief)
+    lr = _get(train_cfg, "lr")
+    if alr is not None:
+        if optimizer is not None:
+            lr = optimizer.param_groups[0]["lr"]
+        want = (alr["desired_kl"], alr["factor"], alr["lr_min"], alr["lr_max"])
+        if agent.learner._adaptive != want:
+            first = agent.learner._adaptive is None
+            agent.learner.set_adaptive_lr(lr=(3e-4 if lr is None else float(lr)) if first else None, **alr)
+    elif "lr" in _schedules(train_cfg):
+        if optimizer is not None:
+            raise ValueError("train_cfg.schedules[\"lr\"] with an optimizer: the optimizer's lr would override the schedule")
+        if not agent.learner.device_hyper:
+            raise hip.CadreHipError("train_cfg.schedules: call apply_schedules(agent, train_cfg, episode) before the section")
+        lr = agent.learner.hyper("lr")
+    return lr
+
+
 class _SectionStats:
     """Device side of a section's diagnostics: one stats row per minibatch step, the explained variance of every storage,
     and the host-side dict filled after the section's single sync."""
@@ -92,6 +198,8 @@ class _SectionStats:
             for r in tab.tolist():
                 d = {f: (r[0][k], r[1][k]) for k, f in enumerate(STAT_FIELDS)}
                 d["applied"] = r[0][6] != 0
+                if lrn.device_hyper:               # (the lr the step's optimiser used; 0 where the row never got a step)
+                    d["lr"] = r[0][hip.PPO_STATS_LR]
                 # model m = kind * 2C + head * C + c (arena segment order) -> row[head][FIELDS + kind * C + c]
                 d["grad_norm"] = [r[(m % (2 * C)) // C][hip.PPO_STATS_FIELDS + (m // (2 * C)) * C + m % C]
                                   for m in range(len(names))]
@@ -114,11 +222,14 @@ def stats_line(episode, stats):
     rows = stats["rows"]
     mean = lambda f, h: float(np.mean([r[f][h] for r in rows]))
     ev = np.array(stats["explained_variance"], dtype=np.float64)
-    return ("Episode: {}, approx kl: {:.6f}/{:.6f}, clip fraction: {:.4f}/{:.4f}, explained variance: {:.4f}/{:.4f}, "
+    line = ("Episode: {}, approx kl: {:.6f}/{:.6f}, clip fraction: {:.4f}/{:.4f}, explained variance: {:.4f}/{:.4f}, "
             "updates applied: {}/{}, max grad norm: {:.4f}").format(
         episode, mean("approx_kl", 0), mean("approx_kl", 1), mean("clip_fraction", 0), mean("clip_fraction", 1),
         float(np.mean(ev[:, 0])), float(np.mean(ev[:, 1])), stats["updates_applied"], stats["steps"],
         max(max(r["grad_norm"]) for r in rows))
+    if "lr" in rows[-1]:                               # device-hyper mode: the lr of the section's last step
+        line += ", lr: {:.3e}".format(rows[-1]["lr"])
+    return line
 
 
 def learner_section(agent, steer_rollout, throttle_rollout, done, train_cfg, shared_grad_buffers,
@@ -146,6 +257,7 @@ def learner_section(agent, steer_rollout, throttle_rollout, done, train_cfg, sha
     skipped steps (their losses are returned); only the optimiser work is gated, and the Adam step count equals the
     number of applied steps."""
     tkl = _target_kl(train_cfg, shared_grad_buffers, in_process_chief)
+    lr = _section_hyper(agent, train_cfg, shared_grad_buffers, in_process_chief, optimizer)
     use_adv_norm = train_cfg["use_adv_norm"]
     sec = None
     if stats is not None or tkl is not None:
@@ -154,7 +266,7 @@ def learner_section(agent, steer_rollout, throttle_rollout, done, train_cfg, sha
     try:
         out = _learner_section(agent, steer_rollout, throttle_rollout, done, train_cfg, shared_grad_buffers, optimizer,
                                traffic_light, counter, shared_model_list, in_process_chief, fused_gather, losses_on_device,
-                               step_events, use_adv_norm, sec)
+                               step_events, use_adv_norm, sec, lr)
     finally:
         if sec is not None:
             agent.learner.set_update_modes()
@@ -173,7 +285,7 @@ def learner_section(agent, steer_rollout, throttle_rollout, done, train_cfg, sha
 
 def _learner_section(agent, steer_rollout, throttle_rollout, done, train_cfg, shared_grad_buffers, optimizer, traffic_light,
                      counter, shared_model_list, in_process_chief, fused_gather, losses_on_device, step_events, use_adv_norm,
-                     sec):
+                     sec, lr):
     nv_s, nv_t = agent.get_value(done, steer_rollout.get_last(as_tensor=True), throttle_rollout.get_last(as_tensor=True))
     steer_adv = steer_rollout.compute_returns(nv_s.detach(), normalise=use_adv_norm,
                                               explained_variance=None if sec is None else sec.ev[0:1])
@@ -206,8 +318,7 @@ def _learner_section(agent, steer_rollout, throttle_rollout, done, train_cfg, sh
             if in_process_chief:
                 shared_grad_buffers.add_gradient(agent.model_dict)
                 # (the next writer of the gradient arena is the next fused update, which overwrites every element)
-                chief_step(shared_grad_buffers, optimizer, train_cfg["max_grad_norm"], lr=_get(train_cfg, "lr"),
-                           zero_grads=False)
+                chief_step(shared_grad_buffers, optimizer, train_cfg["max_grad_norm"], lr=lr, zero_grads=False)
             else:
                 signal_init = traffic_light.get()
                 shared_grad_buffers.add_gradient(agent.model_dict)
@@ -276,6 +387,7 @@ def train(rank, train_cfg, agent_cfg, env_cfg, rollout_cfg, traffic_light=None, 
         if recorder is not None:
             recorder.end_episode()
         stats = {} if log_stats else None
+        apply_schedules(agent, train_cfg, episode)
         vl, pl, el = learner_section(agent, steer_rollout, throttle_rollout, done, train_cfg, shared_grad_buffers,
                                      traffic_light=traffic_light, counter=counter,
                                      shared_model_list=shared_model_list,
@@ -308,6 +420,7 @@ def learner_section_multi(agent, rollouts, dones, train_cfg, shared_grad_buffers
     worker, all 2N storages in one launch after their GAE).  The diagnostics of a step are taken over the N workers'
     minibatches with the losses' denominator: like the losses, they are the SUM of the per-worker means."""
     tkl = _target_kl(train_cfg, shared_grad_buffers)
+    lr = _section_hyper(agent, train_cfg, shared_grad_buffers, True, optimizer)
     use_adv_norm = train_cfg["use_adv_norm"]
     nv = agent.get_values([(s.get_last(as_tensor=True), t.get_last(as_tensor=True)) for s, t in rollouts], dones)
     advs = [(s.compute_returns(v_s.detach(), normalise=use_adv_norm), t.compute_returns(v_t.detach(), normalise=use_adv_norm))
@@ -326,7 +439,7 @@ def learner_section_multi(agent, rollouts, dones, train_cfg, shared_grad_buffers
                 dev_losses.append(agent.update_policy_from_storages(batches, sync=False,
                                                                     stats_row=None if sec is None else sec.next_row()))
                 shared_grad_buffers.add_gradient(agent.model_dict)
-                chief_step(shared_grad_buffers, optimizer, train_cfg["max_grad_norm"], lr=_get(train_cfg, "lr"), zero_grads=False)
+                chief_step(shared_grad_buffers, optimizer, train_cfg["max_grad_norm"], lr=lr, zero_grads=False)
     finally:
         if sec is not None:
             agent.learner.set_update_modes()
@@ -411,6 +524,7 @@ def train_vec(rank, train_cfg, agent_cfg, env_cfg, rollout_cfg, num_envs, env_cl
         if callback is not None:
             callback("rollout", episode=episode, dones=list(dones), **state())
         stats = {} if log_stats else None
+        apply_schedules(agent, train_cfg, episode)
         vl, pl, el = learner_section_multi(agent, rollouts, dones, train_cfg, shared_grad_buffers, optimizer=optimizer,
                                            stats=stats)
         if episode % train_cfg.log_interval == 0 and rank == 0 and logger is not None:

@@ -407,7 +407,7 @@ int cadre_ppo_loss(const float* logits, int64_t ldl, int64_t l_ns, const float* 
  * every mean taken with inv_b (the losses' denominator), the launch writes stats_row[hd * F + k]:
  *   k = 0 approx_kl = mean((r - 1) - log r)   1 old_approx_kl = mean(-log r)   2 clip_fraction = mean(|r - 1| > clip)
  *   3 value_clip_fraction = mean(|v - v_old| > clip)   4 ratio_mean   5 max |log r|   6 applied (1.0 / 0.0)
- * (k = 7 is not written; F >= CADRE_PPO_STATS_FIELDS).  The sums are combined by the loss kernel's last arriving workgroup
+ * (k = 7 is not written here — cadre_grad_norms_hp puts the step's learning rate there; F >= CADRE_PPO_STATS_FIELDS).  The sums are combined by the loss kernel's last arriving workgroup
  * in workgroup order: two launches on the same inputs give the same bits.  stats_scratch: 12 * ceil(B / 16) floats.
  * target_kl > 0 arms the gate: when max(approx_kl steer, throttle) > 1.5 * target_kl, *stop is set to 1; *stop is
  * sticky (only the caller clears it) and `applied` = (*stop == 0) after the check.  target_kl == 0: no check; stop may
@@ -424,6 +424,48 @@ int cadre_ppo_loss_stats(const float* logits, int64_t ldl, int64_t l_ns, const f
  * norms2, into a stats row [2][F]: model m = kind * 2C + head * C + c (the arena's segment order: 2C LSTM blocks, then 2C
  * MLP-tower pairs) goes to stats_row[head * F + CADRE_PPO_STATS_FIELDS + kind * C + c].  F >= CADRE_PPO_STATS_FIELDS + 2 C. */
 int cadre_grad_norms(const double* norms2, int32_t C, float* stats_row, int32_t F, void* stream);
+
+/* ---------------------------------------------------------------- device-resident hyper-parameters
+ * The hyper-parameter block: a device array of CADRE_HP_FIELDS doubles (8-byte aligned) that the `_hp` entry points read
+ * at RUN time, so a captured hipGraph follows whatever the block holds when it is replayed.  Fields past
+ * CADRE_HP_LR_FACTOR are reserved and zero.  betas and eps stay by-value arguments.  The block is written by ordinary
+ * stream-ordered copies from the host, and by the KL-adaptive controller below. */
+#define CADRE_HP_FIELDS 16
+#define CADRE_HP_LR 0
+#define CADRE_HP_CLIP 1
+#define CADRE_HP_VALUE_COEFF 2
+#define CADRE_HP_CLIP_COEFF 3
+#define CADRE_HP_ENT_COEFF 4
+#define CADRE_HP_MAX_GRAD_NORM 5
+#define CADRE_HP_DESIRED_KL 6       /* > 0: the KL-adaptive learning rate is on */
+#define CADRE_HP_LR_MIN 7
+#define CADRE_HP_LR_MAX 8
+#define CADRE_HP_LR_FACTOR 9
+/* cadre_ppo_loss / cadre_ppo_loss_stats with clip, value_coeff, clip_coeff, ent_coeff = (float)hp[CADRE_HP_*] (the same
+ * kernel bodies, the scalars read once per thread before the row loop; the stats variant uses the same clip for its clip
+ * fractions).  Equal values give results bit-identical to the by-value entry points.
+ * cadre_ppo_loss_stats_hp also runs the KL-ADAPTIVE LEARNING RATE when hp[CADRE_HP_DESIRED_KL] > 0: in the last arriving
+ * workgroup, after the target_kl gate check, unless the stop flag is set after that check, with
+ * kl = max(approx_kl steer, approx_kl throttle) of this launch (the float32 values of the stats row, as double):
+ *   kl > 2 desired:         hp[LR] = max(hp[LR_MIN], hp[LR] / hp[LR_FACTOR])
+ *   0 < kl < desired / 2:   hp[LR] = min(hp[LR_MAX], hp[LR] * hp[LR_FACTOR])
+ * in double; the optimiser step that follows on the stream reads the new value. */
+int cadre_ppo_loss_hp(const float* logits, int64_t ldl, int64_t l_ns, const float* values, int64_t ldv,
+                      int64_t v_ns, const int64_t* actions, const int32_t* commands, const float* old_values,
+                      const float* returns, const float* old_logp, const float* adv, int32_t B, int32_t C,
+                      int32_t n_out_steer, int32_t n_out_throttle, double* hp, float inv_b, float* losses,
+                      float* dlogits, float* dvalues, float* scratch, const int32_t* poison, void* stream);
+int cadre_ppo_loss_stats_hp(const float* logits, int64_t ldl, int64_t l_ns, const float* values, int64_t ldv,
+                            int64_t v_ns, const int64_t* actions, const int32_t* commands, const float* old_values,
+                            const float* returns, const float* old_logp, const float* adv, int32_t B, int32_t C,
+                            int32_t n_out_steer, int32_t n_out_throttle, double* hp, float inv_b, float* losses,
+                            float* dlogits, float* dvalues, float* scratch, const int32_t* poison, float* stats_row,
+                            int32_t F, float* stats_scratch, float target_kl, int32_t* stop, void* stream);
+/* cadre_grad_norms that also writes the learning rate the step used, (float)hp[CADRE_HP_LR], into
+ * stats_row[CADRE_PPO_STATS_LR] (field 7 of head 0, which cadre_ppo_loss_stats leaves alone).  To be enqueued after the
+ * optimiser step and before the next loss launch. */
+#define CADRE_PPO_STATS_LR 7
+int cadre_grad_norms_hp(const double* norms2, int32_t C, float* stats_row, int32_t F, const double* hp, void* stream);
 /* Explained variance of the value head per storage: src_table = device array of n_src records {const float* returns,
  * const float* value_preds, int64_t T}; out[i] = 1 - Var(R - V) / Var(R) over rows 0 .. T-1 (population variances,
  * fp64, fixed summation order), NaN where Var(R) == 0. */
@@ -531,6 +573,34 @@ int cadre_clip_adam_norms(const float* grads, const int64_t* seg_off, int32_t n_
 int cadre_clip_adam_apply(float* params, const float* grads, float* exp_avg, float* exp_avg_sq,
                           const int64_t* seg_off, int32_t n_models, const double* norms2, double max_norm,
                           double beta1, double beta2, double eps, int64_t rlo, int64_t rhi, void* stream);
+
+
+/* Hyper-parameter block forms of the optimiser entry points above: lr = hp[CADRE_HP_LR] (read by the preparation kernel,
+ * the only place lr enters the step) and max_norm = (float)hp[CADRE_HP_MAX_GRAD_NORM] at run time; everything else as in
+ * the by-value sibling, and bit-identical to it for equal values. */
+int cadre_clip_adam_graph_hp(float* params, const float* grads, float* exp_avg, float* exp_avg_sq,
+                             const int64_t* seg_off, int32_t n_models, double* norms2, const double* hp,
+                             double beta1, double beta2, double eps, int32_t* step_dev, void* stream);
+int cadre_clip_adam_graph_hp_gated(float* params, const float* grads, float* exp_avg, float* exp_avg_sq,
+                                   const int64_t* seg_off, int32_t n_models, double* norms2, const double* hp,
+                                   double beta1, double beta2, double eps, int32_t* step_dev, const int32_t* stop,
+                                   void* stream);
+int cadre_clip_adam_pack_graph_hp(float* params, const float* grads, float* exp_avg, float* exp_avg_sq,
+                                  const int64_t* seg_off, int32_t n_models, double* norms2, const double* hp,
+                                  double beta1, double beta2, double eps, int32_t* step_dev, int32_t n_lstm,
+                                  int64_t lstm_str, int64_t o_whh, int32_t H4, int32_t ldw, int32_t D, float* fwd,
+                                  float* bwd, int64_t p_str, void* stream);
+int cadre_clip_adam_pack_graph_hp_gated(float* params, const float* grads, float* exp_avg, float* exp_avg_sq,
+                                        const int64_t* seg_off, int32_t n_models, double* norms2, const double* hp,
+                                        double beta1, double beta2, double eps, int32_t* step_dev, int32_t n_lstm,
+                                        int64_t lstm_str, int64_t o_whh, int32_t H4, int32_t ldw, int32_t D,
+                                        float* fwd, float* bwd, int64_t p_str, const int32_t* stop, void* stream);
+int cadre_clip_adam_norms_hp(const float* grads, const int64_t* seg_off, int32_t n_models, double* norms2,
+                             const double* hp, double beta1, double beta2, int32_t* step_dev, int64_t rlo, int64_t rhi,
+                             void* stream);
+int cadre_clip_adam_apply_hp(float* params, const float* grads, float* exp_avg, float* exp_avg_sq,
+                             const int64_t* seg_off, int32_t n_models, const double* norms2, const double* hp,
+                             double beta1, double beta2, double eps, int64_t rlo, int64_t rhi, void* stream);
 
 #ifdef __cplusplus
 }
