@@ -125,6 +125,9 @@ SYMBOLS = {
                                             i64, vp, vp],
     "cadre_clip_adam_norms_hp": [vp, vp, i32, vp, vp, f64, f64, vp, i64, i64, vp],
     "cadre_clip_adam_apply_hp": [vp, vp, vp, vp, vp, i32, vp, vp, f64, f64, f64, i64, i64, vp],
+    "cadre_return_stats": [vp, i32, i32, f64, f64, i32, vp, vp, vp],
+    "cadre_gae_multi": [vp, i32, i32, f32, f32, i32, vp, f32, vp],
+    "cadre_insert_rows_tl": [vp, vp, i32, i32, i64, i64, i32, i32, i32, vp, i64, vp, vp, vp, vp, vp, vp],
 }
 # entry points of the A/B build only (include/cadre_hip_ab.h; CADRE_BUILD_AB=1 python -m cadre_amd.build, then
 # CADRE_HIP_LIB=.../libcadre_hip_ab.so): bound when the loaded library has them
@@ -183,7 +186,9 @@ PPO_STATS_LR = 7      # CADRE_PPO_STATS_LR: field of head 0 of a stats row that 
 
 PPO_STATS_FIELDS = 8  # CADRE_PPO_STATS_FIELDS (include/cadre_hip.h): loss diagnostics per head before the gradient norms
 
-N_CALLS = 0          # C-ABI calls checked so far (one kernel launch each, cadre_clip_adam_graph three): launch census
+RS_SCALE, RS_CARRY = 6, 8  # CADRE_RS_SCALE / CADRE_RS_CARRY: the return-statistics block (count, mean, M2 per head first)
+
+N_CALLS = 0         # C-ABI calls checked so far (one kernel launch each, cadre_clip_adam_graph three): launch census
 
 
 def check(rc, what):

@@ -19,6 +19,7 @@ def _rup(x, m):
 
 class RolloutStorage(object):
     _insert_tables = {}          # insert_batch: device pointer tables of storage sets, keyed by the pointers
+    _finish_tables = {}          # finish_rollouts: likewise
 
     def __init__(self, num_steps, mini_batch_num, feature_dims, seq_length, hidden_size, use_gae, gamma, tau):
         T = num_steps
@@ -31,6 +32,7 @@ class RolloutStorage(object):
         self.gamma = gamma
         self.tau = tau
         self.step = 0
+        self._tl_used = False        # a time-limit flag was ever written: the finishing stage then reads time_limits
         self._ldo = _rup(feature_dims, PAD)
         self._ldh = _rup(hidden_size, PAD)
         self._alloc(torch.device("cpu"))
@@ -52,20 +54,24 @@ class RolloutStorage(object):
         self.action_log_probs = z(T + 1, 1)
         self.action = z(T + 1, 1, dtype=torch.long)
         self.masks = z(T + 1, 1)
+        self.time_limits = z(T + 1, 1)       # 1 where the row's episode was cut by a step limit (insert(time_limit=True))
         self.advantages = z(T, 1)            # filled by compute_returns (train.py:82-88)
         self._next = z(1)
 
     def to(self, device):
         device = torch.device(device)
         old = {k: getattr(self, k) for k in ("_obs", "_hn", "_cn", "command", "rewards", "value_preds", "returns",
-                                             "action_log_probs", "action", "masks", "advantages")}
+                                             "action_log_probs", "action", "masks", "advantages", "time_limits")}
         self._alloc(device)
         for k, v in old.items():
             getattr(self, k).copy_(v)
 
-    def insert(self, obs, action, action_log_probs, value_preds, rewards, masks, hidden_state, command):
-        """storage.py:45-58."""
+    def insert(self, obs, action, action_log_probs, value_preds, rewards, masks, hidden_state, command, time_limit=False):
+        """storage.py:45-58.  `time_limit`: this row's episode was cut by a step budget, not ended (see finish_rollouts)."""
         s = self.step
+        if time_limit or self._tl_used:          # (a storage that never saw a flag keeps the reference's launches)
+            self.time_limits[s] = 1.0 if time_limit else 0.0
+            self._tl_used = True
         self.action[s].copy_(torch.as_tensor(action).reshape(-1)[:1])
         self.action_log_probs[s].copy_(torch.as_tensor(action_log_probs).reshape(-1)[:1])
         self.value_preds[s].copy_(torch.as_tensor(value_preds).reshape(-1)[:1])
@@ -80,13 +86,16 @@ class RolloutStorage(object):
         self.step = (s + 1) % (self.num_steps + 1)
 
     @staticmethod
-    def insert_batch(storages, outputs, rewards, masks, commands):
+    def insert_batch(storages, outputs, rewards, masks, commands, time_limits=None):
         """`insert` (storage.py:45-58) of one env step of N environments into their 2N storages in ONE launch
-        (cadre_insert_rows): storages = [(steer_rollout, throttle_rollout), ...] per environment, outputs = what
+        (cadre_insert_rows; with `time_limits` its twin cadre_insert_rows_tl, which writes the flags in the same launch):
+        time_limits = None, or per environment a bool or a (steer, throttle) pair of bools.  storages = [(steer_rollout, throttle_rollout), ...] per environment, outputs = what
         CadreAgent.act_batch returned for them, rewards / masks = [N][2] (steer, throttle) host values, commands = the N
         host-side commands.  The hidden state written is act()'s zeros.  The cursors (and their modulo-(T+1) drift) stay
         host-side ints, exactly as `insert` keeps them."""
         N = len(storages)
+        if time_limits is not None and len(time_limits) != N:
+            raise ValueError("insert_batch: %d storage pairs, %d time-limit flags" % (N, len(time_limits)))
         if N < 1 or len(outputs) != N or len(rewards) != N or len(masks) != N or len(commands) != N:
             raise ValueError("insert_batch: %d storage pairs, %d outputs, %d rewards, %d masks, %d commands"
                              % (N, len(outputs), len(rewards), len(masks), len(commands)))
@@ -112,8 +121,14 @@ class RolloutStorage(object):
         if feat.dim() != 3 or feat.shape[0] != N or feat.shape[1] != s0.seq_length or feat.shape[2] < s0.z_dims:
             raise ValueError("insert_batch: features of shape %s for %d environments x %d x %d"
                              % (tuple(feat.shape), N, s0.seq_length, s0.z_dims))
+        if time_limits is None and any(s._tl_used for s in flat):       # (flags of an earlier pass must not stay in the rows)
+            time_limits = [False] * N
+        tl = None
+        if time_limits is not None:
+            tl = [[bool(f[0]), bool(f[1])] if isinstance(f, (tuple, list)) else [bool(f), bool(f)] for f in time_limits]
         ptrs = [[hip.ptr(s._obs), hip.ptr(s._hn), hip.ptr(s._cn), hip.ptr(s.action), hip.ptr(s.action_log_probs),
-                 hip.ptr(s.value_preds), hip.ptr(s.rewards), hip.ptr(s.masks), hip.ptr(s.command)] for s in flat]
+                 hip.ptr(s.value_preds), hip.ptr(s.rewards), hip.ptr(s.masks), hip.ptr(s.command)] +
+                ([hip.ptr(s.time_limits)] if tl is not None else []) for s in flat]
         key = tuple(p for row in ptrs for p in row)
         tables = RolloutStorage._insert_tables
         table = tables.get(key)
@@ -123,12 +138,17 @@ class RolloutStorage(object):
             table = tables[key] = torch.tensor(ptrs, dtype=torch.int64).to(dev)
         slots = [s.step for s in flat]
         ints = torch.tensor(slots + [int(c) for c in commands], dtype=torch.int32).to(dev)
-        rm = torch.tensor([[float(rewards[e][h]), float(torch.as_tensor(masks[e][h]).reshape(-1)[0])]
+        rm = torch.tensor([[float(rewards[e][h]), float(torch.as_tensor(masks[e][h]).reshape(-1)[0])] +
+                           ([float(tl[e][h])] if tl is not None else [])
                            for e in range(N) for h in (0, 1)], dtype=torch.float32).to(dev)
-        hip.check(hip.lib().cadre_insert_rows(hip.ptr(table), hip.ptr(ints), 2 * N, s0.seq_length, s0._ldo, s0._ldh,
-                                              s0.z_dims, s0.hid_size, s0.num_steps, hip.ptr(feat), feat.stride(1),
-                                              hip.ptr(action), hip.ptr(logp), hip.ptr(value), hip.ptr(rm),
-                                              hip.ptr(ints[2 * N:]), hip.stream()), "cadre_insert_rows")
+        name = "cadre_insert_rows" if tl is None else "cadre_insert_rows_tl"
+        hip.check(getattr(hip.lib(), name)(hip.ptr(table), hip.ptr(ints), 2 * N, s0.seq_length, s0._ldo, s0._ldh,
+                                           s0.z_dims, s0.hid_size, s0.num_steps, hip.ptr(feat), feat.stride(1),
+                                           hip.ptr(action), hip.ptr(logp), hip.ptr(value), hip.ptr(rm),
+                                           hip.ptr(ints[2 * N:]), hip.stream()), name)
+        if tl is not None:
+            for s in flat:
+                s._tl_used = True
         for s in flat:
             s.step = (s.step + 1) % (s.num_steps + 1)
 
@@ -148,6 +168,9 @@ class RolloutStorage(object):
             raise NotImplementedError("use_gae=False branch (storage.py:77-86) is dead in the reference config")
         if not self.returns.is_cuda:
             raise hip.CadreHipError("RolloutStorage.compute_returns runs on the HIP device: call .to('cuda:N') first")
+        if self._tl_used:                        # time-limit flags were written: the scan that knows them, n = 1
+            return RolloutStorage.finish_rollouts([self], [next_value], normalise=normalise,
+                                                  explained_variance=explained_variance)[0]
         import numpy as np
         self._next.copy_(torch.as_tensor(next_value, dtype=torch.float32).reshape(-1)[:1])
         g32 = float(np.float32(self.gamma))
@@ -158,6 +181,65 @@ class RolloutStorage(object):
         if explained_variance is not None:
             RolloutStorage.explained_variance([self], explained_variance)
         return self.advantages
+
+    @staticmethod
+    def finish_rollouts(storages, next_values, normalise=True, reward_scaler=None, explained_variance=None):
+        """compute_returns of every storage of a learner section in ONE launch (cadre_gae_multi): storages = the flat list
+        [steer_0, throttle_0, steer_1, ...] (storage k belongs to head k & 1), next_values = one bootstrap value each.
+        Returns the list of `advantages` tensors.  Without time-limit flags and without a scaler, returns, advantages and
+        value_preds[T] are bit-identical to compute_returns per storage.
+        Time limits (`insert(time_limit=True)`): in the scan, after gae_t = delta_t + gamma tau m_t gae_{t+1}, a cut row
+        gets gae_t = 0, so returns[t] == value_preds[t]; the chain restarts behind the cut and row t - 1 bootstraps from
+        value_preds[t].  A cut row's advantage is 0 before normalisation and is NOT excluded from the mean / std.
+        `reward_scaler` (a ReturnScaler): one cadre_return_stats launch first updates the running statistics of the
+        discounted returns (when scaler.training) and the scale of each head; the scan then reads every reward as
+        clamp(r * scale_head, -clip, clip).  `storage.rewards` keeps the raw rewards.
+        `explained_variance` (device float64 [len(storages)]): filled by RolloutStorage.explained_variance afterwards."""
+        import numpy as np
+        n = len(storages)
+        if n < 1 or len(next_values) != n:
+            raise ValueError("finish_rollouts: %d storages, %d next values" % (n, len(next_values)))
+        s0 = storages[0]
+        if any((s.num_steps, s.gamma, s.tau, s.device) != (s0.num_steps, s0.gamma, s0.tau, s0.device) for s in storages):
+            raise ValueError("finish_rollouts: every storage needs the same num_steps, gamma, tau and device")
+        if not all(s.use_gae for s in storages):
+            raise NotImplementedError("use_gae=False branch (storage.py:77-86) is dead in the reference config")
+        if reward_scaler is not None:
+            if 2 * reward_scaler.n_envs != n:
+                raise ValueError("finish_rollouts: a ReturnScaler for %d environments with %d storages (two per environment)"
+                                 % (reward_scaler.n_envs, n))
+            if reward_scaler.state.device != s0.device:
+                raise ValueError("finish_rollouts: the ReturnScaler lives on %s, the storages on %s"
+                                 % (reward_scaler.state.device, s0.device))
+        if s0.device.type != "cuda":
+            raise hip.CadreHipError("RolloutStorage.finish_rollouts runs on the HIP device: call .to('cuda:N') first")
+        for s, v in zip(storages, next_values):
+            s._next.copy_(torch.as_tensor(v, dtype=torch.float32).reshape(-1)[:1])
+        flags = any(s._tl_used for s in storages)
+        rows = [[hip.ptr(s.rewards), hip.ptr(s.value_preds), hip.ptr(s.masks), hip.ptr(s._next), hip.ptr(s.returns),
+                 hip.ptr(s.advantages), hip.ptr(s.time_limits) if flags else 0] for s in storages]
+        key = tuple(p for row in rows for p in row)
+        tables = RolloutStorage._finish_tables
+        table = tables.get(key)
+        if table is None:
+            if len(tables) > 16:
+                tables.clear()
+            table = tables[key] = torch.tensor(rows, dtype=torch.int64).to(s0.device)
+        L, T = hip.lib(), s0.num_steps
+        state = None
+        if reward_scaler is not None:
+            state = reward_scaler.state
+            hip.check(L.cadre_return_stats(hip.ptr(table), n, T, float(reward_scaler.gamma), float(reward_scaler.epsilon),
+                                           1 if reward_scaler.training else 0, hip.ptr(state),
+                                           hip.ptr(reward_scaler._scratch), hip.stream()), "cadre_return_stats")
+        g32 = float(np.float32(s0.gamma))
+        gt32 = float(np.float32(s0.gamma * s0.tau))              # double product, then one rounding (storage.py:75)
+        hip.check(L.cadre_gae_multi(hip.ptr(table), n, T, g32, gt32, 1 if normalise else 0, hip.ptr(state),
+                                    float(reward_scaler.clip) if reward_scaler is not None else 0.0, hip.stream()),
+                  "cadre_gae_multi")
+        if explained_variance is not None:
+            RolloutStorage.explained_variance(storages, explained_variance)
+        return [s.advantages for s in storages]
 
     _ev_tables = {}
 
@@ -211,3 +293,58 @@ class RolloutStorage(object):
         [hn, cn], command)."""
         for indices in self.sample_indices():
             yield self.gather(indices, advantages)
+
+
+class ReturnScaler(object):
+    """Return-based reward scaling (the VecNormalize(norm_reward=True) rule) for `n_envs` environments of two heads each:
+    rewards are divided by the running standard deviation of the discounted return G_t = r_t + gamma m'_{t-1} G_{t-1},
+    m' = mask (1 - time_limit), kept per head.  Everything lives in one float64 device block (layout: CADRE_RS_* of
+    include/cadre_hip.h) that cadre_return_stats updates and cadre_gae_multi reads, with no host sync:
+    RolloutStorage.finish_rollouts(..., reward_scaler=self).  `training` False freezes statistics, carries and scale
+    (evaluation, replay).  The scaled reward is clamped to [-clip, clip]; scale = 1 / sqrt(var + epsilon)."""
+
+    def __init__(self, n_envs, gamma, clip=10.0, epsilon=1e-8, device="cpu"):
+        if isinstance(n_envs, bool) or not isinstance(n_envs, int) or not 1 <= n_envs <= 32767:
+            raise ValueError("ReturnScaler: n_envs must be an integer 1 .. 32767 (got %r)" % (n_envs,))
+        gamma, clip, epsilon = float(gamma), float(clip), float(epsilon)
+        if not 0.0 <= gamma <= 1.0:
+            raise ValueError("ReturnScaler: gamma must be in [0, 1] (got %r)" % (gamma,))
+        if not 0.0 < clip < float("inf"):
+            raise ValueError("ReturnScaler: clip must be a positive finite number (got %r)" % (clip,))
+        if not 0.0 <= epsilon < float("inf"):
+            raise ValueError("ReturnScaler: epsilon must be a finite number >= 0 (got %r)" % (epsilon,))
+        self.n_envs, self.gamma, self.clip, self.epsilon = n_envs, gamma, clip, epsilon
+        self.training = True
+        device = torch.device(device)
+        self.state = torch.zeros(hip.RS_CARRY + 4 * n_envs, dtype=torch.float64, device=device)
+        self.state[hip.RS_SCALE:hip.RS_CARRY] = 1.0
+        self._scratch = torch.zeros(1 + 4 * n_envs, dtype=torch.float64, device=device)
+
+    def to(self, device):
+        self.state = self.state.to(device)
+        self._scratch = torch.zeros_like(self._scratch, device=device)
+        return self
+
+    def scale(self):
+        """The two float32 scales (steer, throttle) the next scan multiplies rewards with."""
+        return self.state[hip.RS_SCALE:hip.RS_CARRY].to(torch.float32)
+
+    def count(self):
+        return self.state[0:6:3].clone()
+
+    def state_dict(self):
+        st = self.state.detach()
+        return dict(count=st[0:6:3].clone(), mean=st[1:6:3].clone(), M2=st[2:6:3].clone(), scale=self.scale().clone(),
+                    carry=st[hip.RS_CARRY:].view(2 * self.n_envs, 2).clone())
+
+    def load_state_dict(self, sd):
+        missing = sorted({"count", "mean", "M2", "scale", "carry"} - set(sd))
+        if missing:
+            raise ValueError("ReturnScaler.load_state_dict: missing %r" % (missing,))
+        if tuple(sd["carry"].shape) != (2 * self.n_envs, 2) or any(sd[k].numel() != 2 for k in ("count", "mean", "M2", "scale")):
+            raise ValueError("ReturnScaler.load_state_dict: a state for %d environments does not fit %d"
+                             % (sd["carry"].shape[0] // 2, self.n_envs))
+        for i, k in enumerate(("count", "mean", "M2")):
+            self.state[i:6:3] = sd[k].to(self.state.device, torch.float64)
+        self.state[hip.RS_SCALE:hip.RS_CARRY] = sd["scale"].to(self.state.device, torch.float32).double()
+        self.state[hip.RS_CARRY:] = sd["carry"].to(self.state.device, torch.float64).reshape(-1)

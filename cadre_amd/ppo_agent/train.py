@@ -10,7 +10,7 @@ from .. import hip
 from .agent import CadreAgent
 from .chief import chief_step
 from .models import arena_of, get_vae_output
-from .storage import RolloutStorage
+from .storage import ReturnScaler, RolloutStorage
 from .utils import check_exist
 
 
@@ -51,6 +51,51 @@ def _target_kl(train_cfg, shared_grad_buffers, in_process_chief=True):
     if not in_process_chief:
         raise hip.CadreHipError("train_cfg.target_kl needs the in-process chief (the gate lives on this process's device)")
     return tkl
+
+
+# ----------------------------------------------------------------------------- reward scaling, time limits
+def _check_scaler(reward_scaler, shared_grad_buffers):
+    """A ReturnScaler grows the statistics of THIS rank's environments: like target_kl it is refused with several ranks."""
+    if reward_scaler is not None and shared_grad_buffers is not None and shared_grad_buffers.dist_world() > 1:
+        raise hip.CadreHipError("reward scaling needs a single rank (world size %d): each rank would grow its own return "
+                                "statistics and scale its rewards differently" % shared_grad_buffers.dist_world())
+
+
+def _reward_scaling(train_cfg, shared_grad_buffers=None):
+    """train_cfg["reward_scaling"]: absent / None / False (off), True, or {"clip", "epsilon"} -> None or the keyword
+    arguments of ReturnScaler."""
+    cfg = _get(train_cfg, "reward_scaling")
+    if cfg is None or cfg is False:
+        return None
+    if cfg is True:
+        cfg = {}
+    elif not isinstance(cfg, dict):
+        raise ValueError("train_cfg.reward_scaling: expected None, True or a dict with clip / epsilon (got %r)" % (cfg,))
+    unknown = sorted(set(cfg) - {"clip", "epsilon"})
+    if unknown:
+        raise ValueError("train_cfg.reward_scaling: unknown keys %r (known: clip, epsilon)" % (unknown,))
+    try:
+        kw = dict(clip=float(cfg.get("clip", 10.0)), epsilon=float(cfg.get("epsilon", 1e-8)))
+    except (TypeError, ValueError):
+        raise ValueError("train_cfg.reward_scaling: clip / epsilon of %r are not numbers" % (cfg,))
+    if not 0.0 < kw["clip"] < float("inf") or not 0.0 <= kw["epsilon"] < float("inf"):
+        raise ValueError("train_cfg.reward_scaling: need a finite clip > 0 and a finite epsilon >= 0 (got %r)" % (cfg,))
+    if shared_grad_buffers is not None and shared_grad_buffers.dist_world() > 1:
+        raise hip.CadreHipError("train_cfg.reward_scaling needs a single rank (world size %d): each rank would grow its "
+                                "own return statistics" % shared_grad_buffers.dist_world())
+    return kw
+
+
+def _time_limit_pair(flag):
+    """info["time_limit"]: a bool, or a (steer, throttle) pair -> (steer, throttle) bools."""
+    if isinstance(flag, (tuple, list)):
+        return bool(flag[0]), bool(flag[1])
+    return bool(flag), bool(flag)
+
+
+def _scale_stats(stats, reward_scaler):
+    if stats is not None and reward_scaler is not None:
+        stats["reward_scale"] = tuple(reward_scaler.scale().tolist())
 
 
 # ----------------------------------------------------------------------------- hyper-parameter schedules, KL-adaptive lr
@@ -229,12 +274,14 @@ def stats_line(episode, stats):
         max(max(r["grad_norm"]) for r in rows))
     if "lr" in rows[-1]:                               # device-hyper mode: the lr of the section's last step
         line += ", lr: {:.3e}".format(rows[-1]["lr"])
+    if "reward_scale" in stats:                        # reward scaling: the scales the section's scan used
+        line += ", reward scale: {:.4e}/{:.4e}".format(*stats["reward_scale"])
     return line
 
 
 def learner_section(agent, steer_rollout, throttle_rollout, done, train_cfg, shared_grad_buffers,
                     optimizer=None, traffic_light=None, counter=None, shared_model_list=None, in_process_chief=True,
-                    fused_gather=True, losses_on_device=False, step_events=None, stats=None):
+                    fused_gather=True, losses_on_device=False, step_events=None, stats=None, reward_scaler=None):
     """train.py:76-110.  Returns (value_loss_list, policy_loss_list, ent_loss_list).
     With `in_process_chief` (one process per GPU) the optimiser step runs right after the gradient
     all-reduce instead of waiting on a separate chief process.  `fused_gather` uses the storage ->
@@ -255,7 +302,11 @@ def learner_section(agent, steer_rollout, throttle_rollout, done, train_cfg, sha
     on the device (the Stable-Baselines3 rule).  The sampler still draws every epoch's permutations, so the global CPU
     generator — and every later act() sample — does not depend on the KL outcome; forward and backward still run for
     skipped steps (their losses are returned); only the optimiser work is gated, and the Adam step count equals the
-    number of applied steps."""
+    number of applied steps.
+    `reward_scaler` (a ReturnScaler for one environment, single rank only): return-based reward scaling.  With it, or when
+    a storage holds time-limit flags, the two storages are finished by RolloutStorage.finish_rollouts (see there);
+    otherwise by today's two compute_returns calls."""
+    _check_scaler(reward_scaler, shared_grad_buffers)
     tkl = _target_kl(train_cfg, shared_grad_buffers, in_process_chief)
     lr = _section_hyper(agent, train_cfg, shared_grad_buffers, in_process_chief, optimizer)
     use_adv_norm = train_cfg["use_adv_norm"]
@@ -266,7 +317,7 @@ def learner_section(agent, steer_rollout, throttle_rollout, done, train_cfg, sha
     try:
         out = _learner_section(agent, steer_rollout, throttle_rollout, done, train_cfg, shared_grad_buffers, optimizer,
                                traffic_light, counter, shared_model_list, in_process_chief, fused_gather, losses_on_device,
-                               step_events, use_adv_norm, sec, lr)
+                               step_events, use_adv_norm, sec, lr, reward_scaler)
     finally:
         if sec is not None:
             agent.learner.set_update_modes()
@@ -274,9 +325,11 @@ def learner_section(agent, steer_rollout, throttle_rollout, done, train_cfg, sha
         return out
     if losses_on_device:
         sec.finish(stats, tkl is not None)
+        _scale_stats(stats, reward_scaler)
         return out
     dev_losses, (vl, pl, el) = out
     host = sec.finish(stats, tkl is not None, losses=torch.stack(dev_losses) if dev_losses else None)
+    _scale_stats(stats, reward_scaler)
     if host is not None:
         for v, p, e in host.tolist():
             vl.append(v); pl.append(p); el.append(e)
@@ -285,12 +338,17 @@ def learner_section(agent, steer_rollout, throttle_rollout, done, train_cfg, sha
 
 def _learner_section(agent, steer_rollout, throttle_rollout, done, train_cfg, shared_grad_buffers, optimizer, traffic_light,
                      counter, shared_model_list, in_process_chief, fused_gather, losses_on_device, step_events, use_adv_norm,
-                     sec, lr):
+                     sec, lr, reward_scaler=None):
     nv_s, nv_t = agent.get_value(done, steer_rollout.get_last(as_tensor=True), throttle_rollout.get_last(as_tensor=True))
-    steer_adv = steer_rollout.compute_returns(nv_s.detach(), normalise=use_adv_norm,
-                                              explained_variance=None if sec is None else sec.ev[0:1])
-    throttle_adv = throttle_rollout.compute_returns(nv_t.detach(), normalise=use_adv_norm,
-                                                    explained_variance=None if sec is None else sec.ev[1:2])
+    if reward_scaler is not None or steer_rollout._tl_used or throttle_rollout._tl_used:
+        steer_adv, throttle_adv = RolloutStorage.finish_rollouts(
+            [steer_rollout, throttle_rollout], [nv_s.detach(), nv_t.detach()], normalise=use_adv_norm,
+            reward_scaler=reward_scaler, explained_variance=None if sec is None else sec.ev)
+    else:
+        steer_adv = steer_rollout.compute_returns(nv_s.detach(), normalise=use_adv_norm,
+                                                  explained_variance=None if sec is None else sec.ev[0:1])
+        throttle_adv = throttle_rollout.compute_returns(nv_t.detach(), normalise=use_adv_norm,
+                                                        explained_variance=None if sec is None else sec.ev[1:2])
     dev_losses = []
     vl, pl, el = [], [], []
     # several ranks, CADRE_GRAD_BUCKETS=1: gradient buckets leave as soon as they are final, beside the rest of the backward
@@ -366,6 +424,8 @@ def train(rank, train_cfg, agent_cfg, env_cfg, rollout_cfg, traffic_light=None, 
     if shared_grad_buffers is None:              # single-process use: the agent's own arena is the shared one
         from .models import Shared_grad_buffers
         shared_grad_buffers = Shared_grad_buffers(agent.model_dict, device)
+    rs = _reward_scaling(train_cfg, shared_grad_buffers)
+    agent.reward_scaler = None if rs is None else ReturnScaler(1, rollout_cfg.gamma, device=device, **rs)
     obs = env.reset()
     done = False
     log_stats = bool(_get(train_cfg, "log_stats", False))
@@ -378,10 +438,11 @@ def train(rank, train_cfg, agent_cfg, env_cfg, rollout_cfg, traffic_light=None, 
             ad = info["action_done"]
             if recorder is not None:            # cadre_amd.replay.RolloutRecorder
                 recorder.step(raw, action, alp, values, reward, ad)
+            tl = _time_limit_pair(info.get("time_limit", False))        # (key absent: no flag is ever written)
             steer_rollout.insert(feat, action[0], alp[0], values[0], reward[0],
-                                 torch.tensor([[0.0] if ad[0] else [1.0]]), hidden, command)
+                                 torch.tensor([[0.0] if ad[0] else [1.0]]), hidden, command, time_limit=tl[0])
             throttle_rollout.insert(feat, action[1], alp[1], values[1], reward[1],
-                                    torch.tensor([[0.0] if ad[1] else [1.0]]), hidden, command)
+                                    torch.tensor([[0.0] if ad[1] else [1.0]]), hidden, command, time_limit=tl[1])
             if done:
                 obs = env.reset()
         if recorder is not None:
@@ -391,7 +452,8 @@ def train(rank, train_cfg, agent_cfg, env_cfg, rollout_cfg, traffic_light=None, 
         vl, pl, el = learner_section(agent, steer_rollout, throttle_rollout, done, train_cfg, shared_grad_buffers,
                                      traffic_light=traffic_light, counter=counter,
                                      shared_model_list=shared_model_list,
-                                     in_process_chief=traffic_light is None, stats=stats)   # no chief process -> step in-process
+                                     in_process_chief=traffic_light is None, stats=stats,   # no chief process -> step in-process
+                                     reward_scaler=agent.reward_scaler)
         if episode % train_cfg.log_interval == 0 and rank == 0 and logger is not None:
             logger.log("Episode: {}, value loss: {:.4f}, policy loss: {:.4f}, entropy loss: {:.4f}".format(
                 episode, np.mean(vl), np.mean(pl), np.mean(el)))
@@ -406,7 +468,7 @@ def train(rank, train_cfg, agent_cfg, env_cfg, rollout_cfg, traffic_light=None, 
 
 # ----------------------------------------------------------------------------- N environments in one process
 def learner_section_multi(agent, rollouts, dones, train_cfg, shared_grad_buffers, optimizer=None, losses_on_device=False,
-                          stats=None):
+                          stats=None, reward_scaler=None):
     """train.py:76-110 for N workers that share one agent (`num_processes = N` on one GPU, chief.py:13-21 semantics):
     rollouts = [(steer_rollout, throttle_rollout), ...] per worker, dones[i] = worker i's last `done`.  Bootstrap values
     of all workers in one pass (get_values), GAE + advantage normalisation per storage, then for each ppo_epoch and
@@ -418,17 +480,22 @@ def learner_section_multi(agent, rollouts, dones, train_cfg, shared_grad_buffers
     policy_loss_list, ent_loss_list), or the [steps, 3] loss tensor with `losses_on_device`.
     `stats` and train_cfg["target_kl"]: as in learner_section ("explained_variance" holds one (steer, throttle) pair per
     worker, all 2N storages in one launch after their GAE).  The diagnostics of a step are taken over the N workers'
-    minibatches with the losses' denominator: like the losses, they are the SUM of the per-worker means."""
+    minibatches with the losses' denominator: like the losses, they are the SUM of the per-worker means.
+    The 2N storages are finished by ONE RolloutStorage.finish_rollouts launch (bit-identical to 2N compute_returns calls
+    when no time-limit flag was written and `reward_scaler`, a ReturnScaler for N environments, is None)."""
+    _check_scaler(reward_scaler, shared_grad_buffers)
     tkl = _target_kl(train_cfg, shared_grad_buffers)
     lr = _section_hyper(agent, train_cfg, shared_grad_buffers, True, optimizer)
     use_adv_norm = train_cfg["use_adv_norm"]
     nv = agent.get_values([(s.get_last(as_tensor=True), t.get_last(as_tensor=True)) for s, t in rollouts], dones)
-    advs = [(s.compute_returns(v_s.detach(), normalise=use_adv_norm), t.compute_returns(v_t.detach(), normalise=use_adv_norm))
-            for (s, t), (v_s, v_t) in zip(rollouts, nv)]
     sec = None
     if stats is not None or tkl is not None:
         sec = _SectionStats(agent, train_cfg["ppo_epoch"] * _steps_per_epoch(rollouts[0][0]), 2 * len(rollouts))
-        RolloutStorage.explained_variance([x for pair in rollouts for x in pair], sec.ev)
+    flat = RolloutStorage.finish_rollouts([x for pair in rollouts for x in pair], [v.detach() for pair in nv for v in pair],
+                                          normalise=use_adv_norm, reward_scaler=reward_scaler,
+                                          explained_variance=None if sec is None else sec.ev)
+    advs = [(flat[2 * i], flat[2 * i + 1]) for i in range(len(rollouts))]
+    if sec is not None:
         agent.learner.set_update_modes(stats=True, target_kl=tkl)
     dev_losses = []
     try:
@@ -446,9 +513,11 @@ def learner_section_multi(agent, rollouts, dones, train_cfg, shared_grad_buffers
     losses = torch.stack(dev_losses)
     if sec is not None and not losses_on_device:
         host = sec.finish(stats, tkl is not None, losses=losses)
+        _scale_stats(stats, reward_scaler)
         return tuple(list(c) for c in zip(*host.tolist()))
     if sec is not None:
         sec.finish(stats, tkl is not None)
+        _scale_stats(stats, reward_scaler)
     if losses_on_device:
         return losses
     vl, pl, el = [], [], []
@@ -468,7 +537,10 @@ def train_vec(rank, train_cfg, agent_cfg, env_cfg, rollout_cfg, num_envs, env_cl
     `callback(event, **state)` (optional, for tests and tools): "start" before the first step, "rollout" after each
     rollout (before its learner section; episode, dones), "update" after each learner section, its log line and its
     snapshot (episode, losses; saving a snapshot builds nn.Modules, which draws from the global generator); every event
-    also passes agent, envs and rollouts."""
+    also passes agent, envs, rollouts and reward_scaler.
+    train_cfg["reward_scaling"] (None / absent, True, or {"clip", "epsilon"}; single rank only): return-based reward
+    scaling through one ReturnScaler kept as `agent.reward_scaler`.  An environment that reports info["time_limit"] (a
+    bool, or a (steer, throttle) pair) marks the row as cut by a step budget: see RolloutStorage.finish_rollouts."""
     if env_cls is None:
         from env_wrapper import EnvWrapper as env_cls        # needs the CARLA stack (reference env_wrapper.py)
     if logger is None:
@@ -501,23 +573,28 @@ def train_vec(rank, train_cfg, agent_cfg, env_cfg, rollout_cfg, num_envs, env_cl
     if shared_grad_buffers is None:              # single-process use: the agent's own arena is the shared one
         from .models import Shared_grad_buffers
         shared_grad_buffers = Shared_grad_buffers(agent.model_dict, device)
+    rs = _reward_scaling(train_cfg, shared_grad_buffers)
+    agent.reward_scaler = None if rs is None else ReturnScaler(num_envs, rollout_cfg.gamma, device=device, **rs)
     obs = [env.reset() for env in envs]
     dones = [False] * num_envs
     log_stats = bool(_get(train_cfg, "log_stats", False))
-    state = lambda: dict(agent=agent, envs=envs, rollouts=rollouts)
+    state = lambda: dict(agent=agent, envs=envs, rollouts=rollouts, reward_scaler=agent.reward_scaler)
     if callback is not None:
         callback("start", **state())
     for episode in range(train_cfg.max_episode):
         for _ in range(num_steps):
             commands = [o["command"] for o in obs]
             outs = agent.act_batch(obs)
-            rewards, masks = [], []
+            rewards, masks, tls = [], [], []
             for i, (env, out) in enumerate(zip(envs, outs)):
                 obs[i], reward, dones[i], info = env.step(agent.convert_action(out[1]))
                 ad = info["action_done"]
                 rewards.append(reward)
                 masks.append([0.0 if ad[0] else 1.0, 0.0 if ad[1] else 1.0])
-            RolloutStorage.insert_batch(rollouts, outs, rewards, masks, commands)
+                tls.append(info.get("time_limit"))
+            RolloutStorage.insert_batch(rollouts, outs, rewards, masks, commands,
+                                        time_limits=None if all(f is None for f in tls) else
+                                        [_time_limit_pair(False if f is None else f) for f in tls])
             for i, env in enumerate(envs):
                 if dones[i]:
                     obs[i] = env.reset()
@@ -526,7 +603,7 @@ def train_vec(rank, train_cfg, agent_cfg, env_cfg, rollout_cfg, num_envs, env_cl
         stats = {} if log_stats else None
         apply_schedules(agent, train_cfg, episode)
         vl, pl, el = learner_section_multi(agent, rollouts, dones, train_cfg, shared_grad_buffers, optimizer=optimizer,
-                                           stats=stats)
+                                           stats=stats, reward_scaler=agent.reward_scaler)
         if episode % train_cfg.log_interval == 0 and rank == 0 and logger is not None:
             logger.log("Episode: {}, value loss: {:.4f}, policy loss: {:.4f}, entropy loss: {:.4f}".format(
                 episode, np.mean(vl), np.mean(pl), np.mean(el)))

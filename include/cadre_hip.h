@@ -602,6 +602,45 @@ int cadre_clip_adam_apply_hp(float* params, const float* grads, float* exp_avg, 
                              const int64_t* seg_off, int32_t n_models, const double* norms2, const double* hp,
                              double beta1, double beta2, double eps, int64_t rlo, int64_t rhi, void* stream);
 
+/* ---------------------------------------------------------------- rollout finishing (csrc/rollout_finish.hip)
+ * The stage between a rollout and its update for all n storages of a learner section.  row_table: device array of n
+ * records of seven pointers {rewards, value_preds, masks [T+1], next_value [1], returns [T+1], advantages [T],
+ * time_limits [T+1] or NULL}, all f32; storage k belongs to head k & 1 (steer, throttle).  2 <= T <= 3000.
+ *
+ * Return-statistics state: one block of 8 + 2 n doubles,
+ *   [3 h + 0 .. 2]             count, mean, M2 of the discounted returns head h has seen          (CADRE_RS_STATS)
+ *   [CADRE_RS_SCALE + h]       the reward scale of head h: a float32 value held in a double slot, initially 1
+ *   [CADRE_RS_CARRY + 2 k + 0] G of the last row of storage k's previous rollout, initially 0
+ *   [CADRE_RS_CARRY + 2 k + 1] m' of that row, initially 0
+ * and a scratch of 1 + 2 n doubles, zero before the first launch (a ticket and the per-storage partials).
+ *
+ * cadre_return_stats: for every storage, over rows 0 .. T-1 in slot order, G_t = r_t + gamma m'_{t-1} G_{t-1} in fp64,
+ * m' = mask (1 - time_limit), carries read from and written back to the block; the T values of a storage give a
+ * two-pass (mean, M2), the storages of a head are merged into the head's statistics with Chan's formula in storage
+ * order (a fixed order: equal inputs give equal bits), and then scale_h = float32(1 / sqrt(M2_h / count_h + epsilon)) is
+ * stored.  n even.  With update == 0 nothing is launched: statistics, carries and scale stay as they are. */
+#define CADRE_RS_STATS 0
+#define CADRE_RS_SCALE 6
+#define CADRE_RS_CARRY 8
+int cadre_return_stats(const void* row_table, int32_t n, int32_t T, double gamma, double epsilon, int32_t update,
+                       double* state, double* scratch, void* stream);
+/* cadre_gae for every storage of the table in one launch (one workgroup per storage; next_value is read from the
+ * record, value_preds[T] is overwritten with it): the same arithmetic in the same order, so with time_limits NULL and
+ * state NULL the returns, advantages and value_preds[T] are bit-identical to n cadre_gae launches.
+ * time_limits: after `gae = delta + gamma_tau m gae` of row t, gae = gae * (1 - time_limit[t]) — a cut row has
+ * returns[t] == value_preds[t] and advantage 0 before normalisation (it still counts in the mean / std), the chain
+ * restarts behind it and row t - 1 bootstraps from value_preds[t].
+ * state (may be NULL: no reward scaling): the block of cadre_return_stats; a staged reward becomes
+ * clamp(r * (float)state[CADRE_RS_SCALE + head], -clip_r, clip_r), one fp32 multiply, then the clamp.  The rewards
+ * array itself is not written. */
+int cadre_gae_multi(const void* row_table, int32_t n, int32_t T, float gamma, float gamma_tau, int32_t normalise,
+                    const double* state, float clip_r, void* stream);
+/* cadre_insert_rows whose records carry a tenth pointer, time_limits f32 [T+1], and whose rm is [n_dst][3]:
+ * reward, mask, time-limit flag (0 or 1) of the row. */
+int cadre_insert_rows_tl(const void* dst_table, const int32_t* slot, int32_t n_dst, int32_t S, int64_t ldo, int64_t ldh,
+                         int32_t D, int32_t Hd, int32_t T, const float* feat, int64_t ldf, const int64_t* action,
+                         const float* logp, const float* value, const float* rm, const int32_t* cmd, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
