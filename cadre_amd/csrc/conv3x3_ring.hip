@@ -1556,8 +1556,9 @@ __global__ __launch_bounds__(256, 1) void conv3x3_c64s_kernel(ring_args a) {
   const int PA = a.WPX >> 3;
   for (int i = tid; i < 256; i += 256) reinterpret_cast<unsigned*>(dump)[i] = 0u;      // the ZERO ROW (halo taps) and the dummy DMA target
   // ---- this wave's weights: A fragments of its 32 output channels, all nine taps (w: [64][1][9][128 B]).  The folded-BN
-  // SCALE of an output channel multiplies its weight row once, here (fp32 product, rounded to bf16 again: a caller that
-  // wants single rounding folds the scale into the weights itself and passes scale = NULL, as cadre_amd/encoder.py does);
+  // SCALE of an output channel is expected IN the weight rows (the caller folds it, one rounding to bf16, and passes
+  // scale = NULL, as cadre_amd/encoder.py does): ring_pick sends every call with a scale vector to the ping-pong kernel's
+  // fp32 epilogue, because the multiply below rounds the weights a second time — bf16(bf16(w) * scale) — and is not reached;
   // the SHIFT is the accumulator's initial value (the C operand of an item's first MFMAs): the epilogue has no BN arithmetic.
   f32x4 wfr[9][4];
   {
@@ -2188,10 +2189,12 @@ __global__ __launch_bounds__(256, 1) void conv3x3_ring1w_kernel(ring_args a) {
 // 990 TFLOP/s; the kernel template still takes WVM = 2.)
 struct ring_cfg { int wvm, ntile, bm, wpx, wgs, pp, g; size_t lds; long long items; };
 // pflags: 1 = residual after the activation (act | 16), 2 = a folded-BN scale vector is present — either keeps the launch
-// on the ping-pong kernels (the weight-stationary / one-wave kernels add the residual before the activation; the one-wave
-// kernel wants the scale folded into the weights)
+// on the ping-pong kernels (the weight-stationary / one-wave kernels add the residual before the activation and take the
+// scale folded into the weights: multiplying it into the bf16 weight rows in the kernel would round the weights a SECOND
+// time — bf16(bf16(w) * scale), thousands of accumulation units off the contract act(conv * scale + shift),
+// tests/test_bf16_parity_gpu.py — so a call with a scale vector gets the fp32 epilogue multiply of the ping-pong kernel)
 static void ring_pick(long long M, int W, int N, int bf16, int NC, ring_cfg* c, int pflags = 0) {
-  const bool no_c64s = (pflags & 1) != 0;
+  const bool no_c64s = pflags != 0;
   static const int force_nt = [] { const char* e = getenv("CADRE_RING_NTILE"); return e ? atoi(e) : 0; }();
   static const int force_pp = [] { const char* e = getenv("CADRE_RING_PP"); return e ? atoi(e) : 1; }();
   int ntile = N >= 128 ? 128 : 64;
@@ -2264,6 +2267,7 @@ extern "C" int cadre_conv3x3_ring_supported(int32_t F, int32_t H, int32_t W, int
 }
 
 // tile configuration cadre_conv3x3_ring would use, as ntile (64 / 128) + 1000 * WVM + 100000 * ping-pong + 1000000 * G
+// for a call WITHOUT a scale vector and with the residual before the activation (what cadre_amd/encoder.py launches)
 // (host logic; names the kernel instantiation for profiles: conv3x3_ring_kernel<bf16, ntile, res, out_bf16, WVM>,
 // conv3x3_ring_pp_kernel<bf16, ntile, res, out_bf16, false> or, G > 0, conv3x3_ring_pp2_kernel<ntile, res, out_bf16, G>)
 extern "C" int cadre_conv3x3_ring_ntile(int32_t F, int32_t H, int32_t W, int32_t Cin, int32_t N, int32_t bf16) {
