@@ -47,7 +47,7 @@ class PPOArena:
         with torch.cuda.use_mem_pool(pool, device=idx):
             return fn()
 
-    def __init__(self, device, obs_dim=530, n_out=None, command_num=4, hid=128):
+    def __init__(self, device, obs_dim=530, n_out=None, command_num=4, hid=128, ordinal=None):
         n_out = n_out or {"steer": 33, "throttle": 3}
         self.device = torch.device(device)
         self.D = obs_dim
@@ -95,6 +95,23 @@ class PPOArena:
         self.seg_off.copy_(torch.tensor(offs, dtype=torch.int64))
         self.norms2 = self._small[n_off:n_off + n_nrm].view(torch.float64)
         self.step_dev = self._small[n_off + n_nrm:].view(torch.int32)[:1]                 # Adam step count (graph replay)
+        # ordinal policy heads (opt-in): ordinal_rank = [steer, throttle], each None (categorical head) or the head's
+        # bin -> rank permutation; ord = the device table int32 [2][64] every kernel reads (row h: rank of bin k at column k,
+        # -1 at column 0 for a categorical head), uploaded once — captured graphs hold its address.  Off: both None.
+        self.ordinal_rank = None
+        self.ord = None
+        if ordinal is not None and any(r is not None for r in ordinal):
+            host = torch.zeros(2, 64, dtype=torch.int32)
+            for h, rank in enumerate(ordinal):
+                if rank is None:
+                    host[h, 0] = -1
+                    continue
+                if sorted(int(r) for r in rank) != list(range(self.n_out[h])):
+                    raise ValueError("ordinal rank table of head %d is not a permutation of 0 .. %d" % (h, self.n_out[h] - 1))
+                host[h, :self.n_out[h]] = torch.tensor([int(r) for r in rank], dtype=torch.int32)
+            self.ordinal_rank = [None if r is None else [int(x) for x in r] for r in ordinal]
+            self.ord = self._alloc_shared(lambda: torch.zeros(2, 64, dtype=torch.int32, device=self.device))
+            self.ord.copy_(host)
 
     # ------------------------------------------------------------------ naming
     def net_index(self, head, command):

@@ -33,7 +33,7 @@ def _ab():
 def _plan(ab):
     srcs = SOURCES + (AB_SOURCES if ab else [])
     odir = os.path.join(CSRC, "build", "ab" if ab else "default")
-    hdrs = [os.path.join(INCLUDE, "cadre_hip.h"), os.path.join(CSRC, "winograd_mats.h")] + ([os.path.join(INCLUDE, "cadre_hip_ab.h")] if ab else [])
+    hdrs = [os.path.join(INCLUDE, "cadre_hip.h"), os.path.join(CSRC, "winograd_mats.h"), os.path.join(CSRC, "ordinal.h")] + ([os.path.join(INCLUDE, "cadre_hip_ab.h")] if ab else [])
     return srcs, odir, hdrs, (LIB_AB if ab else LIB)
 
 

@@ -8,6 +8,7 @@
 #include <math.h>
 #include <stdint.h>
 #include "../../include/cadre_hip.h"
+#include "ordinal.h"
 
 int cadre_fail(const char* msg);
 #define ST(s) ((hipStream_t)(s))
@@ -66,16 +67,26 @@ __global__ __launch_bounds__(256) void act_windows_kernel(float* ring, int64_t r
 
 // ---------------------------------------------------------------------------- sampling
 // sample_kernel (cadre_kernels.hip) per (environment, head): argmax(p / q), lowest index wins ties; wave = pair.
+// ORD (cadre_sample_rows_ord): `ord` int32 [2][64] holds each head's bin -> rank table (ordinal.h); a head whose first entry
+// is -1 is the plain categorical head and runs exactly the statements of the ORD = false kernel.
+template <bool ORD>
 __global__ __launch_bounds__(64) void sample_rows_kernel(const float* O3, int64_t ldo, int64_t z_str, const int32_t* pos,
                                                          const int32_t* cmd, int N, int C, const float* q, int K0, int K1,
-                                                         int64_t* action, float* logp, float* value) {
+                                                         int64_t* action, float* logp, float* value, const int32_t* ord) {
   const int e = blockIdx.x >> 1, h = blockIdx.x & 1, lane = threadIdx.x;
   const int K = h ? K1 : K0;
   const int c = cmd[e], p = pos[e];
   if (c < 0 || c >= C || p < 0 || p >= N) return;                 // (the host checked)
   const int z = 2 * (h * C + c);
   const float* lr = O3 + (int64_t)z * z_str + (int64_t)p * ldo;
-  const float x = lane < K ? lr[lane] : -INFINITY;
+  float x = lane < K ? lr[lane] : -INFINITY;
+  if constexpr (ORD) {
+    const int32_t* oh = ord + h * 64;
+    if (oh[0] >= 0) {
+      float s, t;
+      x = ord_logits(x, lane < K, lane < K ? oh[lane] : lane, lane, s, t);
+    }
+  }
   const float mx = wave_max64(x);
   const float se = wave_sum64(lane < K ? expf(x - mx) : 0.f);
   const float lg = x - (mx + logf(se));
@@ -159,8 +170,21 @@ extern "C" int cadre_sample_rows(const float* O3, int64_t ldo, int64_t z_str, co
   FAIL_IF(N < 1 || C < 1 || C > 16 || K_steer < 1 || K_steer > 64 || K_throttle < 1 || K_throttle > 64 || ldo < K_steer ||
               ldo < K_throttle || z_str < (int64_t)N * ldo,
           "cadre_sample_rows: bad argument (N >= 1, 1 <= C <= 16, 1 <= K <= 64, ldo >= K, z_str >= N * ldo)");
-  hipLaunchKernelGGL(sample_rows_kernel, dim3(2 * N), dim3(64), 0, ST(stream), O3, ldo, z_str, pos, cmd, N, C, q, K_steer,
-                     K_throttle, action, logp, value);
+  hipLaunchKernelGGL(sample_rows_kernel<false>, dim3(2 * N), dim3(64), 0, ST(stream), O3, ldo, z_str, pos, cmd, N, C, q, K_steer,
+                     K_throttle, action, logp, value, nullptr);
+  return (int)hipGetLastError();
+}
+
+extern "C" int cadre_sample_rows_ord(const float* O3, int64_t ldo, int64_t z_str, const int32_t* pos, const int32_t* cmd,
+                                     int32_t N, int32_t C, const float* q, int32_t K_steer, int32_t K_throttle, int64_t* action,
+                                     float* logp, float* value, const int32_t* ord, void* stream) {
+  FAIL_IF(!O3 || !pos || !cmd || !q || !action || !logp || !value, "cadre_sample_rows_ord: null operand");
+  FAIL_IF(!ord, "cadre_sample_rows_ord: null rank table (device int32 [2][64]; ord[h][0] = -1 marks a categorical head)");
+  FAIL_IF(N < 1 || C < 1 || C > 16 || K_steer < 1 || K_steer > 64 || K_throttle < 1 || K_throttle > 64 || ldo < K_steer ||
+              ldo < K_throttle || z_str < (int64_t)N * ldo,
+          "cadre_sample_rows_ord: bad argument (N >= 1, 1 <= C <= 16, 1 <= K <= 64, ldo >= K, z_str >= N * ldo)");
+  hipLaunchKernelGGL(sample_rows_kernel<true>, dim3(2 * N), dim3(64), 0, ST(stream), O3, ldo, z_str, pos, cmd, N, C, q, K_steer,
+                     K_throttle, action, logp, value, ord);
   return (int)hipGetLastError();
 }
 

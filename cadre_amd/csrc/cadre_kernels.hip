@@ -9,6 +9,7 @@
 #include <string.h>
 #include <algorithm>
 #include "../../include/cadre_hip.h"
+#include "ordinal.h"
 #ifdef CADRE_AB_KERNELS
 #include "../../include/cadre_hip_ab.h"
 #endif
@@ -1502,7 +1503,11 @@ struct ppo_stats_t {
 // HP: the four PPO scalars come from the device hyper-parameter block (include/cadre_hip.h: CADRE_HP_*), read once into
 // registers before the row loop; the by-value arguments are then ignored.  With STATS the last arriver also runs the
 // KL-adaptive learning-rate controller on hp[CADRE_HP_LR] (after the gate check: a stopped round leaves lr alone).
-template <bool STATS, bool HP>
+// ORD: `ord` int32 [2][64] is the bin -> rank table of the ordinal heads (ordinal.h); a head whose first entry is -1 is the
+// plain categorical head and runs exactly the statements of the ORD = false bodies.  For an ordinal head the logits of the
+// bins come from ord_logits, everything up to d total / d logit stays in bin space, and ord_backward turns that into the
+// gradient with respect to the raw tower outputs, which is what dlogits then holds.
+template <bool STATS, bool HP, bool ORD = false>
 __device__ __forceinline__ void ppo_loss_body(const float* logits, int64_t ldl, int64_t l_ns,
                                               const float* values, int64_t ldv, int64_t v_ns,
                                               const int64_t* actions, const int32_t* commands,
@@ -1511,7 +1516,8 @@ __device__ __forceinline__ void ppo_loss_body(const float* logits, int64_t ldl, 
                                               int n_steer, int n_throttle, float clip, float value_coeff,
                                               float clip_coeff, float ent_coeff, float inv_b,
                                               float* losses, float* dlogits, float* dvalues, float* scratch,
-                                              const int32_t* poison, const ppo_stats_t& so, double* hp) {
+                                              const int32_t* poison, const ppo_stats_t& so, double* hp,
+                                              const int32_t* ord = nullptr) {
   if constexpr (HP) {
     clip = (float)hp[CADRE_HP_CLIP];
     value_coeff = (float)hp[CADRE_HP_VALUE_COEFF];
@@ -1524,6 +1530,15 @@ __device__ __forceinline__ void ppo_loss_body(const float* logits, int64_t ldl, 
   __shared__ float red[STATS ? 3 + PPO_NSTAT : 3][4];
   float s_act = 0.f, s_val = 0.f, s_ent = 0.f;     // lane 0 of each wave
   float s_kl = 0.f, s_okl = 0.f, s_cf = 0.f, s_vcf = 0.f, s_r = 0.f, m_lr = 0.f;   // (STATS only)
+  bool ordinal = false;                            // (ORD only) this head is ordinal; rk / binv: its table and the inverse
+  int rk = lane, binv = lane;
+  if constexpr (ORD) {
+    ordinal = ord[hd * 64] >= 0;
+    if (ordinal) {
+      rk = lane < K ? ord[hd * 64 + lane] : lane;
+      binv = ord_inverse(rk, lane);
+    }
+  }
   for (int i = 0; i < 4; ++i) {
     const int b = blockIdx.x * 16 + wave * 4 + i;
     if (b >= B) break;
@@ -1540,7 +1555,11 @@ __device__ __forceinline__ void ppo_loss_body(const float* logits, int64_t ldl, 
     const int a = (int)actions[row];
     const int net = hd * C + c;
     const bool on = lane < K;
-    const float x = on ? logits[(int64_t)net * l_ns + (int64_t)b * ldl + lane] : -INFINITY;
+    float x = on ? logits[(int64_t)net * l_ns + (int64_t)b * ldl + lane] : -INFINITY;
+    float sg = 0.f, tg = 0.f;                      // (ordinal head) sigmoid(x), sigmoid(-x) of this lane's threshold unit
+    if constexpr (ORD) {
+      if (ordinal) x = ord_logits(x, on, rk, lane, sg, tg);
+    }
     const float mx = wave_max(x);
     const float se = wave_sum(on ? expf(x - mx) : 0.f);
     const float lse = mx + logf(se);               // Categorical(logits=x).logits  distributions.py:80-81
@@ -1590,9 +1609,11 @@ __device__ __forceinline__ void ppo_loss_body(const float* logits, int64_t ldl, 
     else dmax_dv = 0.5f * g1 + 0.5f * g2;
     if (lane == 0) dvalues[(int64_t)net * v_ns + (int64_t)b * ldv] = value_coeff * inv_b * 0.5f * dmax_dv;
     const float dH = -ent_coeff * inv_b;
-    if (lane < ldl)
-      dlogits[(int64_t)net * l_ns + (int64_t)b * ldl + lane] =
-          on ? dlp * ((lane == a ? 1.f : 0.f) - pk) + dH * (-pk * (lg + H)) : 0.f;
+    float gk = on ? dlp * ((lane == a ? 1.f : 0.f) - pk) + dH * (-pk * (lg + H)) : 0.f;
+    if constexpr (ORD) {
+      if (ordinal) gk = ord_backward(gk, on, sg, tg, binv, lane);
+    }
+    if (lane < ldl) dlogits[(int64_t)net * l_ns + (int64_t)b * ldl + lane] = gk;
   }
   if (lane == 0) { red[0][wave] = s_val; red[1][wave] = s_act; red[2][wave] = s_ent; }
   if constexpr (STATS) {
@@ -1808,11 +1829,70 @@ extern "C" int cadre_ppo_loss_stats_hp(const float* logits, int64_t ldl, int64_t
   return (int)hipGetLastError();
 }
 
+// ---------------------------------------------------------------------------- ordinal heads: the four modes in one entry
+template <bool STATS, bool HP>
+__global__ __launch_bounds__(256) void ppo_loss_ord_kernel(const float* logits, int64_t ldl, int64_t l_ns,
+                                                           const float* values, int64_t ldv, int64_t v_ns,
+                                                           const int64_t* actions, const int32_t* commands,
+                                                           const float* old_values, const float* returns,
+                                                           const float* old_logp, const float* adv, int B, int C,
+                                                           int n_steer, int n_throttle, double* hp, float clip,
+                                                           float value_coeff, float clip_coeff, float ent_coeff, float inv_b,
+                                                           float* losses, float* dlogits, float* dvalues, float* scratch,
+                                                           const int32_t* poison, ppo_stats_t so, const int32_t* ord) {
+  ppo_loss_body<STATS, HP, true>(logits, ldl, l_ns, values, ldv, v_ns, actions, commands, old_values, returns, old_logp, adv, B,
+                                 C, n_steer, n_throttle, clip, value_coeff, clip_coeff, ent_coeff, inv_b, losses, dlogits,
+                                 dvalues, scratch, poison, so, hp, ord);
+}
+
+extern "C" int cadre_ppo_loss_ord(const float* logits, int64_t ldl, int64_t l_ns, const float* values, int64_t ldv,
+                                  int64_t v_ns, const int64_t* actions, const int32_t* commands, const float* old_values,
+                                  const float* returns, const float* old_logp, const float* adv, int32_t B, int32_t C,
+                                  int32_t n_out_steer, int32_t n_out_throttle, double* hp, float clip, float value_coeff,
+                                  float clip_coeff, float ent_coeff, float inv_b, float* losses, float* dlogits,
+                                  float* dvalues, float* scratch, const int32_t* poison, float* stats_row, int32_t F,
+                                  float* stats_scratch, float target_kl, int32_t* stop, const int32_t* ord, void* stream) {
+  FAIL_IF(!logits || !values || !actions || !commands || !old_values || !returns || !old_logp || !adv || !losses ||
+              !dlogits || !dvalues || !scratch || B < 1 || C < 1 || n_out_steer < 1 || n_out_steer > MAX_NOUT || n_out_throttle < 1 ||
+              n_out_throttle > MAX_NOUT || ldl < n_out_steer || ldl < n_out_throttle || ldl > 64,
+          "cadre_ppo_loss_ord: bad argument");
+  FAIL_IF(!ord, "cadre_ppo_loss_ord: null rank table (device int32 [2][64]; ord[h][0] = -1 marks a categorical head)");
+  FAIL_IF(stats_row && (F < CADRE_PPO_STATS_FIELDS || !stats_scratch || !(target_kl >= 0.f) || (target_kl > 0.f && !stop)),
+          "cadre_ppo_loss_ord: bad stats argument (F >= CADRE_PPO_STATS_FIELDS, target_kl >= 0, a stop flag with target_kl > 0)");
+  FAIL_IF(hp && ((uintptr_t)hp & 7), "cadre_ppo_loss_ord: bad hyper-parameter block (device double[CADRE_HP_FIELDS], 8-byte aligned)");
+  const ppo_stats_t so{stats_row, F, stats_scratch, target_kl, stop};
+  const dim3 grid((B + 15) / 16, 2), block(256);
+#define CADRE_ORD_LAUNCH(S_, H_)                                                                                              \
+  hipLaunchKernelGGL((ppo_loss_ord_kernel<S_, H_>), grid, block, 0, ST(stream), logits, ldl, l_ns, values, ldv, v_ns, actions,  \
+                     commands, old_values, returns, old_logp, adv, B, C, n_out_steer, n_out_throttle, hp, clip, value_coeff,  \
+                     clip_coeff, ent_coeff, inv_b, losses, dlogits, dvalues, scratch, poison, so, ord)
+  if (stats_row && hp) CADRE_ORD_LAUNCH(true, true);
+  else if (stats_row) CADRE_ORD_LAUNCH(true, false);
+  else if (hp) CADRE_ORD_LAUNCH(false, true);
+  else CADRE_ORD_LAUNCH(false, false);
+#undef CADRE_ORD_LAUNCH
+  return (int)hipGetLastError();
+}
+
 // ============================================================================ sampling: argmax(p / q)
+// ORD (the `_ord` entry points here and below): `ord` int32 [64] is the head's bin -> rank table (ordinal.h); ord[0] = -1
+// selects the plain categorical head, which runs exactly the statements of the ORD = false kernel.
+template <bool ORD>
+__device__ __forceinline__ float ord_row_logit(float x, int K, int lane, const int32_t* ord) {
+  if constexpr (ORD) {
+    if (ord[0] >= 0) {
+      float s, t;
+      return ord_logits(x, lane < K, lane < K ? ord[lane] : lane, lane, s, t);
+    }
+  }
+  return x;
+}
+
+template <bool ORD>
 __global__ __launch_bounds__(64) void sample_kernel(const float* logits, int64_t ldl, const float* q, int64_t ldq,
-                                                    int K, int64_t* action, float* logp) {
+                                                    int K, int64_t* action, float* logp, const int32_t* ord) {
   const int r = blockIdx.x, lane = threadIdx.x;
-  const float x = lane < K ? logits[(int64_t)r * ldl + lane] : -INFINITY;
+  const float x = ord_row_logit<ORD>(lane < K ? logits[(int64_t)r * ldl + lane] : -INFINITY, K, lane, ord);
   const float mx = wave_max(x);
   const float se = wave_sum(lane < K ? expf(x - mx) : 0.f);
   const float lg = x - (mx + logf(se));                          // normalised logits
@@ -1834,17 +1914,26 @@ __global__ __launch_bounds__(64) void sample_kernel(const float* logits, int64_t
 extern "C" int cadre_sample(const float* logits, int64_t ldl, const float* q, int64_t ldq, int32_t R, int32_t n_out,
                             int64_t* action, float* logp, void* stream) {
   FAIL_IF(!logits || !q || !action || !logp || R < 1 || n_out < 1 || n_out > 64, "cadre_sample: bad argument");
-  hipLaunchKernelGGL(sample_kernel, dim3(R), dim3(64), 0, ST(stream), logits, ldl, q, ldq, n_out, action, logp);
+  hipLaunchKernelGGL(sample_kernel<false>, dim3(R), dim3(64), 0, ST(stream), logits, ldl, q, ldq, n_out, action, logp, nullptr);
+  return (int)hipGetLastError();
+}
+extern "C" int cadre_sample_ord(const float* logits, int64_t ldl, const float* q, int64_t ldq, int32_t R, int32_t n_out,
+                                int64_t* action, float* logp, const int32_t* ord, void* stream) {
+  FAIL_IF(!logits || !q || !action || !logp || R < 1 || n_out < 1 || n_out > 64 || ldl < n_out || ldq < n_out,
+          "cadre_sample_ord: bad argument");
+  FAIL_IF(!ord, "cadre_sample_ord: null rank table (device int32 [64]; ord[0] = -1 marks the categorical head)");
+  hipLaunchKernelGGL(sample_kernel<true>, dim3(R), dim3(64), 0, ST(stream), logits, ldl, q, ldq, n_out, action, logp, ord);
   return (int)hipGetLastError();
 }
 
 // ============================================================================ categorical evaluate (forward only)
 // Model.evaluate_actions / Categorical_1d.log_probs + entropy (models.py:199-208,
 // distributions.py:101-105) for a batch of rows; one wave per row.
+template <bool ORD>
 __global__ __launch_bounds__(64) void categorical_eval_kernel(const float* logits, int64_t ldl, const int64_t* actions,
-                                                              int K, float* logp, float* entropy) {
+                                                              int K, float* logp, float* entropy, const int32_t* ord) {
   const int r = blockIdx.x, lane = threadIdx.x;
-  const float x = lane < K ? logits[(int64_t)r * ldl + lane] : -INFINITY;
+  const float x = ord_row_logit<ORD>(lane < K ? logits[(int64_t)r * ldl + lane] : -INFINITY, K, lane, ord);
   const float mx = wave_max(x);
   const float se = wave_sum(lane < K ? expf(x - mx) : 0.f);
   const float lg = x - (mx + logf(se));
@@ -1859,15 +1948,26 @@ __global__ __launch_bounds__(64) void categorical_eval_kernel(const float* logit
 extern "C" int cadre_categorical_eval(const float* logits, int64_t ldl, const int64_t* actions, int32_t R, int32_t n_out,
                                       float* logp, float* entropy, void* stream) {
   FAIL_IF(!logits || !actions || !logp || !entropy || R < 1 || n_out < 1 || n_out > 64, "cadre_categorical_eval: bad argument");
-  hipLaunchKernelGGL(categorical_eval_kernel, dim3(R), dim3(64), 0, ST(stream), logits, ldl, actions, n_out, logp, entropy);
+  hipLaunchKernelGGL(categorical_eval_kernel<false>, dim3(R), dim3(64), 0, ST(stream), logits, ldl, actions, n_out, logp, entropy,
+                     nullptr);
+  return (int)hipGetLastError();
+}
+extern "C" int cadre_categorical_eval_ord(const float* logits, int64_t ldl, const int64_t* actions, int32_t R, int32_t n_out,
+                                          float* logp, float* entropy, const int32_t* ord, void* stream) {
+  FAIL_IF(!logits || !actions || !logp || !entropy || R < 1 || n_out < 1 || n_out > 64 || ldl < n_out,
+          "cadre_categorical_eval_ord: bad argument");
+  FAIL_IF(!ord, "cadre_categorical_eval_ord: null rank table (device int32 [64]; ord[0] = -1 marks the categorical head)");
+  hipLaunchKernelGGL(categorical_eval_kernel<true>, dim3(R), dim3(64), 0, ST(stream), logits, ldl, actions, n_out, logp, entropy,
+                     ord);
   return (int)hipGetLastError();
 }
 
 // Categorical_1d.forward (distributions.py:66-83): normalised logits, probs and per-row mode.
+template <bool ORD>
 __global__ __launch_bounds__(64) void categorical_dist_kernel(const float* raw, int64_t ldl, int K, float* logits_out,
-                                                              float* probs_out, int64_t* mode_out) {
+                                                              float* probs_out, int64_t* mode_out, const int32_t* ord) {
   const int r = blockIdx.x, lane = threadIdx.x;
-  const float x = lane < K ? raw[(int64_t)r * ldl + lane] : -INFINITY;
+  const float x = ord_row_logit<ORD>(lane < K ? raw[(int64_t)r * ldl + lane] : -INFINITY, K, lane, ord);
   const float mx = wave_max(x);
   const float se = wave_sum(lane < K ? expf(x - mx) : 0.f);
   const float lg = x - (mx + logf(se));
@@ -1891,8 +1991,16 @@ __global__ __launch_bounds__(64) void categorical_dist_kernel(const float* raw, 
 extern "C" int cadre_categorical_dist(const float* raw, int64_t ldl, int32_t R, int32_t n_out, float* logits_out,
                                       float* probs_out, int64_t* mode_out, void* stream) {
   FAIL_IF(!raw || R < 1 || n_out < 1 || n_out > 64 || ldl < n_out, "cadre_categorical_dist: bad argument");
-  hipLaunchKernelGGL(categorical_dist_kernel, dim3(R), dim3(64), 0, ST(stream), raw, ldl, n_out, logits_out, probs_out,
-                     mode_out);
+  hipLaunchKernelGGL(categorical_dist_kernel<false>, dim3(R), dim3(64), 0, ST(stream), raw, ldl, n_out, logits_out, probs_out,
+                     mode_out, nullptr);
+  return (int)hipGetLastError();
+}
+extern "C" int cadre_categorical_dist_ord(const float* raw, int64_t ldl, int32_t R, int32_t n_out, float* logits_out,
+                                          float* probs_out, int64_t* mode_out, const int32_t* ord, void* stream) {
+  FAIL_IF(!raw || R < 1 || n_out < 1 || n_out > 64 || ldl < n_out, "cadre_categorical_dist_ord: bad argument");
+  FAIL_IF(!ord, "cadre_categorical_dist_ord: null rank table (device int32 [64]; ord[0] = -1 marks the categorical head)");
+  hipLaunchKernelGGL(categorical_dist_kernel<true>, dim3(R), dim3(64), 0, ST(stream), raw, ldl, n_out, logits_out, probs_out,
+                     mode_out, ord);
   return (int)hipGetLastError();
 }
 

@@ -128,6 +128,13 @@ SYMBOLS = {
     "cadre_return_stats": [vp, i32, i32, f64, f64, i32, vp, vp, vp],
     "cadre_gae_multi": [vp, i32, i32, f32, f32, i32, vp, f32, vp],
     "cadre_insert_rows_tl": [vp, vp, i32, i32, i64, i64, i32, i32, i32, vp, i64, vp, vp, vp, vp, vp, vp],
+    # ordinal policy heads (the rank table `ord` is the argument before the stream)
+    "cadre_ppo_loss_ord": [vp, i64, i64, vp, i64, i64, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, vp, f32, f32, f32, f32, f32,
+                           vp, vp, vp, vp, vp, vp, i32, vp, f32, vp, vp, vp],
+    "cadre_sample_ord": [vp, i64, vp, i64, i32, i32, vp, vp, vp, vp],
+    "cadre_sample_rows_ord": [vp, i64, i64, vp, vp, i32, i32, vp, i32, i32, vp, vp, vp, vp, vp],
+    "cadre_categorical_eval_ord": [vp, i64, vp, i32, i32, vp, vp, vp, vp],
+    "cadre_categorical_dist_ord": [vp, i64, i32, i32, vp, vp, vp, vp, vp],
 }
 # entry points of the A/B build only (include/cadre_hip_ab.h; CADRE_BUILD_AB=1 python -m cadre_amd.build, then
 # CADRE_HIP_LIB=.../libcadre_hip_ab.so): bound when the loaded library has them

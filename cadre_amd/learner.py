@@ -123,9 +123,11 @@ class PPOLearnerHIP:
 
     def _mode_key(self):
         """hipGraph key suffix of the update modes: () when all are off (today's graphs).  Device-hyper mode is a mode
-        (("hp",)); the VALUES in the block are not part of any key."""
+        (("hp",)); the VALUES in the block are not part of any key.  Ordinal policy heads are a mode (("ord",)): the loss
+        launch is then cadre_ppo_loss_ord."""
         key = (("stats", self.target_kl),) if self._loss_stats() else ()
-        return key + ((("hp",),) if self._hp_on else ())
+        key = key + ((("hp",),) if self._hp_on else ())
+        return key + ((("ord",),) if getattr(self.a, "ord", None) is not None else ())
 
     # ------------------------------------------------------------------ device-resident hyper-parameters
     def _drop_update_graphs(self, hp=False):
@@ -535,7 +537,23 @@ class PPOLearnerHIP:
         O3, dO3 = w["O3"], w["dO3"]
         if front:
             self._forward(w, B, (0, 1, Z), C, seg=seg, fused_mlp=True)
-        if front and self._hp_on:
+        ord_t = getattr(a, "ord", None)                 # ordinal policy heads: the rank table (static, like every pointer here)
+        if front and ord_t is not None:
+            # one entry point for the four modes: hp NULL = by-value scalars, stats row NULL = no diagnostics
+            stats = self._loss_stats()
+            srow, sscr = self._stats_ws(w, B) if stats else (None, None)
+            tkl = 0.0 if self.target_kl is None else self.target_kl
+            hip.check(L.cadre_ppo_loss_ord(hip.ptr(O3), NP, 2 * B * NP, hip.ptr(O3[1]), NP, 2 * B * NP,
+                                           hip.ptr(w["actions"]), hip.ptr(w["commands"]), hip.ptr(w["old_values"]),
+                                           hip.ptr(w["returns"]), hip.ptr(w["old_logp"]), hip.ptr(w["adv"]), B, C,
+                                           a.n_out[0], a.n_out[1], hip.ptr(self._hp) if self._hp_on else None,
+                                           self.clip, self.vc, self.cc, self.ec, inv_b,
+                                           hip.ptr(w["losses"]), hip.ptr(dO3), hip.ptr(dO3[1]), hip.ptr(w["loss_scratch"]),
+                                           hip.ptr(w["sync"][Z * S:]), hip.ptr(srow), srow.shape[1] if stats else 0,
+                                           hip.ptr(sscr), tkl,
+                                           hip.ptr(self._stop) if (stats and self.target_kl is not None) else None,
+                                           hip.ptr(ord_t), st), "cadre_ppo_loss_ord")
+        elif front and self._hp_on:
             loss_args = (hip.ptr(O3), NP, 2 * B * NP, hip.ptr(O3[1]), NP, 2 * B * NP,
                          hip.ptr(w["actions"]), hip.ptr(w["commands"]), hip.ptr(w["old_values"]),
                          hip.ptr(w["returns"]), hip.ptr(w["old_logp"]), hip.ptr(w["adv"]), B, C,

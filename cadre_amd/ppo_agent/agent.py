@@ -9,7 +9,7 @@ import torch
 
 from .. import hip
 from ..learner import PPOLearnerHIP
-from .models import LSTM, Model, _cfg, arena_of, create_model, get_vae_output
+from .models import LSTM, Model, _cfg, arena_of, create_model, get_vae_output, ordinal_rank, resolve_ordinal  # noqa: F401
 
 
 def command_rows(commands, command_num):
@@ -62,6 +62,14 @@ class CadreAgent(object):
     def __init__(self, rank, model_cfg, frame, STEER_CONTROL, THROTTLE_CONTROL, ent_coeff, value_coeff, clip_coeff,
                  clip):
         self.rank = rank
+        # ordinal policy heads (model_cfg["ordinal_policy"], opt-in): True orders a head by its control table; create_model
+        # then gets the explicit permutations.  Absent / None / False: model_cfg goes through untouched.
+        spec = _cfg(model_cfg, "ordinal_policy")
+        if spec is not None and spec is not False:
+            ranks = resolve_ordinal(spec, _cfg(model_cfg, "num_output"), {"steer": STEER_CONTROL, "throttle": THROTTLE_CONTROL})
+            model_cfg = dict(model_cfg)
+            model_cfg["ordinal_policy"] = None if ranks is None else {h: (False if r is None else r)
+                                                                       for h, r in zip(("steer", "throttle"), ranks)}
         self.vae_model, self.model_dict = create_model(model_cfg, load_vae=True)
         self.use_lstm = _cfg(model_cfg, "use_lstm")
         self.command_num = _cfg(model_cfg, "command_num")
@@ -77,6 +85,7 @@ class CadreAgent(object):
         self.hidden_state = (torch.zeros(1, self.lstm_input, device=self.device),
                              torch.zeros(1, self.lstm_input, device=self.device))
         self.arena = arena_of(self.model_dict)
+        self.ordinal_rank = self.arena.ordinal_rank     # host copy: [steer, throttle] rank lists (None: categorical), or None
         self.learner = PPOLearnerHIP(self.arena, clip, value_coeff, clip_coeff, ent_coeff, seq_length=frame)
         self.arena._learner = self.learner
         self.mutate_route = _cfg(model_cfg, "mutate_route", True)
@@ -151,9 +160,19 @@ class CadreAgent(object):
         q = q_host.to(self.device, non_blocking=True)
         action = torch.empty(1, dtype=torch.int64, device=self.device)
         logp = torch.empty(1, 1, device=self.device)
-        hip.check(hip.lib().cadre_sample(hip.ptr(O3[tower_row]), O3.shape[-1], hip.ptr(q), K, 1, K, hip.ptr(action),
-                                         hip.ptr(logp), hip.stream()), "cadre_sample")
+        self._sample_launch(O3, tower_row, K, q, action, logp)
         return action, logp
+
+    def _sample_launch(self, O3, tower_row, K, q, action, logp):
+        """cadre_sample on actor-tower row `tower_row` of O3 (0 steer, 2 throttle), or cadre_sample_ord with the head's rank
+        table when the agent has ordinal heads."""
+        L, ord_t = hip.lib(), self.arena.ord
+        if ord_t is not None:
+            hip.check(L.cadre_sample_ord(hip.ptr(O3[tower_row]), O3.shape[-1], hip.ptr(q), K, 1, K, hip.ptr(action),
+                                         hip.ptr(logp), hip.ptr(ord_t[tower_row // 2]), hip.stream()), "cadre_sample_ord")
+        else:
+            hip.check(L.cadre_sample(hip.ptr(O3[tower_row]), O3.shape[-1], hip.ptr(q), K, 1, K, hip.ptr(action),
+                                     hip.ptr(logp), hip.stream()), "cadre_sample")
 
     def act(self, tick_data):
         """agent.py:114-141.  Sampling consumes the global torch CPU generator exactly like the
@@ -203,8 +222,7 @@ class CadreAgent(object):
         O3, _, _ = self.learner.infer(feat[:, :self.lstm_input], (command, command))
         nS, nT = self.arena.n_out
         for j, (row, K) in enumerate(((0, nS), (2, nT))):
-            hip.check(L.cadre_sample(hip.ptr(O3[row]), O3.shape[-1], hip.ptr(st["d_q"][j]), K, 1, K, hip.ptr(st["action"][j:]),
-                                     hip.ptr(st["logp"][j:]), stream), "cadre_sample")
+            self._sample_launch(O3, row, K, st["d_q"][j], st["action"][j:], st["logp"][j:])
         return O3
 
     def _act_graphed(self, tick_data):
@@ -370,9 +388,14 @@ class CadreAgent(object):
         action = torch.empty(N, 2, dtype=torch.int64, device=dev)
         logp = torch.empty(N, 2, device=dev)
         value = torch.empty(N, 2, device=dev)
-        hip.check(L.cadre_sample_rows(hip.ptr(O3), O3.stride(1), O3.stride(0), hip.ptr(pos_d), hip.ptr(cmd_d), N, a.C,
-                                      hip.ptr(q_d), nS, nT, hip.ptr(action), hip.ptr(logp), hip.ptr(value), stream),
-                  "cadre_sample_rows")
+        if a.ord is not None:
+            hip.check(L.cadre_sample_rows_ord(hip.ptr(O3), O3.stride(1), O3.stride(0), hip.ptr(pos_d), hip.ptr(cmd_d), N, a.C,
+                                              hip.ptr(q_d), nS, nT, hip.ptr(action), hip.ptr(logp), hip.ptr(value),
+                                              hip.ptr(a.ord), stream), "cadre_sample_rows_ord")
+        else:
+            hip.check(L.cadre_sample_rows(hip.ptr(O3), O3.stride(1), O3.stride(0), hip.ptr(pos_d), hip.ptr(cmd_d), N, a.C,
+                                          hip.ptr(q_d), nS, nT, hip.ptr(action), hip.ptr(logp), hip.ptr(value), stream),
+                      "cadre_sample_rows")
         # route quirk + window caches (one host sync for the normalised route, as act() has)
         rn_h = rn_d.cpu().numpy() if rn_d is not None else None
         out = ActBatch()

@@ -15,14 +15,21 @@ from .utils import init
 class CategoricalHIP(object):
     """What `Categorical(logits=x)` exposes to the reference's callers (distributions.py:81-105):
     `.logits` (normalised), `.probs`, `.sample()`, `.log_prob(a)`, `.entropy()` — device tensors
-    produced by the HIP kernels from the raw head outputs `raw` [R, ld] (first K columns valid)."""
+    produced by the HIP kernels from the raw head outputs `raw` [R, ld] (first K columns valid).  `ord`: the head's
+    device rank table int32 [64] when the head is ordinal (the `_ord` kernels: the same quantities, in bin space, of the
+    ordinal transform of `raw`), None for the categorical head."""
 
-    def __init__(self, raw, K):
-        self._raw, self.K = raw, K
+    def __init__(self, raw, K, ord=None):
+        self._raw, self.K, self._ord = raw, K, ord
         R = raw.shape[0]
         self.logits = torch.empty(R, K, device=raw.device)
         self.probs = torch.empty(R, K, device=raw.device)
         self._mode = torch.empty(R, dtype=torch.int64, device=raw.device)
+        if ord is not None:
+            hip.check(hip.lib().cadre_categorical_dist_ord(hip.ptr(raw), raw.stride(0), R, K, hip.ptr(self.logits),
+                                                           hip.ptr(self.probs), hip.ptr(self._mode), hip.ptr(ord),
+                                                           hip.stream()), "cadre_categorical_dist_ord")
+            return
         hip.check(hip.lib().cadre_categorical_dist(hip.ptr(raw), raw.stride(0), R, K, hip.ptr(self.logits),
                                                    hip.ptr(self.probs), hip.ptr(self._mode), hip.stream()),
                   "cadre_categorical_dist")
@@ -34,6 +41,11 @@ class CategoricalHIP(object):
         q = torch.empty(R, self.K).exponential_(1).to(self._raw.device)
         action = torch.empty(R, dtype=torch.int64, device=self._raw.device)
         logp = torch.empty(R, 1, device=self._raw.device)
+        if self._ord is not None:
+            hip.check(hip.lib().cadre_sample_ord(hip.ptr(self._raw), self._raw.stride(0), hip.ptr(q), self.K, R, self.K,
+                                                 hip.ptr(action), hip.ptr(logp), hip.ptr(self._ord), hip.stream()),
+                      "cadre_sample_ord")
+            return action
         hip.check(hip.lib().cadre_sample(hip.ptr(self._raw), self._raw.stride(0), hip.ptr(q), self.K, R, self.K,
                                          hip.ptr(action), hip.ptr(logp), hip.stream()), "cadre_sample")
         return action
@@ -45,6 +57,11 @@ class CategoricalHIP(object):
             raise ValueError("expected one action per row (%d), got %d" % (R, act.numel()))
         logp = torch.empty(R, device=self._raw.device)
         ent = torch.empty(R, device=self._raw.device)
+        if self._ord is not None:
+            hip.check(hip.lib().cadre_categorical_eval_ord(hip.ptr(self._raw), self._raw.stride(0), hip.ptr(act), R, self.K,
+                                                           hip.ptr(logp), hip.ptr(ent), hip.ptr(self._ord), hip.stream()),
+                      "cadre_categorical_eval_ord")
+            return logp, ent
         hip.check(hip.lib().cadre_categorical_eval(hip.ptr(self._raw), self._raw.stride(0), hip.ptr(act), R, self.K,
                                                    hip.ptr(logp), hip.ptr(ent), hip.stream()), "cadre_categorical_eval")
         return logp, ent
@@ -81,10 +98,10 @@ class Categorical_1d(nn.Module):
         arena = getattr(self, "_cadre_arena", None)
         if arena is None:
             raise hip.CadreHipError("Categorical_1d is not bound to a parameter arena (build it with create_model)")
-        from .models import _module_net
+        from .models import _module_net, module_ord
         _a, learner, g = _module_net(self)
         raw, _value = learner.mlp_module_forward(g, x)
-        self.dis_cat = CategoricalHIP(raw[:, :self.num_outputs].clone(), self.num_outputs)
+        self.dis_cat = CategoricalHIP(raw[:, :self.num_outputs].clone(), self.num_outputs, module_ord(self)[0])
         self.logits = self.dis_cat.logits
         self.probs = self.dis_cat.probs
         self._last_action = None

@@ -7,7 +7,7 @@ import os
 import torch
 import torch.nn as nn
 
-from ..arena import PPOArena
+from ..arena import HEADS, PPOArena
 from ..encoder import DANetEncoderHIP
 from .. import autograd, hip
 from .distributions import Categorical_1d
@@ -56,6 +56,100 @@ def get_vae_output(model_cfg):
     md = _cfg(model_cfg, "measurement_dim")
     obs_dim = (2 * z if name in ("CoPM", "CoPM w/o att") else z) + md
     return obs_dim, vae_params
+
+
+# ----------------------------------------------------------------------------- ordinal policy heads
+ORDINAL_EPS = 1e-8      # the reference's constant (distributions.py:45-79); CADRE_ORD_EPS of csrc/ordinal.h
+
+
+def ordinal_rank(control, key=None):
+    """rank list of an ordinal head from its control table {bin: value}: rank[k] = position of bin k in ascending order of
+    key(value) (a stable argsort).  Default key: the value itself for scalars, throttle - brake for [throttle, brake] pairs.
+    Equal keys raise CadreHipError: an ordinal head needs a strict order."""
+    K = len(control)
+    if sorted(control.keys()) != list(range(K)):
+        raise hip.CadreHipError("ordinal_rank: the control table must have the bins 0 .. %d as keys" % (K - 1))
+    if key is None:
+        def key(v):
+            try:
+                return float(v)
+            except (TypeError, ValueError):
+                th, br = v
+                return float(th) - float(br)
+    keys = [key(control[k]) for k in range(K)]
+    order = sorted(range(K), key=lambda k: keys[k])
+    for a, b in zip(order, order[1:]):
+        if not keys[a] < keys[b]:
+            raise hip.CadreHipError("ordinal_rank: bins %d and %d have the same key %r; an ordinal head needs a strict order"
+                                    % (a, b, keys[a]))
+    rank = [0] * K
+    for r, k in enumerate(order):
+        rank[k] = r
+    return rank
+
+
+def check_ordinal_rank(rank, K, head):
+    """An explicit permutation for a head with K bins -> list of K ints, or CadreHipError."""
+    try:
+        out = [int(r) for r in rank]
+        exact = all(float(r) == int(r) for r in rank)
+    except (TypeError, ValueError):
+        out, exact = None, False
+    if out is None or not exact or len(out) != K or sorted(out) != list(range(K)):
+        raise hip.CadreHipError("ordinal_policy: the %s rank table must be a permutation of 0 .. %d (got %r)" % (head, K - 1, rank))
+    return out
+
+
+def resolve_ordinal(spec, n_out, controls=None):
+    """model_cfg["ordinal_policy"] -> None (off) or [steer, throttle], each None (categorical head) or a rank list.
+    spec: None / False (off), True (both heads), or {"steer": s, "throttle": s} with s True, False or an explicit
+    permutation.  True orders a head by its control table (`controls` = {head: table}, via ordinal_rank); without a table
+    (create_model called on its own) it means the identity order."""
+    if spec is None or spec is False:
+        return None
+    if spec is True:
+        spec = {"steer": True, "throttle": True}
+    if not hasattr(spec, "keys") or any(k not in HEADS for k in spec.keys()):
+        raise hip.CadreHipError("ordinal_policy: True, False or a dict with the keys 'steer' / 'throttle' (got %r)" % (spec,))
+    out = []
+    for head in HEADS:
+        s, K = spec.get(head, False), int(n_out[head])
+        if s is None or s is False:
+            out.append(None)
+        elif s is True:
+            if controls is None or controls.get(head) is None:
+                out.append(list(range(K)))
+            else:
+                if len(controls[head]) != K:
+                    raise hip.CadreHipError("ordinal_policy: the %s control table has %d bins, the head %d outputs"
+                                            % (head, len(controls[head]), K))
+                out.append(ordinal_rank(controls[head]))
+        else:
+            out.append(check_ordinal_rank(s, K, head))
+    return out if any(r is not None for r in out) else None
+
+
+
+def ordinal_logits(raw, rank):
+    """The ordinal head in torch (differentiable): raw [N, K] threshold units in rank space -> unnormalised bin logits
+    [N, K].  Written like the kernels: sigmoid(-x) for the complement, the same eps, cumsum / reversed cumsum, rank gather."""
+    u = torch.log(torch.sigmoid(raw) + ORDINAL_EPS)
+    w = torch.log(torch.sigmoid(-raw) + ORDINAL_EPS)
+    w_next = torch.cat([w[:, 1:], torch.zeros_like(w[:, :1])], dim=1)
+    z = u.cumsum(1) + w_next.flip(1).cumsum(1).flip(1)               # z_r = sum_{j <= r} u_j + sum_{j > r} w_j
+    return z.index_select(1, torch.as_tensor(rank, dtype=torch.int64, device=raw.device))
+
+
+def module_ord(module):
+    """(device int32 [64] rank table, host rank list) of the head a bound module belongs to, or (None, None) for a
+    categorical head."""
+    arena = getattr(module, "_cadre_arena", None)
+    if arena is None or getattr(arena, "ord", None) is None:
+        return None, None
+    h = HEADS.index(module._cadre_name.split("_")[0])
+    if arena.ordinal_rank[h] is None:
+        return None, None
+    return arena.ord[h], arena.ordinal_rank[h]
 
 
 def _module_net(module):
@@ -143,8 +237,13 @@ class Model(nn.Module):
         q = torch.empty(R, K).exponential_(1).to(obs_feature.device)
         action = torch.empty(R, dtype=torch.int64, device=obs_feature.device)
         logp = torch.empty(R, 1, device=obs_feature.device)
-        hip.check(hip.lib().cadre_sample(hip.ptr(logits), logits.stride(0), hip.ptr(q), K, R, K, hip.ptr(action),
-                                         hip.ptr(logp), hip.stream()), "cadre_sample")
+        ord_d, _rank = module_ord(self)
+        if ord_d is not None:
+            hip.check(hip.lib().cadre_sample_ord(hip.ptr(logits), logits.stride(0), hip.ptr(q), K, R, K, hip.ptr(action),
+                                                 hip.ptr(logp), hip.ptr(ord_d), hip.stream()), "cadre_sample_ord")
+        else:
+            hip.check(hip.lib().cadre_sample(hip.ptr(logits), logits.stride(0), hip.ptr(q), K, R, K, hip.ptr(action),
+                                             hip.ptr(logp), hip.stream()), "cadre_sample")
         self.control._last_action, self.control._last_logp = action, logp
         return value.clone(), action, obs_feature.clone().detach()
 
@@ -152,8 +251,11 @@ class Model(nn.Module):
         """models.py:199-208 -> (value [N,1], log_prob [N,1], entropy [N,1]); differentiable when gradients are wanted
         (towers on the HIP kernels, the categorical tail on [N, n_out] in torch)."""
         tw = self._towers(obs_feature)
+        ord_d, rank = module_ord(self)
         if tw is not None:
             raw, value = tw
+            if rank is not None:
+                raw = ordinal_logits(raw, rank)
             logits = raw - raw.logsumexp(dim=-1, keepdim=True)           # distributions.py:66-83 Categorical(logits=...)
             logp = logits.gather(1, action.reshape(-1, 1).to(torch.int64))
             ent = -(logits.exp() * logits).sum(-1, keepdim=True)
@@ -164,6 +266,11 @@ class Model(nn.Module):
         logp = torch.empty(R, 1, device=obs_feature.device)
         ent = torch.empty(R, 1, device=obs_feature.device)
         act = action.reshape(-1).to(torch.int64).contiguous()
+        if ord_d is not None:
+            hip.check(hip.lib().cadre_categorical_eval_ord(hip.ptr(logits), logits.stride(0), hip.ptr(act), R,
+                                                           self.control.num_outputs, hip.ptr(logp), hip.ptr(ent),
+                                                           hip.ptr(ord_d), hip.stream()), "cadre_categorical_eval_ord")
+            return value.clone(), logp, ent
         hip.check(hip.lib().cadre_categorical_eval(hip.ptr(logits), logits.stride(0), hip.ptr(act), R,
                                                    self.control.num_outputs, hip.ptr(logp), hip.ptr(ent),
                                                    hip.stream()), "cadre_categorical_eval")
@@ -221,7 +328,10 @@ def create_model(model_cfg, load_vae=False):
         raise hip.CadreHipError("command_num=%r: 1 .. 16 navigation commands (the row sort keeps one counter per command in a "
                                 "wave; agent_config.py ships command_num=4)" % (command_num,))
     n_out = _cfg(model_cfg, "num_output")
-    arena = PPOArena(device, obs_dim, {"steer": n_out["steer"], "throttle": n_out["throttle"]}, command_num)
+    # ordinal policy heads (opt-in): explicit permutations, or True = the identity order (CadreAgent resolves True through
+    # its control tables before it calls this)
+    ordinal = resolve_ordinal(_cfg(model_cfg, "ordinal_policy"), n_out)
+    arena = PPOArena(device, obs_dim, {"steer": n_out["steer"], "throttle": n_out["throttle"]}, command_num, ordinal=ordinal)
     model_dict = {}
     for c in range(command_num):
         for head in ("steer", "throttle"):

@@ -515,6 +515,49 @@ int cadre_categorical_eval(const float* logits, int64_t ldl, const int64_t* acti
 int cadre_categorical_dist(const float* raw, int64_t ldl, int32_t R, int32_t n_out, float* logits_out,
                            float* probs_out, int64_t* mode_out, void* stream);
 
+/* ---------------------------------------------------------------- ordinal policy heads (opt-in, csrc/ordinal.h)
+ * The ordinal parameterisation of Tang & Agrawal, "Discretizing Continuous Action Space for On-Policy Optimization" (the
+ * commented-out "ordinal policy" block of distributions.py:45-79) for heads whose bins are an ordered quantity.  Per head
+ * with K bins, rank[k] in 0 .. K-1 is the position of bin k in ascending order of its control value (a permutation),
+ * bin[r] its inverse, and column j of the actor tower's raw output x is threshold unit j in RANK space.  With eps = 1e-8:
+ *   s_j = sigmoid(x_j)   t_j = sigmoid(-x_j)   u_j = log(s_j + eps)   w_j = log(t_j + eps)
+ *   z_r = sum_{j <= r} u_j + sum_{j > r} w_j            (mask1 of the reference: a[i][j] = 1 iff i >= j)
+ *   logit of bin k = z_{rank[k]}
+ * From there everything is the categorical head on these logits, in bin space: normalised logits, probs, entropy,
+ * log-prob, argmax(p / q) sampling with q[k] belonging to bin k (lowest bin index wins ties), mode, diagnostics.
+ * Backward, with g_k = d total / d logit_k (what dlogits holds for a categorical head) and G_r = g_{bin[r]}:
+ *   d total / d x_j = s_j t_j / (s_j + eps) * sum_{r >= j} G_r  -  s_j t_j / (t_j + eps) * sum_{r < j} G_r
+ * which is what dlogits holds for an ordinal head: the gradient with respect to the raw tower outputs.  The running sums
+ * are wave scans with one fixed combination order: two launches on the same inputs give the same bits.
+ * Rank table `ord`: device int32 [2][64], head-major, ord[h][k] = rank[k] for k < K_h; ord[h][0] = -1 marks head h as the
+ * plain categorical head.  A single-head table is int32 [64] with the same convention.  The caller guarantees a
+ * permutation of 0 .. K-1 (the kernels do not check).  With the -1 marker every output is bit-identical to the entry
+ * point that is extended.
+ *
+ * cadre_ppo_loss_ord: cadre_ppo_loss / _stats / _hp / _stats_hp in one entry point.  hp == NULL: clip, value_coeff,
+ * clip_coeff and ent_coeff are the by-value arguments, else they are read from the block and the by-value ones are
+ * ignored.  stats_row == NULL: no diagnostics (F, stats_scratch, target_kl, stop are then ignored).  Same grid, scratch
+ * sizes and last-arriver reduction as the entry points it extends. */
+int cadre_ppo_loss_ord(const float* logits, int64_t ldl, int64_t l_ns, const float* values, int64_t ldv,
+                       int64_t v_ns, const int64_t* actions, const int32_t* commands, const float* old_values,
+                       const float* returns, const float* old_logp, const float* adv, int32_t B, int32_t C,
+                       int32_t n_out_steer, int32_t n_out_throttle, double* hp, float clip, float value_coeff,
+                       float clip_coeff, float ent_coeff, float inv_b, float* losses, float* dlogits, float* dvalues,
+                       float* scratch, const int32_t* poison, float* stats_row, int32_t F, float* stats_scratch,
+                       float target_kl, int32_t* stop, const int32_t* ord, void* stream);
+/* cadre_sample / cadre_categorical_eval / cadre_categorical_dist with one head's rank table ord int32 [64] (ldl >= n_out
+ * is checked here); cadre_categorical_dist_ord returns normalised logits, probs and mode in bin space. */
+int cadre_sample_ord(const float* logits, int64_t ldl, const float* q, int64_t ldq, int32_t R, int32_t n_out,
+                     int64_t* action, float* logp, const int32_t* ord, void* stream);
+int cadre_categorical_eval_ord(const float* logits, int64_t ldl, const int64_t* actions, int32_t R, int32_t n_out,
+                               float* logp, float* entropy, const int32_t* ord, void* stream);
+int cadre_categorical_dist_ord(const float* raw, int64_t ldl, int32_t R, int32_t n_out, float* logits_out,
+                               float* probs_out, int64_t* mode_out, const int32_t* ord, void* stream);
+/* cadre_sample_rows with both heads' tables ord int32 [2][64]. */
+int cadre_sample_rows_ord(const float* O3, int64_t ldo, int64_t z_str, const int32_t* pos, const int32_t* cmd, int32_t N,
+                          int32_t C, const float* q, int32_t K_steer, int32_t K_throttle, int64_t* action, float* logp,
+                          float* value, const int32_t* ord, void* stream);
+
 /* Initial LSTM state of every net z < Z: Hs[z*z_str ..] <- h0[(z / x_div)*n_per ..], same for Cs <- c0 (n_per floats
  * each, agent.py:166-175 hidden_state_batch shared by a head's command nets) and dC (Z*n_per floats, may be NULL) <- 0 */
 int cadre_lstm_init(const float* h0, const float* c0, float* Hs, float* Cs, float* dC, int64_t n_per,
