@@ -157,18 +157,21 @@ def dense_products(A, B):
     return products, An.shape[1], An.shape[0] * N
 
 
-def c_bar_of(groups, y64, mag, scale=None, shift=None, resid=None, act=0, slope=0.01, n_sample=4096, seed=0, what=""):
+def c_bar_of(groups, y64, mag, scale=None, shift=None, resid=None, act=0, slope=0.01, n_sample=4096, seed=0, what="", cap=None, idx=None):
     """c_bar of one test case.  groups: [(products, K, n_out)] from conv_products / dense_products — several groups form ONE
     accumulation (the shortcut of cadre_conv3x3_s1x rides behind conv2's k-tiles).  A sample of output elements is summed strictly
     sequentially in fp32, the fp32 epilogue applied, and the worst error against y64 in units doubled.  y64 / mag: the float64
-    reference of the SAME (pre-pool) outputs, flat in the products' output order."""
+    reference of the SAME (pre-pool) outputs, flat in the products' output order.  cap: the a-priori bound c_bar is asserted under
+    (default K + 4, the bf16 kernels' exact products; tests/f32_parity.py passes the one it derives for rounded fp32 products).  idx: the
+    flat output indices to sum in place of the random sample (tests/f32_parity.py: every output of a small case)."""
     y = np.asarray(f64(y64)).reshape(-1)
     m = np.asarray(f64(mag)).reshape(-1)
     n_out = groups[0][2]
     assert all(g[2] == n_out for g in groups) and y.size == n_out
     K = sum(g[1] for g in groups)
     N = y64.shape[-1]
-    idx = np.sort(np.random.RandomState(seed).choice(n_out, min(n_sample, n_out), replace=False)).astype(np.int64)
+    if idx is None:
+        idx = np.sort(np.random.RandomState(seed).choice(n_out, min(n_sample, n_out), replace=False)).astype(np.int64)
     step = max(1, (1 << 24) // K)                          # <= 64 MB of products at a time
     acc = np.empty(len(idx), np.float32)
     for s in range(0, len(idx), step):
@@ -192,7 +195,8 @@ def c_bar_of(groups, y64, mag, scale=None, shift=None, resid=None, act=0, slope=
     assert v.dtype == np.float32
     worst = float(np.max(np.abs(v.astype(np.float64) - y[idx]) / (U * m[idx])))
     c_bar = 2.0 * worst
-    assert 0 < c_bar <= K + 4, "%s: c_bar %.3g outside (0, K + 4 = %d]: the helper is wrong" % (what, c_bar, K + 4)
+    cap = K + 4 if cap is None else cap
+    assert 0 < c_bar <= cap, "%s: c_bar %.3g outside (0, cap = %d]: the helper is wrong" % (what, c_bar, cap)
     return c_bar
 
 
