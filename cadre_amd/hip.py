@@ -135,6 +135,8 @@ SYMBOLS = {
     "cadre_sample_rows_ord": [vp, i64, i64, vp, vp, i32, i32, vp, i32, i32, vp, vp, vp, vp, vp],
     "cadre_categorical_eval_ord": [vp, i64, vp, i32, i32, vp, vp, vp, vp],
     "cadre_categorical_dist_ord": [vp, i64, i32, i32, vp, vp, vp, vp, vp],
+    # training checkpoints: range table, n_ranges, staging (NULL: digests only), digests, stream
+    "cadre_state_capture": [vp, i32, vp, vp, vp],
 }
 # entry points of the A/B build only (include/cadre_hip_ab.h; CADRE_BUILD_AB=1 python -m cadre_amd.build, then
 # CADRE_HIP_LIB=.../libcadre_hip_ab.so): bound when the loaded library has them
@@ -195,6 +197,10 @@ PPO_STATS_FIELDS = 8  # CADRE_PPO_STATS_FIELDS (include/cadre_hip.h): loss diagn
 
 RS_SCALE, RS_CARRY = 6, 8  # CADRE_RS_SCALE / CADRE_RS_CARRY: the return-statistics block (count, mean, M2 per head first)
 
+CAPTURE_MAX_RANGES = 65535        # CADRE_CAPTURE_MAX_RANGES
+CAPTURE_BAD_RANGE = 2 ** 64 - 1   # CADRE_CAPTURE_BAD_RANGE: digest slot of a record the launch found malformed
+DIGEST_K = 0x9E3779B97F4A7C15     # the digest's odd multiplier (include/cadre_hip.h)
+
 N_CALLS = 0         # C-ABI calls checked so far (one kernel launch each, cadre_clip_adam_graph three): launch census
 
 
@@ -216,6 +222,29 @@ def ptr(t):
 
 def stream():
     return torch.cuda.current_stream().cuda_stream
+
+
+def capture_table(records, device):
+    """Device range table of cadre_state_capture from host records [(src pointer, dst_off, bytes), ...] (int64 [n][3]).
+    Everything the launch itself cannot report is refused here: bytes no multiple of 4 (state is fp32, fp64, int32 or
+    int64), pointers or offsets off a 4-byte boundary, negative values, too many ranges."""
+    if len(records) > CAPTURE_MAX_RANGES:
+        raise CadreHipError("cadre_state_capture: %d ranges; at most %d per launch" % (len(records), CAPTURE_MAX_RANGES))
+    for k, (src, off, nbytes) in enumerate(records):
+        if nbytes < 0 or nbytes % 4 or off < 0 or off % 4 or src % 4 or (nbytes and not src):
+            raise CadreHipError("cadre_state_capture: range %d (src 0x%x, dst_off %d, %d bytes) is not a run of 32-bit words: "
+                                "bytes must be a multiple of 4, src and dst_off 4-byte aligned" % (k, src, off, nbytes))
+    return torch.tensor([[int(v) for v in r] for r in records], dtype=torch.int64).reshape(len(records), 3).to(device)
+
+
+def state_capture(table, n_ranges, staging, digests):
+    """cadre_state_capture on the current stream: `table` from capture_table, `staging` a device byte buffer or None
+    (digests only), `digests` a device int64 tensor of n_ranges slots (the uint64 digests' bit patterns)."""
+    if digests.dtype != torch.int64 or digests.numel() < n_ranges or not digests.is_contiguous():
+        raise CadreHipError("cadre_state_capture: digests must be a contiguous int64 tensor of at least %d slots" % n_ranges)
+    if table.dtype != torch.int64 or table.numel() < 3 * n_ranges or not table.is_contiguous():
+        raise CadreHipError("cadre_state_capture: the range table holds fewer than %d records" % n_ranges)
+    check(lib().cadre_state_capture(ptr(table), n_ranges, ptr(staging), ptr(digests), stream()), "cadre_state_capture")
 
 
 # Optional launch profiler (bench.py): when PROFILE is a list, every gemm launch is bracketed by

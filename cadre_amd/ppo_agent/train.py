@@ -6,6 +6,7 @@ import os
 import numpy as np
 import torch
 
+from .. import checkpoint as ckpt
 from .. import hip
 from .agent import CadreAgent
 from .chief import chief_step
@@ -84,6 +85,65 @@ def _reward_scaling(train_cfg, shared_grad_buffers=None):
         raise hip.CadreHipError("train_cfg.reward_scaling needs a single rank (world size %d): each rank would grow its "
                                 "own return statistics" % shared_grad_buffers.dist_world())
     return kw
+
+
+# ----------------------------------------------------------------------------- training checkpoints
+def _checkpointing(train_cfg, shared_grad_buffers=None):
+    """train_cfg["checkpoint_interval"] (absent / None / 0: off; else a positive integer of episodes) and
+    train_cfg["resume_from"] (absent / None, or the path of a checkpoint) -> (interval or None, path or None).  Like
+    target_kl both are refused with several ranks: the generators and scalers of the other ranks are not captured."""
+    interval, path = _get(train_cfg, "checkpoint_interval"), _get(train_cfg, "resume_from")
+    if interval is not None:
+        if isinstance(interval, bool) or not isinstance(interval, (int, np.integer)) or interval < 0:
+            raise ValueError("train_cfg.checkpoint_interval: expected None, 0 or a positive integer of episodes (got %r)"
+                             % (interval,))
+        interval = int(interval) or None
+    if path is not None:
+        if not isinstance(path, (str, os.PathLike)) or not os.fspath(path):
+            raise ValueError("train_cfg.resume_from: expected None or the path of a checkpoint (got %r)" % (path,))
+        path = os.fspath(path)
+    for key, v in (("checkpoint_interval", interval), ("resume_from", path)):
+        if v is not None and shared_grad_buffers is not None and shared_grad_buffers.dist_world() > 1:
+            raise hip.CadreHipError("train_cfg.%s needs a single rank (world size %d): the checkpoint is per rank and the "
+                                    "generators and scalers of the other ranks are not captured"
+                                    % (key, shared_grad_buffers.dist_world()))
+    return interval, path
+
+
+class _Checkpointer:
+    """The checkpoint side of train() / train_vec(): resume before the first episode, a capture after every `interval`-th
+    episode.  A capture is written just before the next one is taken (and before the loop returns), so the copy to the
+    host runs beside the next rollout and the loop never waits for it; the newest file is therefore one interval behind
+    the newest capture."""
+
+    def __init__(self, work_dir, interval, agent, rollouts, callback=None):
+        self.interval, self.agent, self.rollouts, self.callback = interval, agent, rollouts, callback
+        self.dir = os.path.join(work_dir, "checkpoints")
+        self.pending = None
+        if interval is not None:
+            check_exist(self.dir)
+
+    def resume(self, path):
+        """restore() from `path`; returns the episode the loop continues at."""
+        state = ckpt.load(path)
+        if state.get("episode") is None:
+            raise ValueError("train_cfg.resume_from: %s holds no episode number (it was not written by a training loop)" % path)
+        ckpt.restore(self.agent, state, self.rollouts, self.agent.reward_scaler)
+        return int(state["episode"]) + 1
+
+    def flush(self):
+        if self.pending is not None:
+            episode, cap = self.pending
+            self.pending = None
+            path = cap.save(os.path.join(self.dir, "ckpt_{}.pt".format(episode)))
+            if self.callback is not None:
+                self.callback("checkpoint", episode=episode, path=path)
+
+    def after_episode(self, episode):
+        if self.interval is None or (episode + 1) % self.interval:
+            return
+        self.flush()
+        self.pending = (episode, ckpt.capture(self.agent, self.rollouts, self.agent.reward_scaler, episode=episode))
 
 
 def _time_limit_pair(flag):
@@ -426,10 +486,16 @@ def train(rank, train_cfg, agent_cfg, env_cfg, rollout_cfg, traffic_light=None, 
         shared_grad_buffers = Shared_grad_buffers(agent.model_dict, device)
     rs = _reward_scaling(train_cfg, shared_grad_buffers)
     agent.reward_scaler = None if rs is None else ReturnScaler(1, rollout_cfg.gamma, device=device, **rs)
+    ck_interval, ck_resume = _checkpointing(train_cfg, shared_grad_buffers)
+    ck, first_episode = None, 0
+    if ck_interval is not None or ck_resume is not None:
+        ck = _Checkpointer(env.work_dir, ck_interval, agent, [(steer_rollout, throttle_rollout)])
+        if ck_resume is not None:                # (the environment is the caller's: it restarts through reset())
+            first_episode = ck.resume(ck_resume)
     obs = env.reset()
     done = False
     log_stats = bool(_get(train_cfg, "log_stats", False))
-    for episode in range(train_cfg.max_episode):
+    for episode in range(first_episode, train_cfg.max_episode):
         for _ in range(num_steps):
             command = obs["command"]
             raw = dict(obs, rgb=obs["rgb"].copy(), route_fig=obs["route_fig"].copy()) if recorder is not None else None
@@ -461,6 +527,10 @@ def train(rank, train_cfg, agent_cfg, env_cfg, rollout_cfg, traffic_light=None, 
                 logger.log(stats_line(episode, stats))
         if episode % train_cfg.save_interval == 0 and rank == 0:
             agent.save_snapshot(os.path.join(model_dir, "ppo_model_{}.pt".format(episode)))
+        if ck is not None:                       # (after the snapshot: building its nn.Modules draws from the generator)
+            ck.after_episode(episode)
+    if ck is not None:
+        ck.flush()
     if son_process_counter is not None:
         son_process_counter.increment()
     print("process {} finished.".format(rank))
@@ -540,7 +610,14 @@ def train_vec(rank, train_cfg, agent_cfg, env_cfg, rollout_cfg, num_envs, env_cl
     also passes agent, envs, rollouts and reward_scaler.
     train_cfg["reward_scaling"] (None / absent, True, or {"clip", "epsilon"}; single rank only): return-based reward
     scaling through one ReturnScaler kept as `agent.reward_scaler`.  An environment that reports info["time_limit"] (a
-    bool, or a (steer, throttle) pair) marks the row as cut by a step budget: see RolloutStorage.finish_rollouts."""
+    bool, or a (steer, throttle) pair) marks the row as cut by a step budget: see RolloutStorage.finish_rollouts.
+    train_cfg["checkpoint_interval"] (absent / None / 0: off; single rank only): after every interval-th episode (its
+    learner section, log line and snapshot) the training state is captured (cadre_amd.checkpoint.capture: one launch on
+    the compute stream, no host sync) and written to <work_dir>/checkpoints/ckpt_<episode>.pt just before the next capture
+    or before the loop returns; the callback then gets "checkpoint" (episode, path).  train_cfg["resume_from"] (a path):
+    after agent, storages, scaler and environments are built, the checkpoint is restored and the loop continues at its
+    episode + 1 (schedules see that episode).  Environment state is not part of a checkpoint: the environments are the
+    caller's and restart through reset().  With both keys absent nothing of this runs."""
     if env_cls is None:
         from env_wrapper import EnvWrapper as env_cls        # needs the CARLA stack (reference env_wrapper.py)
     if logger is None:
@@ -575,13 +652,19 @@ def train_vec(rank, train_cfg, agent_cfg, env_cfg, rollout_cfg, num_envs, env_cl
         shared_grad_buffers = Shared_grad_buffers(agent.model_dict, device)
     rs = _reward_scaling(train_cfg, shared_grad_buffers)
     agent.reward_scaler = None if rs is None else ReturnScaler(num_envs, rollout_cfg.gamma, device=device, **rs)
+    ck_interval, ck_resume = _checkpointing(train_cfg, shared_grad_buffers)
+    ck, first_episode = None, 0
+    if ck_interval is not None or ck_resume is not None:
+        ck = _Checkpointer(envs[0].work_dir, ck_interval, agent, rollouts, callback)
+        if ck_resume is not None:                # (the environments are the caller's: they restart through reset())
+            first_episode = ck.resume(ck_resume)
     obs = [env.reset() for env in envs]
     dones = [False] * num_envs
     log_stats = bool(_get(train_cfg, "log_stats", False))
     state = lambda: dict(agent=agent, envs=envs, rollouts=rollouts, reward_scaler=agent.reward_scaler)
     if callback is not None:
         callback("start", **state())
-    for episode in range(train_cfg.max_episode):
+    for episode in range(first_episode, train_cfg.max_episode):
         for _ in range(num_steps):
             commands = [o["command"] for o in obs]
             outs = agent.act_batch(obs)
@@ -611,7 +694,11 @@ def train_vec(rank, train_cfg, agent_cfg, env_cfg, rollout_cfg, num_envs, env_cl
                 logger.log(stats_line(episode, stats))
         if episode % train_cfg.save_interval == 0 and rank == 0:
             agent.save_snapshot(os.path.join(model_dir, "ppo_model_{}.pt".format(episode)))
+        if ck is not None:                       # (after the snapshot: building its nn.Modules draws from the generator)
+            ck.after_episode(episode)
         if callback is not None:
             callback("update", episode=episode, losses=(vl, pl, el), **state())
+    if ck is not None:
+        ck.flush()
     print("process {} finished ({} environments).".format(rank, num_envs))
     return agent

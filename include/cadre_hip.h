@@ -684,6 +684,31 @@ int cadre_insert_rows_tl(const void* dst_table, const int32_t* slot, int32_t n_d
                          int32_t D, int32_t Hd, int32_t T, const float* feat, int64_t ldf, const int64_t* action,
                          const float* logp, const float* value, const float* rm, const int32_t* cmd, void* stream);
 
+/* ---------------------------------------------------------------- training checkpoints (csrc/checkpoint.hip)
+ * cadre_state_capture: ONE launch copies n_ranges device ranges into one staging buffer and forms one 64-bit digest per
+ * range from the same read (each source word is read once, each staging word written once; the digest costs no further
+ * memory traffic).  range_table: device array of n_ranges records {const void* src; int64_t dst_off; int64_t bytes}
+ * (24 bytes each); range k goes to (char*)staging + dst_off and its digest to digests[k].  bytes is a multiple of 4 (every
+ * piece of state is fp32, fp64, int32 or int64); src and staging + dst_off need 4-byte alignment only: 16-byte accesses
+ * are used where the alignment allows, with a word-wise head and tail.  staging == NULL: digests only (verification of
+ * an uploaded checkpoint).  The digest slots are zeroed on `stream` before the launch.
+ *
+ * Digest of the 32-bit words w_0 .. w_{n-1} of a range, all arithmetic mod 2^64, i a 64-bit index:
+ *     D = sum_i (uint64(w_i) + 1) * ((2 i + 1) * 0x9E3779B97F4A7C15)
+ * Wrap-around addition is associative and commutative: the partial sums of lanes, waves and workgroups give the same
+ * bits in any order, so equal bytes give equal digests in every launch.  The multiplier is odd (every single-bit flip
+ * changes D) and the + 1 makes the length count.  This is an INTEGRITY check against corruption and mix-ups, NOT a
+ * cryptographic hash: it is trivially forgeable.
+ *
+ * Status: the arguments the host can see are checked (0 <= n_ranges <= CADRE_CAPTURE_MAX_RANGES, non-NULL table and
+ * digests of 8-byte alignment, staging of 4-byte alignment) and refused with a negative status.  The table lives in
+ * device memory; a record the launch finds malformed (bytes negative or no multiple of 4, src or dst_off off a 4-byte
+ * boundary) is not copied and its digest slot is set to CADRE_CAPTURE_BAD_RANGE.  cadre_amd.hip.capture_table refuses
+ * such records on the host before a table is built. */
+#define CADRE_CAPTURE_MAX_RANGES 65535
+#define CADRE_CAPTURE_BAD_RANGE 0xFFFFFFFFFFFFFFFFull
+int cadre_state_capture(const void* range_table, int32_t n_ranges, void* staging, uint64_t* digests, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
