@@ -106,12 +106,14 @@ def chain_outputs(y64, mag, K, budget=DIRECT_BUDGET, seed=0):
     return np.unique(np.concatenate([top, rnd])).astype(np.int64)
 
 
-def c_bar_direct(groups, y64, mag, scale=None, shift=None, resid=None, act=0, slope=0.01, what="", budget=DIRECT_BUDGET):
+def c_bar_direct(groups, y64, mag, scale=None, shift=None, resid=None, act=0, slope=0.01, what="", budget=DIRECT_BUDGET, idx=None):
     """-> (c_bar, cap) of a direct case: the sequential fp32 chain of bf16_parity.c_bar_of on products rounded to fp32, over the outputs
-    chain_outputs names, asserted under DIRECT_CAP(K)."""
+    chain_outputs names, asserted under DIRECT_CAP(K).  idx: the flat outputs to sum in place of chain_outputs' choice
+    (tests/update_parity.py: every output whose magnitude is not zero — an empty sum has no unit to measure an error in)."""
     K = sum(g[1] for g in groups)
     cap = DIRECT_CAP(K)
-    return bp.c_bar_of(groups, y64, mag, scale, shift, resid, act, slope, what=what, cap=cap, idx=chain_outputs(y64, mag, K, budget)), cap
+    idx = chain_outputs(y64, mag, K, budget) if idx is None else idx
+    return bp.c_bar_of(groups, y64, mag, scale, shift, resid, act, slope, what=what, cap=cap, idx=idx), cap
 
 
 def check32(got, y64, mag, c_bar, cap, what=""):
