@@ -10,6 +10,7 @@
 #include <algorithm>
 #include "../../include/cadre_hip.h"
 #include "ordinal.h"
+#include "kl_rule.h"
 #ifdef CADRE_AB_KERNELS
 #include "../../include/cadre_hip_ab.h"
 #endif
@@ -1668,22 +1669,10 @@ __device__ __forceinline__ void ppo_loss_body(const float* logits, int64_t ldl, 
           o[5] = t[5];
           kl[h] = t[0] * inv_b;
         }
-        int32_t stopped = so.stop ? __hip_atomic_load(so.stop, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0;
-        if (so.stop && so.target_kl > 0.f && fmaxf(kl[0], kl[1]) > 1.5f * so.target_kl) stopped = 1;
-        if (so.stop) __hip_atomic_store(so.stop, stopped, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        so.row[6] = stopped ? 0.f : 1.f;            // applied: the optimiser step of this minibatch runs
-        so.row[so.F + 6] = so.row[6];
-        if constexpr (HP) {
-          // KL-adaptive lr (the rsl_rl / RL-Games rule), all in double; the optimiser step of THIS minibatch reads the result
-          const double desired = hp[CADRE_HP_DESIRED_KL];
-          if (desired > 0.0 && !stopped) {
-            const double k = fmax((double)kl[0], (double)kl[1]);
-            double lr = hp[CADRE_HP_LR];
-            if (k > 2.0 * desired) lr = fmax(hp[CADRE_HP_LR_MIN], lr / hp[CADRE_HP_LR_FACTOR]);
-            else if (k > 0.0 && k < desired / 2.0) lr = fmin(hp[CADRE_HP_LR_MAX], lr * hp[CADRE_HP_LR_FACTOR]);
-            hp[CADRE_HP_LR] = lr;
-          }
-        }
+        // the gate, `applied` and (HP) the KL-adaptive lr: the rule of kl_rule.h, which cadre_kl_consensus applies to the
+        // KL summed over the ranks
+        if constexpr (HP) cadre_kl_rule(kl[0], kl[1], so.target_kl, so.stop, so.row, so.F, hp[CADRE_HP_DESIRED_KL], hp);
+        else cadre_kl_rule(kl[0], kl[1], so.target_kl, so.stop, so.row, so.F, 0.0, nullptr);
       }
       // the counter goes back to zero for the next launch on this scratch (stream-ordered): no clearing launch per step
       __hip_atomic_store(reinterpret_cast<unsigned*>(scratch), 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);

@@ -137,6 +137,10 @@ SYMBOLS = {
     "cadre_categorical_dist_ord": [vp, i64, i32, i32, vp, vp, vp, vp, vp],
     # training checkpoints: range table, n_ranges, staging (NULL: digests only), digests, stream
     "cadre_state_capture": [vp, i32, vp, vp, vp],
+    # rank consensus: reduced kl pair, target_kl, stop, desired_kl, hp, stats row, F, stream / per-rank statistics, world,
+    # epsilon, state, merged (may be NULL), stream
+    "cadre_kl_consensus": [vp, f32, vp, f64, vp, vp, i32, vp],
+    "cadre_return_scale_merge": [vp, i32, f64, vp, vp, vp],
 }
 # entry points of the A/B build only (include/cadre_hip_ab.h; CADRE_BUILD_AB=1 python -m cadre_amd.build, then
 # CADRE_HIP_LIB=.../libcadre_hip_ab.so): bound when the loaded library has them

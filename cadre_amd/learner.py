@@ -96,6 +96,14 @@ class PPOLearnerHIP:
         self.target_kl = None
         self._stop = None          # device int32: the gate's sticky flag for the current round
         self._norm_row = None      # stats row that receives the next optimiser step's per-model gradient norms
+        # rank consensus (opt-in, several ranks): the gate and the adaptive lr are decided by cadre_kl_consensus from the KL
+        # summed over the ranks (kl_consensus, between the gradient exchange and the optimiser step), not by the loss kernel
+        self.consensus = False
+        self._cons_modes = False   # asked for by set_update_modes (the section's gate / diagnostics)
+        self._cons_adaptive = False  # asked for by set_adaptive_lr (stays on between sections)
+        self._kl_buf = None        # device float32 [4]: approx_kl steer, throttle of the step (two spare slots), reduced in place
+        self._kl_sink = None       # device float32 [2] that receives the next step's reduced pair (the section's table)
+        self._last_stats = None    # the workspace stats row of the update that ran last
         hip.lib()
 
     # ------------------------------------------------------------------ diagnostics / KL gate
@@ -103,9 +111,14 @@ class PPOLearnerHIP:
         """F of a stats row [2 heads][F]: hip.PPO_STATS_FIELDS loss diagnostics, then the head's 2 C gradient norms."""
         return hip.PPO_STATS_FIELDS + 2 * self.a.C
 
-    def set_update_modes(self, stats=False, target_kl=None):
+    def set_update_modes(self, stats=False, target_kl=None, consensus=False):
         """stats: the update writes its diagnostics (update(..., stats_row=)); target_kl (> 0): arm the KL gate and clear
-        its flag — the round starts with the optimiser enabled.  set_update_modes() returns to the plain update."""
+        its flag — the round starts with the optimiser enabled.  set_update_modes() returns to the plain update.
+        consensus (several ranks): the loss launch only reports the KL (it gets target_kl = 0 and reads the flag); the gate is
+        decided by kl_consensus() from the KL summed over the ranks, which chief_step runs before the optimiser step."""
+        if consensus and self._adaptive is not None and not self._cons_adaptive:
+            raise hip.CadreHipError("rank consensus: the adaptive lr of this learner was armed without it "
+                                    "(set_adaptive_lr(..., consensus=True)); one step cannot mix the two forms")
         if target_kl is not None:
             target_kl = float(target_kl)
             if not target_kl > 0.0:
@@ -117,6 +130,38 @@ class PPOLearnerHIP:
         self.stats = bool(stats)
         self.target_kl = target_kl
         self._norm_row = None
+        self._kl_sink = None
+        self._cons_modes = bool(consensus)
+        self.consensus = self._cons_modes or self._cons_adaptive
+
+    def _loss_tkl(self):
+        """target_kl of the loss launch: 0 (no check in the kernel) without a gate, and in consensus mode."""
+        return 0.0 if (self.target_kl is None or self.consensus) else self.target_kl
+
+    def kl_consensus(self, all_reduce_small):
+        """Consensus mode, once per optimiser step, after the update and before clip_adam: the step's approx_kl pair (this
+        rank's workspace stats row) -> `all_reduce_small` (SUM over the ranks, Shared_grad_buffers.all_reduce_small) ->
+        cadre_kl_consensus on the sum: the stop flag, `applied` of the pending stats row and the adaptive lr, identically
+        on every rank.  The collective is issued unconditionally: nothing here depends on a device value."""
+        if not self.consensus:
+            raise hip.CadreHipError("kl_consensus needs the consensus mode (set_update_modes / set_adaptive_lr with consensus=True)")
+        if self._last_stats is None:
+            raise hip.CadreHipError("kl_consensus: no update has run in a stats mode yet")
+        if self._kl_buf is None:
+            self._kl_buf = torch.zeros(4, device=self.a.device)
+        buf = self._kl_buf
+        buf[:2].copy_(self._last_stats[:, 0])
+        all_reduce_small(buf)
+        sink, self._kl_sink = self._kl_sink, None
+        if sink is not None:
+            sink.copy_(buf[:2])
+        row = self._norm_row
+        ad = self._adaptive if self._cons_adaptive else None
+        hip.check(hip.lib().cadre_kl_consensus(hip.ptr(buf), 0.0 if self.target_kl is None else self.target_kl,
+                                               hip.ptr(self._stop) if self.target_kl is not None else None,
+                                               0.0 if ad is None else ad[0], hip.ptr(self._hp) if ad is not None else None,
+                                               hip.ptr(row), 0 if row is None else row.shape[-1], hip.stream()),
+                  "cadre_kl_consensus")
 
     def _loss_stats(self):
         return self.stats or self.target_kl is not None or self._adaptive is not None
@@ -124,10 +169,12 @@ class PPOLearnerHIP:
     def _mode_key(self):
         """hipGraph key suffix of the update modes: () when all are off (today's graphs).  Device-hyper mode is a mode
         (("hp",)); the VALUES in the block are not part of any key.  Ordinal policy heads are a mode (("ord",)): the loss
-        launch is then cadre_ppo_loss_ord."""
+        launch is then cadre_ppo_loss_ord.  Rank consensus is a mode (("consensus",)): the loss launch then decides nothing, so
+        the graphs of the two forms never mix."""
         key = (("stats", self.target_kl),) if self._loss_stats() else ()
         key = key + ((("hp",),) if self._hp_on else ())
-        return key + ((("ord",),) if getattr(self.a, "ord", None) is not None else ())
+        key = key + ((("ord",),) if getattr(self.a, "ord", None) is not None else ())
+        return key + ((("consensus",),) if self.consensus else ())
 
     # ------------------------------------------------------------------ device-resident hyper-parameters
     def _drop_update_graphs(self, hp=False):
@@ -234,15 +281,20 @@ class PPOLearnerHIP:
             #  inside the span only when it is itself being set)
             self._hp_upload(min(idx), max(idx) + 1)
 
-    def set_adaptive_lr(self, desired_kl, factor=1.5, lr_min=1e-5, lr_max=1e-2, lr=None):
+    def set_adaptive_lr(self, desired_kl, factor=1.5, lr_min=1e-5, lr_max=1e-2, lr=None, consensus=False):
         """KL-adaptive learning rate, on the device (switches to device-hyper mode and implies the stats loss kernel): after
         a minibatch's loss and before its optimiser step, with kl = max(approx_kl steer, approx_kl throttle) of that
         minibatch,  kl > 2 desired_kl: lr = max(lr_min, lr / factor);  0 < kl < desired_kl / 2: lr = min(lr_max, lr * factor)
         (float64; the rsl_rl / RL-Games rule).  The target_kl gate is checked first: once it has fired, lr stays.  `lr`: the
         starting value (None: the block's current one — the adapted value carries over).  While the controller is on,
         clip_adam's `lr` argument is ignored.  set_adaptive_lr(None) switches it off; the next clip_adam(lr=) then sets lr.
-        Refused with several ranks (each rank would move its own lr) and by the sharded optimiser step."""
+        Refused with several ranks (each rank would move its own lr) and by the sharded optimiser step.
+        consensus (several ranks, not refused): the block's desired_kl field stays 0, so the loss kernel does not adapt; the
+        desired KL is kept on the host and handed by value to cadre_kl_consensus, which applies the same rule to the KL
+        summed over the ranks (kl_consensus, run by chief_step before the optimiser step)."""
         if desired_kl is None:
+            self._cons_adaptive = False
+            self.consensus = self._cons_modes
             if self._adaptive is not None:
                 self._adaptive = None
                 self._hp_host[hip.HP["desired_kl"]] = 0.0
@@ -259,7 +311,7 @@ class PPOLearnerHIP:
         if lr is not None and not (float(lr) > 0.0 and np.isfinite(float(lr))):
             raise ValueError("adaptive lr: lr must be > 0 (got %r)" % (lr,))
         import torch.distributed as dist
-        if dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1:
+        if not consensus and dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1:
             raise hip.CadreHipError("adaptive lr needs a single rank (world size %d): the controller is per rank and every "
                                     "rank would move its own lr" % dist.get_world_size())
         if getattr(self.a, "_shard", None) is not None:
@@ -270,9 +322,11 @@ class PPOLearnerHIP:
         if lr is not None:                         # (None: whatever the block holds carries over)
             m[hip.HP["lr"]] = float(lr)
             lo = 0
-        m[hip.HP["desired_kl"]], m[hip.HP["lr_factor"]] = desired_kl, factor
+        m[hip.HP["desired_kl"]], m[hip.HP["lr_factor"]] = (0.0 if consensus else desired_kl), factor
         m[hip.HP["lr_min"]], m[hip.HP["lr_max"]] = lr_min, lr_max
         self._adaptive = (desired_kl, factor, lr_min, lr_max)
+        self._cons_adaptive = bool(consensus)
+        self.consensus = self._cons_modes or self._cons_adaptive
         self._hp_upload(lo, hip.HP["lr_factor"] + 1)
 
     def _sync_hyper(self, lr, max_grad_norm):
@@ -460,6 +514,7 @@ class PPOLearnerHIP:
 
     def _stats_out(self, B, stats_row):
         w = self.workspace(B)
+        self._last_stats = w.get("stats")
         if stats_row is not None:
             stats_row.copy_(w["stats"])
             self._norm_row = stats_row
@@ -542,7 +597,7 @@ class PPOLearnerHIP:
             # one entry point for the four modes: hp NULL = by-value scalars, stats row NULL = no diagnostics
             stats = self._loss_stats()
             srow, sscr = self._stats_ws(w, B) if stats else (None, None)
-            tkl = 0.0 if self.target_kl is None else self.target_kl
+            tkl = self._loss_tkl()
             hip.check(L.cadre_ppo_loss_ord(hip.ptr(O3), NP, 2 * B * NP, hip.ptr(O3[1]), NP, 2 * B * NP,
                                            hip.ptr(w["actions"]), hip.ptr(w["commands"]), hip.ptr(w["old_values"]),
                                            hip.ptr(w["returns"]), hip.ptr(w["old_logp"]), hip.ptr(w["adv"]), B, C,
@@ -562,7 +617,7 @@ class PPOLearnerHIP:
                          hip.ptr(w["sync"][Z * S:]))
             if self._loss_stats():
                 srow, sscr = self._stats_ws(w, B)
-                tkl = 0.0 if self.target_kl is None else self.target_kl
+                tkl = self._loss_tkl()
                 hip.check(L.cadre_ppo_loss_stats_hp(*loss_args, hip.ptr(srow), srow.shape[1], hip.ptr(sscr), tkl,
                                                     hip.ptr(self._stop) if self.target_kl is not None else None, st),
                           "cadre_ppo_loss_stats_hp")
@@ -570,7 +625,7 @@ class PPOLearnerHIP:
                 hip.check(L.cadre_ppo_loss_hp(*loss_args, st), "cadre_ppo_loss_hp")
         elif front and self._loss_stats():
             srow, sscr = self._stats_ws(w, B)
-            tkl = 0.0 if self.target_kl is None else self.target_kl
+            tkl = self._loss_tkl()
             hip.check(L.cadre_ppo_loss_stats(hip.ptr(O3), NP, 2 * B * NP, hip.ptr(O3[1]), NP, 2 * B * NP,
                                              hip.ptr(w["actions"]), hip.ptr(w["commands"]), hip.ptr(w["old_values"]),
                                              hip.ptr(w["returns"]), hip.ptr(w["old_logp"]), hip.ptr(w["adv"]), B, C,
@@ -731,6 +786,9 @@ class PPOLearnerHIP:
         `all_reduce_norms(norms2[:n_models])` (SUM of 16 doubles over the ranks) -> clip + Adam on the shard.
         The Adam moments exist for the shard only (1/N of the state and of the pass's HBM traffic)."""
         a = self.a
+        if self.consensus:
+            raise hip.CadreHipError("rank consensus is not available for the sharded optimiser step: it has no gated form "
+                                    "(use the all-reduce exchange)")
         if self.target_kl is not None:
             raise hip.CadreHipError("target_kl: the KL gate is not available for the sharded optimiser step (several ranks)")
         if self._adaptive is not None:

@@ -6,6 +6,7 @@ import time
 
 import torch
 
+from .. import hip
 from ..learner import PPOLearnerHIP
 
 
@@ -28,7 +29,9 @@ def chief_step(shared_grad_buffers, optimizer, max_grad_norm, lr=None, zero_grad
     autograd path and foreign arenas ACCUMULATE into `p.grad` / the arena and need the fill).
     With the learner in device-hyper mode (PPOLearnerHIP.set_device_hyper) `lr` and `max_grad_norm` are values in device
     memory, not graph keys: an optimizer whose lr a torch scheduler moves costs one small copy per change and the
-    captured step is replayed.  While the KL-adaptive learning rate is on, the lr read here is ignored."""
+    captured step is replayed.  While the KL-adaptive learning rate is on, the lr read here is ignored.
+    With the learner in consensus mode (train_cfg["rank_consensus"], all-reduce exchange only) the KL gate and the adaptive lr
+    are decided between the gradient exchange and the optimiser step from the KL summed over the ranks."""
     arena = shared_grad_buffers.arena
     if optimizer is not None:
         lr, betas, eps = _hyper(optimizer)
@@ -38,6 +41,10 @@ def chief_step(shared_grad_buffers, optimizer, max_grad_norm, lr=None, zero_grad
     if step is None:
         arena._learner = step = PPOLearnerHIP(arena)
     if shared_grad_buffers.exchange_mode() == "sharded":
+        if step.consensus:      # (decided from configuration, alike on every rank, before any collective of this step)
+            raise hip.CadreHipError("train_cfg.rank_consensus is not available with the sharded gradient exchange "
+                                    "(CADRE_GRAD_EXCHANGE=sharded): the sharded optimiser step has no gated form; use the "
+                                    "all-reduce exchange")
         # (nothing handed in since the last exchange: no collective, but still the SHARDED optimiser — the arena's Adam
         #  moments exist for this rank's shard only; every rank's gradients are then its own, as in the replicated form)
         rng = shared_grad_buffers.reduce_scatter() or shared_grad_buffers.shard()
@@ -46,6 +53,11 @@ def chief_step(shared_grad_buffers, optimizer, max_grad_norm, lr=None, zero_grad
         shared_grad_buffers.all_gather_params()
     else:
         shared_grad_buffers.all_reduce()
+        if step.consensus:
+            # rank consensus: ONE more small collective per optimiser step — the step's two approx_kl values summed over the
+            # ranks — then cadre_kl_consensus decides gate, `applied` and lr from the sum, identically on every rank; the
+            # gated clip + Adam graph below reads what it decided
+            step.kl_consensus(shared_grad_buffers.all_reduce_small)
         step.clip_adam(lr=lr, max_grad_norm=max_grad_norm, betas=betas, eps=eps)
     shared_grad_buffers.reset(zero=zero_grads)
 

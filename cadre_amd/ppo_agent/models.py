@@ -515,6 +515,22 @@ class Shared_grad_buffers(object):
         import torch.distributed as dist
         dist.all_reduce(norms2, op=dist.ReduceOp.SUM)
 
+    def all_reduce_small(self, t):
+        """Rank consensus (train_cfg["rank_consensus"]): one all-reduce(SUM) of a small contiguous tensor (device or CPU),
+        in place; a no-op when no exchange runs (dist_world() == 0).  Every rank must call it at the same point of every
+        step, unconditionally: never depending on a device value, never from an exception path (see native_scatter_gather) —
+        a rank that skipped it would leave its peers waiting.  Every rank receives the same reduced bits (the property the
+        gradient arena's exchange already rests on), so a kernel that decides from them decides alike on every rank.
+        A gather is the same call: each rank fills its own row of a zeroed [world][n] buffer (x + 0 is exact, and gloo has
+        no all-gather on device tensors)."""
+        import torch.distributed as dist
+        if not self.dist_world():
+            return t
+        if not t.is_contiguous():
+            raise hip.CadreHipError("all_reduce_small needs a contiguous tensor (got strides %r)" % (t.stride(),))
+        dist.all_reduce(t, op=dist.ReduceOp.SUM)
+        return t
+
     def all_gather_params(self):
         """Sharded exchange, step 3: every rank's updated parameter shard to every rank."""
         import torch.distributed as dist

@@ -183,7 +183,7 @@ class RolloutStorage(object):
         return self.advantages
 
     @staticmethod
-    def finish_rollouts(storages, next_values, normalise=True, reward_scaler=None, explained_variance=None):
+    def finish_rollouts(storages, next_values, normalise=True, reward_scaler=None, explained_variance=None, consensus=None):
         """compute_returns of every storage of a learner section in ONE launch (cadre_gae_multi): storages = the flat list
         [steer_0, throttle_0, steer_1, ...] (storage k belongs to head k & 1), next_values = one bootstrap value each.
         Returns the list of `advantages` tensors.  Without time-limit flags and without a scaler, returns, advantages and
@@ -194,7 +194,13 @@ class RolloutStorage(object):
         `reward_scaler` (a ReturnScaler): one cadre_return_stats launch first updates the running statistics of the
         discounted returns (when scaler.training) and the scale of each head; the scan then reads every reward as
         clamp(r * scale_head, -clip, clip).  `storage.rewards` keeps the raw rewards.
-        `explained_variance` (device float64 [len(storages)]): filled by RolloutStorage.explained_variance afterwards."""
+        `explained_variance` (device float64 [len(storages)]): filled by RolloutStorage.explained_variance afterwards.
+        `consensus` (a Shared_grad_buffers, with a `reward_scaler`; several ranks): after cadre_return_stats has grown THIS
+        rank's statistics, every rank puts its six numbers (count, mean, M2 per head) into its own row of a zeroed
+        [world][6] float64 buffer, the buffer is summed over the ranks (consensus.all_reduce_small: a gather, x + 0 is
+        exact) and cadre_return_scale_merge forms the scale of each head from the ranks' statistics merged in rank order —
+        the same two scales on every rank.  The rank's own statistics and carries stay its own.  Every rank must pass it
+        at the same rollouts (the collective is issued whenever the scaler is training); a no-op without an exchange."""
         import numpy as np
         n = len(storages)
         if n < 1 or len(next_values) != n:
@@ -232,6 +238,17 @@ class RolloutStorage(object):
             hip.check(L.cadre_return_stats(hip.ptr(table), n, T, float(reward_scaler.gamma), float(reward_scaler.epsilon),
                                            1 if reward_scaler.training else 0, hip.ptr(state),
                                            hip.ptr(reward_scaler._scratch), hip.stream()), "cadre_return_stats")
+            if consensus is not None and reward_scaler.training and consensus.dist_world():
+                import torch.distributed as dist
+                world, rank = dist.get_world_size(), dist.get_rank()
+                buf = reward_scaler._rank_stats
+                if buf is None or buf.shape[0] != world or buf.device != state.device:
+                    buf = reward_scaler._rank_stats = torch.zeros(world, 6, dtype=torch.float64, device=state.device)
+                buf.zero_()
+                buf[rank].copy_(state[:6])
+                consensus.all_reduce_small(buf)
+                hip.check(L.cadre_return_scale_merge(hip.ptr(buf), world, float(reward_scaler.epsilon), hip.ptr(state), None,
+                                                     hip.stream()), "cadre_return_scale_merge")
         g32 = float(np.float32(s0.gamma))
         gt32 = float(np.float32(s0.gamma * s0.tau))              # double product, then one rounding (storage.py:75)
         hip.check(L.cadre_gae_multi(hip.ptr(table), n, T, g32, gt32, 1 if normalise else 0, hip.ptr(state),
@@ -319,6 +336,7 @@ class ReturnScaler(object):
         self.state = torch.zeros(hip.RS_CARRY + 4 * n_envs, dtype=torch.float64, device=device)
         self.state[hip.RS_SCALE:hip.RS_CARRY] = 1.0
         self._scratch = torch.zeros(1 + 4 * n_envs, dtype=torch.float64, device=device)
+        self._rank_stats = None    # rank consensus: the [world][6] gather buffer of finish_rollouts(consensus=)
 
     def to(self, device):
         self.state = self.state.to(device)

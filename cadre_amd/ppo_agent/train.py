@@ -36,16 +36,49 @@ def _default_logger():
 STAT_FIELDS = ("approx_kl", "old_approx_kl", "clip_fraction", "value_clip_fraction", "ratio_mean", "max_abs_log_ratio")
 
 
+def _rank_consensus(train_cfg, shared_grad_buffers=None, in_process_chief=True):
+    """train_cfg["rank_consensus"] (absent / None / False: off; True).  With it the KL early stop, the KL-adaptive lr and
+    reward scaling are allowed with several ranks: the few numbers the ranks must agree on (the step's two approx_kl values,
+    the per-rank return statistics) are SUMMED over the ranks by one small collective per optimiser step (per rollout for
+    the statistics) and the decision is taken from the sum by a kernel that runs identically on every rank — R ranks with N
+    workers each decide what one rank with R N workers decides.  Needs the in-process chief and the all-reduce exchange.
+    Returns whether the key is set; the consensus path itself runs only where an exchange runs (_consensus_on)."""
+    on = _get(train_cfg, "rank_consensus", False)
+    if on is None:
+        on = False
+    if not isinstance(on, (bool, np.bool_)):
+        raise ValueError("train_cfg.rank_consensus: expected None, False or True (got %r)" % (on,))
+    if not on:
+        return False
+    if not in_process_chief:
+        raise hip.CadreHipError("train_cfg.rank_consensus needs the in-process chief (the decision is taken on this process's "
+                                "device, between the gradient exchange and the optimiser step)")
+    mode = getattr(shared_grad_buffers, "exchange_mode", None)
+    if mode is not None and shared_grad_buffers.dist_world() and mode() == "sharded":
+        raise hip.CadreHipError("train_cfg.rank_consensus is not available with the sharded gradient exchange "
+                                "(CADRE_GRAD_EXCHANGE=sharded): the sharded optimiser step has no gated form")
+    return True
+
+
+def _consensus_on(train_cfg, shared_grad_buffers, in_process_chief=True):
+    """Whether the consensus path runs: the key is set AND a gradient exchange runs (dist_world() >= 1; world 1 is the forced
+    form, CADRE_BENCH_FORCE_DIST=1).  Without an exchange the key changes nothing: the loss kernel decides as always."""
+    return bool(_rank_consensus(train_cfg, shared_grad_buffers, in_process_chief) and shared_grad_buffers is not None
+                and shared_grad_buffers.dist_world() >= 1)
+
+
 def _target_kl(train_cfg, shared_grad_buffers, in_process_chief=True):
     """train_cfg["target_kl"] (absent / None: no gate).  The gate is a device flag of THIS rank: ranks would disagree on it,
-    so it is refused with several ranks; a chief in another process does not see it either."""
+    so it is refused with several ranks unless train_cfg["rank_consensus"] is set; a chief in another process does not see
+    it either."""
     tkl = _get(train_cfg, "target_kl")
     if tkl is None:
         return None
     tkl = float(tkl)
     if not tkl > 0.0:
         raise ValueError("train_cfg.target_kl must be > 0 (got %r)" % (tkl,))
-    if shared_grad_buffers is not None and shared_grad_buffers.dist_world() > 1:
+    cons = _rank_consensus(train_cfg, shared_grad_buffers, in_process_chief)
+    if not cons and shared_grad_buffers is not None and shared_grad_buffers.dist_world() > 1:
         raise hip.CadreHipError("train_cfg.target_kl needs a single rank (world size %d): the KL gate is per rank and ranks "
                                 "would disagree on it; the diagnostics (log_stats) work at any world size"
                                 % shared_grad_buffers.dist_world())
@@ -55,11 +88,21 @@ def _target_kl(train_cfg, shared_grad_buffers, in_process_chief=True):
 
 
 # ----------------------------------------------------------------------------- reward scaling, time limits
-def _check_scaler(reward_scaler, shared_grad_buffers):
-    """A ReturnScaler grows the statistics of THIS rank's environments: like target_kl it is refused with several ranks."""
-    if reward_scaler is not None and shared_grad_buffers is not None and shared_grad_buffers.dist_world() > 1:
+def _check_scaler(reward_scaler, shared_grad_buffers, train_cfg=None):
+    """A ReturnScaler grows the statistics of THIS rank's environments: like target_kl it is refused with several ranks
+    unless train_cfg["rank_consensus"] is set (the scale then comes from the statistics of all ranks, merged)."""
+    if reward_scaler is None:
+        return
+    cons = train_cfg is not None and _rank_consensus(train_cfg, shared_grad_buffers)
+    if not cons and shared_grad_buffers is not None and shared_grad_buffers.dist_world() > 1:
         raise hip.CadreHipError("reward scaling needs a single rank (world size %d): each rank would grow its own return "
                                 "statistics and scale its rewards differently" % shared_grad_buffers.dist_world())
+
+
+def _scaler_consensus(cons, reward_scaler, shared_grad_buffers):
+    """The `consensus=` argument of finish_rollouts, only where the consensus path runs with a scaler (every other call is
+    exactly the call it was)."""
+    return dict(consensus=shared_grad_buffers) if (cons and reward_scaler is not None) else {}
 
 
 def _reward_scaling(train_cfg, shared_grad_buffers=None):
@@ -81,7 +124,8 @@ def _reward_scaling(train_cfg, shared_grad_buffers=None):
         raise ValueError("train_cfg.reward_scaling: clip / epsilon of %r are not numbers" % (cfg,))
     if not 0.0 < kw["clip"] < float("inf") or not 0.0 <= kw["epsilon"] < float("inf"):
         raise ValueError("train_cfg.reward_scaling: need a finite clip > 0 and a finite epsilon >= 0 (got %r)" % (cfg,))
-    if shared_grad_buffers is not None and shared_grad_buffers.dist_world() > 1:
+    cons = _rank_consensus(train_cfg, shared_grad_buffers)
+    if not cons and shared_grad_buffers is not None and shared_grad_buffers.dist_world() > 1:
         raise hip.CadreHipError("train_cfg.reward_scaling needs a single rank (world size %d): each rank would grow its "
                                 "own return statistics" % shared_grad_buffers.dist_world())
     return kw
@@ -207,7 +251,8 @@ def _schedules(train_cfg):
 def _adaptive_lr(train_cfg, shared_grad_buffers, in_process_chief=True):
     """train_cfg["adaptive_lr"] = {"desired_kl", "factor", "min", "max"} (absent / None: nothing) as the keyword arguments of
     PPOLearnerHIP.set_adaptive_lr.  The controller is a device value of THIS rank: like target_kl it is refused with
-    several ranks and with a chief in another process; it excludes a schedule for lr."""
+    several ranks (unless train_cfg["rank_consensus"] is set) and with a chief in another process; it excludes a schedule
+    for lr."""
     cfg = _get(train_cfg, "adaptive_lr")
     if cfg is None:
         return None
@@ -221,7 +266,8 @@ def _adaptive_lr(train_cfg, shared_grad_buffers, in_process_chief=True):
               lr_max=float(cfg.get("max", 1e-2)))
     if not kw["desired_kl"] > 0.0 or not kw["factor"] > 1.0 or not 0.0 < kw["lr_min"] <= kw["lr_max"]:
         raise ValueError("train_cfg.adaptive_lr: need desired_kl > 0, factor > 1, 0 < min <= max (got %r)" % (cfg,))
-    if shared_grad_buffers is not None and shared_grad_buffers.dist_world() > 1:
+    cons = _rank_consensus(train_cfg, shared_grad_buffers, in_process_chief)
+    if not cons and shared_grad_buffers is not None and shared_grad_buffers.dist_world() > 1:
         raise hip.CadreHipError("train_cfg.adaptive_lr needs a single rank (world size %d): the controller is per rank and "
                                 "every rank would move its own lr" % shared_grad_buffers.dist_world())
     if not in_process_chief:
@@ -252,9 +298,10 @@ def _section_hyper(agent, train_cfg, shared_grad_buffers, in_process_chief, opti
         if optimizer is not None:
             lr = optimizer.param_groups[0]["lr"]
         want = (alr["desired_kl"], alr["factor"], alr["lr_min"], alr["lr_max"])
-        if agent.learner._adaptive != want:
+        cons = _consensus_on(train_cfg, shared_grad_buffers, in_process_chief)
+        if agent.learner._adaptive != want or agent.learner._cons_adaptive != cons:
             first = agent.learner._adaptive is None
-            agent.learner.set_adaptive_lr(lr=(3e-4 if lr is None else float(lr)) if first else None, **alr)
+            agent.learner.set_adaptive_lr(lr=(3e-4 if lr is None else float(lr)) if first else None, consensus=cons, **alr)
     elif "lr" in _schedules(train_cfg):
         if optimizer is not None:
             raise ValueError("train_cfg.schedules[\"lr\"] with an optimizer: the optimizer's lr would override the schedule")
@@ -268,8 +315,11 @@ class _SectionStats:
     """Device side of a section's diagnostics: one stats row per minibatch step, the explained variance of every storage,
     and the host-side dict filled after the section's single sync."""
 
-    def __init__(self, agent, n_steps, n_storages):
+    def __init__(self, agent, n_steps, n_storages, consensus_world=0):
         lrn = agent.learner
+        # rank consensus: the reduced (steer, throttle) approx_kl pair of every step, as cadre_kl_consensus read it
+        self.world = consensus_world
+        self.gkl = torch.zeros(n_steps, 2, device=agent.arena.device) if consensus_world else None
         self.agent, self.F = agent, lrn.stats_fields()
         dev = agent.arena.device
         self.rows = torch.zeros(n_steps, 2, self.F, device=dev)
@@ -279,16 +329,21 @@ class _SectionStats:
 
     def next_row(self):
         r = self.rows[self.i]
+        if self.gkl is not None:
+            self.agent.learner._kl_sink = self.gkl[self.i]
         self.i += 1
         return r
 
     def finish(self, stats, gated, losses=None):
         """One device->host copy of (losses,) rows and explained variances; the host step count follows the device's."""
         parts = ([losses.double().reshape(-1)] if losses is not None else []) + [self.rows.double().reshape(-1), self.ev]
+        if self.gkl is not None:
+            parts.append(self.gkl.double().reshape(-1))
         host = torch.cat(parts).cpu()
         nl = 0 if losses is None else losses.numel()
         tab = host[nl:nl + self.rows.numel()].view(self.rows.shape)
-        ev = host[nl + self.rows.numel():].view(-1, 2)
+        ev = host[nl + self.rows.numel():nl + self.rows.numel() + self.ev.numel()].view(-1, 2)
+        gkl = None if self.gkl is None else host[host.numel() - self.gkl.numel():].view(-1, 2).tolist()
         applied = [bool(r[0, 6] != 0) for r in tab]
         n_applied = sum(applied)
         a, lrn = self.agent.arena, self.agent.learner
@@ -300,9 +355,11 @@ class _SectionStats:
         if stats is not None:
             C, names = a.C, a.model_names()
             rows = []
-            for r in tab.tolist():
+            for i, r in enumerate(tab.tolist()):
                 d = {f: (r[0][k], r[1][k]) for k, f in enumerate(STAT_FIELDS)}
                 d["applied"] = r[0][6] != 0
+                if gkl is not None:                # (the SUM over the ranks: what the gate and the lr rule compared)
+                    d["global_approx_kl"] = tuple(gkl[i])
                 if lrn.device_hyper:               # (the lr the step's optimiser used; 0 where the row never got a step)
                     d["lr"] = r[0][hip.PPO_STATS_LR]
                 # model m = kind * 2C + head * C + c (arena segment order) -> row[head][FIELDS + kind * C + c]
@@ -313,6 +370,8 @@ class _SectionStats:
             stats.update(rows=rows, model_names=names, explained_variance=[tuple(e) for e in ev.tolist()],
                          updates_applied=n_applied, steps=len(applied),
                          stopped_at_step=None if n_applied == len(applied) else applied.index(False))
+            if gkl is not None:
+                stats["consensus_world"] = self.world
         return None if losses is None else host[:nl].view(losses.shape)
 
 
@@ -357,7 +416,10 @@ def learner_section(agent, steer_rollout, throttle_rollout, done, train_cfg, sha
     value_clip_fraction, ratio_mean, max_abs_log_ratio as (steer, throttle) pairs, "applied", and "grad_norm", the
     pre-clip norm of every model in "model_names" order), "explained_variance" [(steer, throttle)], "updates_applied",
     "steps" and "stopped_at_step" (None unless the KL gate fired).
-    train_cfg["target_kl"] (optional, single rank only): KL early stop.  When the approx KL of a minibatch exceeds
+    train_cfg["rank_consensus"] (optional, True): with several ranks, target_kl, adaptive_lr and reward scaling are decided
+    from numbers SUMMED over the ranks (one extra small collective per optimiser step; see _rank_consensus); each stats row
+    then carries "global_approx_kl" and `stats` "consensus_world".  Without a process group the key changes nothing.
+    train_cfg["target_kl"] (optional, single rank unless rank_consensus): KL early stop.  When the approx KL of a minibatch exceeds
     1.5 * target_kl in either head, the optimiser step of that minibatch and of every later one of this section is skipped
     on the device (the Stable-Baselines3 rule).  The sampler still draws every epoch's permutations, so the global CPU
     generator — and every later act() sample — does not depend on the KL outcome; forward and backward still run for
@@ -366,18 +428,20 @@ def learner_section(agent, steer_rollout, throttle_rollout, done, train_cfg, sha
     `reward_scaler` (a ReturnScaler for one environment, single rank only): return-based reward scaling.  With it, or when
     a storage holds time-limit flags, the two storages are finished by RolloutStorage.finish_rollouts (see there);
     otherwise by today's two compute_returns calls."""
-    _check_scaler(reward_scaler, shared_grad_buffers)
+    _check_scaler(reward_scaler, shared_grad_buffers, train_cfg)
     tkl = _target_kl(train_cfg, shared_grad_buffers, in_process_chief)
+    cons = _consensus_on(train_cfg, shared_grad_buffers, in_process_chief)
     lr = _section_hyper(agent, train_cfg, shared_grad_buffers, in_process_chief, optimizer)
     use_adv_norm = train_cfg["use_adv_norm"]
     sec = None
     if stats is not None or tkl is not None:
-        sec = _SectionStats(agent, train_cfg["ppo_epoch"] * _steps_per_epoch(steer_rollout), 2)
-        agent.learner.set_update_modes(stats=True, target_kl=tkl)
+        sec = _SectionStats(agent, train_cfg["ppo_epoch"] * _steps_per_epoch(steer_rollout), 2,
+                            consensus_world=shared_grad_buffers.dist_world() if cons else 0)
+        agent.learner.set_update_modes(stats=True, target_kl=tkl, consensus=cons)
     try:
         out = _learner_section(agent, steer_rollout, throttle_rollout, done, train_cfg, shared_grad_buffers, optimizer,
                                traffic_light, counter, shared_model_list, in_process_chief, fused_gather, losses_on_device,
-                               step_events, use_adv_norm, sec, lr, reward_scaler)
+                               step_events, use_adv_norm, sec, lr, reward_scaler, cons)
     finally:
         if sec is not None:
             agent.learner.set_update_modes()
@@ -398,12 +462,13 @@ def learner_section(agent, steer_rollout, throttle_rollout, done, train_cfg, sha
 
 def _learner_section(agent, steer_rollout, throttle_rollout, done, train_cfg, shared_grad_buffers, optimizer, traffic_light,
                      counter, shared_model_list, in_process_chief, fused_gather, losses_on_device, step_events, use_adv_norm,
-                     sec, lr, reward_scaler=None):
+                     sec, lr, reward_scaler=None, cons=False):
     nv_s, nv_t = agent.get_value(done, steer_rollout.get_last(as_tensor=True), throttle_rollout.get_last(as_tensor=True))
     if reward_scaler is not None or steer_rollout._tl_used or throttle_rollout._tl_used:
         steer_adv, throttle_adv = RolloutStorage.finish_rollouts(
             [steer_rollout, throttle_rollout], [nv_s.detach(), nv_t.detach()], normalise=use_adv_norm,
-            reward_scaler=reward_scaler, explained_variance=None if sec is None else sec.ev)
+            reward_scaler=reward_scaler, explained_variance=None if sec is None else sec.ev,
+            **_scaler_consensus(cons, reward_scaler, shared_grad_buffers))
     else:
         steer_adv = steer_rollout.compute_returns(nv_s.detach(), normalise=use_adv_norm,
                                                   explained_variance=None if sec is None else sec.ev[0:1])
@@ -553,20 +618,23 @@ def learner_section_multi(agent, rollouts, dones, train_cfg, shared_grad_buffers
     minibatches with the losses' denominator: like the losses, they are the SUM of the per-worker means.
     The 2N storages are finished by ONE RolloutStorage.finish_rollouts launch (bit-identical to 2N compute_returns calls
     when no time-limit flag was written and `reward_scaler`, a ReturnScaler for N environments, is None)."""
-    _check_scaler(reward_scaler, shared_grad_buffers)
+    _check_scaler(reward_scaler, shared_grad_buffers, train_cfg)
     tkl = _target_kl(train_cfg, shared_grad_buffers)
+    cons = _consensus_on(train_cfg, shared_grad_buffers)
     lr = _section_hyper(agent, train_cfg, shared_grad_buffers, True, optimizer)
     use_adv_norm = train_cfg["use_adv_norm"]
     nv = agent.get_values([(s.get_last(as_tensor=True), t.get_last(as_tensor=True)) for s, t in rollouts], dones)
     sec = None
     if stats is not None or tkl is not None:
-        sec = _SectionStats(agent, train_cfg["ppo_epoch"] * _steps_per_epoch(rollouts[0][0]), 2 * len(rollouts))
+        sec = _SectionStats(agent, train_cfg["ppo_epoch"] * _steps_per_epoch(rollouts[0][0]), 2 * len(rollouts),
+                            consensus_world=shared_grad_buffers.dist_world() if cons else 0)
     flat = RolloutStorage.finish_rollouts([x for pair in rollouts for x in pair], [v.detach() for pair in nv for v in pair],
                                           normalise=use_adv_norm, reward_scaler=reward_scaler,
-                                          explained_variance=None if sec is None else sec.ev)
+                                          explained_variance=None if sec is None else sec.ev,
+                                          **_scaler_consensus(cons, reward_scaler, shared_grad_buffers))
     advs = [(flat[2 * i], flat[2 * i + 1]) for i in range(len(rollouts))]
     if sec is not None:
-        agent.learner.set_update_modes(stats=True, target_kl=tkl)
+        agent.learner.set_update_modes(stats=True, target_kl=tkl, consensus=cons)
     dev_losses = []
     try:
         for _ in range(train_cfg["ppo_epoch"]):

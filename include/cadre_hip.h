@@ -684,6 +684,33 @@ int cadre_insert_rows_tl(const void* dst_table, const int32_t* slot, int32_t n_d
                          int32_t D, int32_t Hd, int32_t T, const float* feat, int64_t ldf, const int64_t* action,
                          const float* logp, const float* value, const float* rm, const int32_t* cmd, void* stream);
 
+/* ---------------------------------------------------------------- rank consensus (csrc/consensus.hip)
+ * Decisions that several data-parallel ranks must take identically.  The caller sums the inputs over the ranks first (one
+ * small all-reduce); every rank then runs the same kernel on the same reduced bits.  Sums, not means: R ranks with N workers
+ * each decide what one rank with R N workers decides.
+ *
+ * cadre_kl_consensus: one workgroup, one deciding lane, the rule the last arriver of cadre_ppo_loss_stats[_hp] applies
+ * (csrc/kl_rule.h, the same function, the same types).  kl: device float[2], the reduced approx_kl of steer and throttle.
+ * *stop is sticky; target_kl > 0 and fmaxf(kl[0], kl[1]) > 1.5f * target_kl sets it; applied = (*stop == 0) after the check
+ * goes to stats_row[6] and stats_row[F + 6] (stats_row may be NULL; no other field is written).  Then, unless stopped and when
+ * desired_kl > 0, the double-precision lr rule of cadre_ppo_loss_stats_hp runs on hp[CADRE_HP_LR] with hp[CADRE_HP_LR_MIN],
+ * hp[CADRE_HP_LR_MAX] and hp[CADRE_HP_LR_FACTOR]; desired_kl is the by-value argument, hp[CADRE_HP_DESIRED_KL] is not read
+ * (the caller keeps it 0 so that the loss kernel does not adapt on its own).  No other hp field is written.
+ * NaN: fmaxf ignores a NaN operand, so a head with a NaN KL does not count; with both NaN every comparison is false, the flag
+ * is not set and lr does not move — as in the loss kernel.
+ * Refused before any launch: NULL kl, target_kl negative or NaN, target_kl > 0 without stop, desired_kl > 0 without hp,
+ * stats_row with F < CADRE_PPO_STATS_FIELDS. */
+int cadre_kl_consensus(const float* kl, float target_kl, int32_t* stop, double desired_kl, double* hp, float* stats_row,
+                       int32_t F, void* stream);
+/* cadre_return_scale_merge: stats = device double [world][6], per rank the (count, mean, M2) of head 0 then head 1 (the
+ * first six doubles of that rank's return-statistics state).  Per head the ranks are merged with Chan's formula in rank
+ * order 0 .. world - 1 from an empty accumulator, ranks with count 0 skipped, and
+ * state[CADRE_RS_SCALE + h] = float32(1 / sqrt(M2 / count + epsilon)) is stored — the expression and rounding of
+ * cadre_return_stats.  While the merged count is 0 the scale slot is left as it is (initially 1).  Nothing else of `state`
+ * is written: the rank's own statistics and carries stay.  merged (may be NULL): receives the six merged doubles.
+ * Refused before any launch: NULL stats or state, world < 1, epsilon negative, NaN or infinite. */
+int cadre_return_scale_merge(const double* stats, int32_t world, double epsilon, double* state, double* merged, void* stream);
+
 /* ---------------------------------------------------------------- training checkpoints (csrc/checkpoint.hip)
  * cadre_state_capture: ONE launch copies n_ranges device ranges into one staging buffer and forms one 64-bit digest per
  * range from the same read (each source word is read once, each staging word written once; the digest costs no further
