@@ -141,6 +141,10 @@ SYMBOLS = {
     # epsilon, state, merged (may be NULL), stream
     "cadre_kl_consensus": [vp, f32, vp, f64, vp, vp, i32, vp],
     "cadre_return_scale_merge": [vp, i32, f64, vp, vp, vp],
+    # ensemble evaluation: O3, ldo, z_str, pos, cmd, N, C, Mg, m0, M, q (NULL: greedy), K_steer, K_throttle, action, logp,
+    # value, ord (may be NULL), stream / action, N, M, steer table, K_steer, throttle table, K_throttle, controls, stream
+    "cadre_sample_rows_ens": [vp, i64, i64, vp, vp, i32, i32, i32, i32, i32, vp, i32, i32, vp, vp, vp, vp, vp],
+    "cadre_ensemble_controls": [vp, i32, i32, vp, i32, vp, i32, vp, vp],
 }
 # entry points of the A/B build only (include/cadre_hip_ab.h; CADRE_BUILD_AB=1 python -m cadre_amd.build, then
 # CADRE_HIP_LIB=.../libcadre_hip_ab.so): bound when the loaded library has them

@@ -174,15 +174,17 @@ class CadreAgent(object):
             hip.check(L.cadre_sample(hip.ptr(O3[tower_row]), O3.shape[-1], hip.ptr(q), K, 1, K, hip.ptr(action),
                                      hip.ptr(logp), hip.stream()), "cadre_sample")
 
-    def act(self, tick_data):
+    def act(self, tick_data, deterministic=False):
         """agent.py:114-141.  Sampling consumes the global torch CPU generator exactly like the
         reference (one exponential_(1) draw of n_out floats per head, steer first).  The launch chain of an
         env step (packing, encoder, LSTM x 2, heads, sampling: ~150 kernels) has fixed shapes and pointers, so
         it is captured once per (window mode, command) into a hipGraph and replayed — same kernels, same order,
-        same results; inputs and outputs go through static buffers."""
+        same results; inputs and outputs go through static buffers.
+        `deterministic=True`: the greedy action (the first largest probability) — the sampler's q is all ones (p / 1.0f is
+        exact), nothing is drawn from the generator."""
         if self.act_graph and self.latent_cache and self.vae_device == self.device:
-            return self._act_graphed(tick_data)
-        return self.act_from_feature(self.get_latent_feature(tick_data), tick_data["command"])
+            return self._act_graphed(tick_data, deterministic)
+        return self.act_from_feature(self.get_latent_feature(tick_data), tick_data["command"], deterministic)
 
     # ------------------------------------------------------------------ act() as a hipGraph
     def _act_static(self, S, H, W):
@@ -225,7 +227,7 @@ class CadreAgent(object):
             self._sample_launch(O3, row, K, st["d_q"][j], st["action"][j:], st["logp"][j:])
         return O3
 
-    def _act_graphed(self, tick_data):
+    def _act_graphed(self, tick_data, deterministic=False):
         rgb, route_np, command = tick_data["rgb"], tick_data["route_fig"], int(tick_data["command"])
         S, H, W = rgb.shape[0], rgb.shape[1], rgb.shape[2]
         st = self._ag
@@ -250,8 +252,11 @@ class CadreAgent(object):
         st["h_route"][first:].copy_(torch.from_numpy(np.ascontiguousarray(route_np[first:])))
         st["h_meas"].copy_(torch.from_numpy(np.ascontiguousarray(tick_data["measurements"], dtype=np.float64)))
         nS, nT = self.arena.n_out
-        st["h_q"][0, :nS] = torch.empty(1, nS).exponential_(1)[0]          # steer draws first (reference order)
-        st["h_q"][1, :nT] = torch.empty(1, nT).exponential_(1)[0]
+        if deterministic:
+            st["h_q"].fill_(1.0)
+        else:
+            st["h_q"][0, :nS] = torch.empty(1, nS).exponential_(1)[0]      # steer draws first (reference order)
+            st["h_q"][1, :nT] = torch.empty(1, nT).exponential_(1)[0]
         st["d_rgb"][first:].copy_(st["h_rgb"][first:], non_blocking=True)
         st["d_route"][first:].copy_(st["h_route"][first:], non_blocking=True)
         st["d_meas"].copy_(st["h_meas"], non_blocking=True)
@@ -295,12 +300,15 @@ class CadreAgent(object):
         # the reference discards the new hidden state and returns the zeros (agent.py:123-124,141)
         return feat, [a_s, a_t], [lp_s, lp_t], [v_s, v_t], self.hidden_state
 
-    def act_from_feature(self, ppo_feature, command):
+    def act_from_feature(self, ppo_feature, command, deterministic=False):
         """The part of `act` after the encoder (agent.py:116-141) on a given [S,530] feature window."""
         O3, _, _ = self.learner.infer(ppo_feature, (command, command))
         nS, nT = self.arena.n_out
-        q_s = torch.empty(1, nS).exponential_(1)
-        q_t = torch.empty(1, nT).exponential_(1)
+        if deterministic:
+            q_s, q_t = torch.ones(1, nS), torch.ones(1, nT)
+        else:
+            q_s = torch.empty(1, nS).exponential_(1)
+            q_t = torch.empty(1, nT).exponential_(1)
         a_s, lp_s = self._sample(O3, 0, nS, q_s)
         a_t, lp_t = self._sample(O3, 2, nT, q_t)
         v_s = O3[1, :, :1].clone()
@@ -313,7 +321,7 @@ class CadreAgent(object):
         return ppo_feature, [a_s[0], a_t[0]], [lp_s, lp_t], [v_s, v_t], self.hidden_state
 
     # ------------------------------------------------------------------ act for N environments
-    def act_batch(self, obs_list, shifted=None):
+    def act_batch(self, obs_list, shifted=None, deterministic=False):
         """`[self.act(o) for o in obs_list]` for N environments in ONE launch chain: one encoder pass over every fresh
         frame (the newest frame of each window that shifted, all S frames of the others), cadre_act_windows (the LSTM
         input rows of all windows, rows sorted by command), one LSTM + MLP pass over all 2C command nets
@@ -322,6 +330,7 @@ class CadreAgent(object):
         frame since the last call, which skips the host-side comparison of the frames.  Global-RNG consumption is the
         loop's: one exponential_(1) draw per environment and head, env 0 steer, env 0 throttle, env 1 steer, ...
         The route quirk (agent.py:51-54: the caller's route_fig normalised in place) is kept per environment.
+        `deterministic=True`: the greedy action of every (environment, head) — q stays all ones, nothing is drawn.
         Returns an ActBatch: N tuples in exactly act()'s format."""
         check_act_batch(obs_list, shifted, self.max_envs, self.device, self.vae_device, self.command_num)
         N = len(obs_list)
@@ -371,7 +380,7 @@ class CadreAgent(object):
         meas_d = torch.from_numpy(np.ascontiguousarray(meas)).to(dev)
         nS, nT = a.n_out
         q = torch.ones(N, 2, 64)
-        for e in range(N):                                  # act()'s order: steer draws first, environment after environment
+        for e in range(0 if deterministic else N):          # act()'s order: steer draws first, environment after environment
             q[e, 0, :nS] = torch.empty(1, nS).exponential_(1)[0]
             q[e, 1, :nT] = torch.empty(1, nT).exponential_(1)[0]
         q_d = q.to(dev)
@@ -657,6 +666,14 @@ class CadreAgent(object):
             out.append(a.act_from_feature(f, tick_data["command"]))
         return out
 
+    @staticmethod
+    def ensemble_act_batch(agent_group, obs_list, shifted=None, deterministic=False):
+        """`[CadreAgent.ensemble_act(agent_group, o) for o in obs_list]` plus `avg_action` per environment (`.controls`) in
+        one launch chain per agent group: ppo_agent/evaluate.py EnsembleEvaluator.act, with one evaluator per agent group
+        kept on the lead agent.  Returns an EnsembleActBatch."""
+        from .evaluate import ensemble_act_batch
+        return ensemble_act_batch(agent_group, obs_list, shifted=shifted, deterministic=deterministic)
+
     # ------------------------------------------------------------------ snapshots
     def save_snapshot(self, model_path, fix_missing_lstm=False):
         """agent.py:245-260: pickled nn.Modules keyed by model name.  The reference writes
@@ -683,5 +700,9 @@ class CadreAgent(object):
             model_dict = torch.load(model_path, map_location="cpu", weights_only=False)
             for name in model_dict:
                 self.model_dict[name].load_state_dict(model_dict[name].state_dict())
+            # the modules' parameters are arena views with version counters of their own: the in-place load does not move
+            # arena.params._version, which keys the packed recurrent weights (learner.packed_weights) and the stacked copies
+            # of an EnsembleEvaluator — an in-place no-op on the arena does
+            self.arena.params[:0].zero_()
         except Exception as e:
             raise ImportError("load snapshot error due to {}".format(e))

@@ -558,6 +558,27 @@ int cadre_sample_rows_ord(const float* O3, int64_t ldo, int64_t z_str, const int
                           int32_t C, const float* q, int32_t K_steer, int32_t K_throttle, int64_t* action, float* logp,
                           float* value, const int32_t* ord, void* stream);
 
+/* ---------------------------------------------------------------- ensemble evaluation (csrc/ensemble.hip)
+ * eval.py:53-63 for N environments and M snapshots.  A group of Mg agents (Mg * C <= 16) shares one stacked arena with
+ * Mg * C commands: agent j's net (head h, command c) is arena net h * Mg * C + j * C + c, and O3 [2 * 2 Mg C][z_str] is
+ * that arena's tower output on the N sorted rows (row pitch ldo).
+ * cadre_sample_rows_ens: cadre_sample_rows / _ord for every (environment e, group agent j < Mg, head h), one wave each,
+ * the same statements: the actor row is tower z = 2 * (h * Mg * C + j * C + cmd[e]) at row pos[e], the critic z + 1.
+ * q [N][M][2][64] (agent m0 + j of the M of the whole ensemble); q == NULL is the greedy pick: the divisor is exactly
+ * 1.0f, the lowest index among the largest probabilities wins.  ord: NULL, or both heads' rank tables int32 [2][64] as
+ * in cadre_sample_rows_ord.  action i64 / logp / value f32 [N][M][2] are written at agent m0 + j only; an environment
+ * whose cmd or pos is out of range is skipped. */
+int cadre_sample_rows_ens(const float* O3, int64_t ldo, int64_t z_str, const int32_t* pos, const int32_t* cmd, int32_t N,
+                          int32_t C, int32_t Mg, int32_t m0, int32_t M, const float* q, int32_t K_steer, int32_t K_throttle,
+                          int64_t* action, float* logp, float* value, const int32_t* ord, void* stream);
+/* CadreAgent.avg_action (agent.py:83-95) per environment: action i64 [N][M][2] (steer bin, throttle bin), steer_tab f64
+ * [K_steer], throttle_tab f64 [K_throttle][2] (throttle, brake) -> controls f64 [N][3] = (steer, throttle, brake).  Each
+ * column is summed in float64 in agent order 0 .. M-1 and divided by (double)M (numpy's mean(0), bit for bit); with
+ * M > 1 a brake < 0.5 becomes 0.  A bin outside its table gives NaN for that environment's three controls; no table is
+ * read out of bounds. */
+int cadre_ensemble_controls(const int64_t* action, int32_t N, int32_t M, const double* steer_tab, int32_t K_steer,
+                            const double* throttle_tab, int32_t K_throttle, double* controls, void* stream);
+
 /* Initial LSTM state of every net z < Z: Hs[z*z_str ..] <- h0[(z / x_div)*n_per ..], same for Cs <- c0 (n_per floats
  * each, agent.py:166-175 hidden_state_batch shared by a head's command nets) and dC (Z*n_per floats, may be NULL) <- 0 */
 int cadre_lstm_init(const float* h0, const float* c0, float* Hs, float* Cs, float* dC, int64_t n_per,
