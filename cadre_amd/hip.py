@@ -145,6 +145,13 @@ SYMBOLS = {
     # value, ord (may be NULL), stream / action, N, M, steer table, K_steer, throttle table, K_throttle, controls, stream
     "cadre_sample_rows_ens": [vp, i64, i64, vp, vp, i32, i32, i32, i32, i32, vp, i32, i32, vp, vp, vp, vp, vp],
     "cadre_ensemble_controls": [vp, i32, i32, vp, i32, vp, i32, vp, vp],
+    # behaviour cloning: logits, ldl, l_ns, values, ldv, v_ns, actions, commands, returns, weights (may be NULL), B, C, K_steer,
+    # K_throttle, label_smoothing, bc_coeff, value_coeff, ent_coeff, inv_b, losses, dlogits, dvalues (both NULL: evaluation),
+    # scratch, poison, stats row (may be NULL), F, stats scratch, ord (may be NULL), stream / latent, ld_lat, n_frames, window,
+    # meas, T, S, obs, ldo, stream
+    "cadre_bc_loss": [vp, i64, i64, vp, i64, i64, vp, vp, vp, vp, i32, i32, i32, i32, f32, f32, f32, f32, f32, vp, vp, vp,
+                      vp, vp, vp, i32, vp, vp, vp],
+    "cadre_demo_rows": [vp, i64, i32, vp, vp, i32, i32, vp, i64, vp],
 }
 # entry points of the A/B build only (include/cadre_hip_ab.h; CADRE_BUILD_AB=1 python -m cadre_amd.build, then
 # CADRE_HIP_LIB=.../libcadre_hip_ab.so): bound when the loaded library has them
@@ -202,6 +209,7 @@ HP = dict(lr=0, clip=1, value_coeff=2, clip_coeff=3, ent_coeff=4, max_grad_norm=
 PPO_STATS_LR = 7      # CADRE_PPO_STATS_LR: field of head 0 of a stats row that cadre_grad_norms_hp fills with the step's lr
 
 PPO_STATS_FIELDS = 8  # CADRE_PPO_STATS_FIELDS (include/cadre_hip.h): loss diagnostics per head before the gradient norms
+BC_STATS_FIELDS = 6   # CADRE_BC_STATS_FIELDS: accuracy, NLL, entropy, |v - R|, weight sum, rows counted (means over inv_b)
 
 RS_SCALE, RS_CARRY = 6, 8  # CADRE_RS_SCALE / CADRE_RS_CARRY: the return-statistics block (count, mean, M2 per head first)
 

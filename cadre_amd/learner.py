@@ -104,7 +104,72 @@ class PPOLearnerHIP:
         self._kl_buf = None        # device float32 [4]: approx_kl steer, throttle of the step (two spare slots), reduced in place
         self._kl_sink = None       # device float32 [2] that receives the next step's reduced pair (the section's table)
         self._last_stats = None    # the workspace stats row of the update that ran last
+        # loss of the update (set_loss): "ppo", or "bc" — the imitation loss cadre_bc_loss in the place of the PPO loss
+        # launch, everything behind it unchanged.  The mode and its two scalars are part of the hipGraph keys.
+        self.loss_mode = "ppo"
+        self._bc = (0.0, 1.0)      # (label_smoothing, bc_coeff) of the imitation loss
         hip.lib()
+
+    # ------------------------------------------------------------------ loss selection
+    def set_loss(self, mode, label_smoothing=0.0, bc_coeff=1.0):
+        """"ppo" (default): the clipped-surrogate loss.  "bc": behaviour cloning — cross-entropy against the demonstrated bin
+        (workspace `actions`; -1 = no label for that head) with `label_smoothing` in [0, 1) and weight `bc_coeff`, the critic
+        regressed on workspace `returns`, the learner's own value_coeff / ent_coeff, per-row weights from the `adv` slot;
+        old_values / old_logp are not read.  The imitation statistics of a step (hip.BC_STATS_FIELDS per head) are in
+        workspace(B)["bc_stats"].  By-value scalars only: refused together with the device-hyper block."""
+        if mode not in ("ppo", "bc"):
+            raise ValueError("set_loss: mode %r (known: 'ppo', 'bc')" % (mode,))
+        if mode == "bc":
+            eps, coeff = float(label_smoothing), float(bc_coeff)
+            if not 0.0 <= eps < 1.0:
+                raise ValueError("set_loss: label_smoothing must be in [0, 1) (got %r)" % (label_smoothing,))
+            if not np.isfinite(coeff):
+                raise ValueError("set_loss: bc_coeff=%r" % (bc_coeff,))
+            self._check_bc_modes()
+            self._bc = (eps, coeff)
+        self.loss_mode = mode
+
+    def _check_bc_modes(self):
+        if self._hp_on:
+            raise hip.CadreHipError("the imitation loss takes its scalars by value: it is not available in device-hyper mode "
+                                    "(set_device_hyper(False), or pretrain before schedules / adaptive lr are armed)")
+        if self._loss_stats() or self.consensus:
+            raise hip.CadreHipError("the imitation loss has no PPO diagnostics, KL gate or rank consensus: call "
+                                    "set_update_modes() first")
+
+    def _bc_launch(self, w, B, inv_b, grad=True):
+        """cadre_bc_loss on the tower outputs in workspace(B): losses[3], the stats row bc_stats [2][BC_STATS_FIELDS] and,
+        with `grad`, dO3 (dlogits and dvalues).  grad=False is the evaluation form."""
+        a, S = self.a, self.S
+        O3, dO3, NP = w["O3"], w["dO3"], a.NP
+        if "bc_stats" not in w:
+            w["bc_stats"] = torch.zeros(2, hip.BC_STATS_FIELDS, device=a.device)
+            w["bc_scratch"] = torch.zeros(2 * hip.BC_STATS_FIELDS * ((B + 15) // 16), device=a.device)
+        eps, coeff = self._bc
+        ord_t = getattr(a, "ord", None)
+        hip.check(hip.lib().cadre_bc_loss(hip.ptr(O3), NP, 2 * B * NP, hip.ptr(O3[1]), NP, 2 * B * NP,
+                                          hip.ptr(w["actions"]), hip.ptr(w["commands"]), hip.ptr(w["returns"]), hip.ptr(w["adv"]),
+                                          B, a.C, a.n_out[0], a.n_out[1], eps, coeff, self.vc, self.ec, inv_b,
+                                          hip.ptr(w["losses"]), hip.ptr(dO3) if grad else None, hip.ptr(dO3[1]) if grad else None,
+                                          hip.ptr(w["loss_scratch"]), hip.ptr(w["sync"][a.Z * S:]), hip.ptr(w["bc_stats"]),
+                                          hip.BC_STATS_FIELDS, hip.ptr(w["bc_scratch"]), hip.ptr(ord_t), hip.stream()),
+                  "cadre_bc_loss")
+
+    def bc_evaluate(self, B, inv_b, sorted_rows=False, stats_row=None):
+        """Forward + the evaluation form of the imitation loss on the packed minibatch in workspace(B): no gradient is
+        written, no parameter moves.  The launch chain runs eagerly (no captured graph: a validation pass is bound by launch
+        overhead, once per epoch).  Returns (losses[3], bc_stats [2][BC_STATS_FIELDS]) — the workspace tensors, which the
+        next step overwrites; `stats_row` (device float32 [2][>= BC_STATS_FIELDS]) receives a copy of the statistics."""
+        if self.loss_mode != "bc":
+            raise hip.CadreHipError("bc_evaluate needs set_loss('bc')")
+        self._check_bc_modes()
+        a = self.a
+        w = self.workspace(B)
+        self._forward(w, B, (0, 1, a.Z), a.C, seg=w["seg"] if sorted_rows else None, fused_mlp=True)
+        self._bc_launch(w, B, inv_b, grad=False)
+        if stats_row is not None:
+            stats_row[:, :hip.BC_STATS_FIELDS].copy_(w["bc_stats"])
+        return w["losses"], w["bc_stats"]
 
     # ------------------------------------------------------------------ diagnostics / KL gate
     def stats_fields(self):
@@ -174,7 +239,9 @@ class PPOLearnerHIP:
         key = (("stats", self.target_kl),) if self._loss_stats() else ()
         key = key + ((("hp",),) if self._hp_on else ())
         key = key + ((("ord",),) if getattr(self.a, "ord", None) is not None else ())
-        return key + ((("consensus",),) if self.consensus else ())
+        key = key + ((("consensus",),) if self.consensus else ())
+        # the imitation loss is a mode (("bc", label_smoothing, bc_coeff)): its graphs hold cadre_bc_loss and its scalars
+        return key + ((("bc",) + self._bc,) if self.loss_mode == "bc" else ())
 
     # ------------------------------------------------------------------ device-resident hyper-parameters
     def _drop_update_graphs(self, hp=False):
@@ -389,6 +456,14 @@ class PPOLearnerHIP:
             self._wp_key = None if torch.cuda.is_current_stream_capturing() else key
         return self._wp[0, g0:], gs * self._wp.stride(1)
 
+    def invalidate_parameter_caches(self):
+        """The parameters were rewritten behind the optimiser's back (a broadcast, a reset of the step count): forget the
+        packed recurrent weights and move `params._version`, which keys every other copy held of them (the stacked arenas
+        of an EnsembleEvaluator).  The version moves through an in-place no-op on the arena, as load_snapshot does."""
+        self._wp_key = None
+        self._adam_fresh = None
+        self.a.params[:0].zero_()
+
     def _pkey(self):
         a = self.a
         return (a.step, a.params._version, a.params.data_ptr())
@@ -488,7 +563,10 @@ class PPOLearnerHIP:
         diagnostics are copied there after the launch sequence (one device-to-device copy), and the next clip_adam writes its
         per-model gradient norms into the same row."""
         a = self.a
-        if stats_row is not None and not self._loss_stats():
+        bc = self.loss_mode == "bc"
+        if bc:
+            self._check_bc_modes()
+        if stats_row is not None and not bc and not self._loss_stats():
             raise hip.CadreHipError("update(stats_row=...) needs set_update_modes(stats=True) (or a target_kl)")
         # The packed W_hh copies are current iff this learner's own fused optimiser step produced the parameters that are
         # in the arena now (a chief in another process, a broadcast or a checkpoint load change them behind our back: then
@@ -514,6 +592,10 @@ class PPOLearnerHIP:
 
     def _stats_out(self, B, stats_row):
         w = self.workspace(B)
+        if self.loss_mode == "bc":            # the imitation statistics; no gradient norms follow
+            if stats_row is not None:
+                stats_row[:, :hip.BC_STATS_FIELDS].copy_(w["bc_stats"])
+            return w["losses"]
         self._last_stats = w.get("stats")
         if stats_row is not None:
             stats_row.copy_(w["stats"])
@@ -593,7 +675,9 @@ class PPOLearnerHIP:
         if front:
             self._forward(w, B, (0, 1, Z), C, seg=seg, fused_mlp=True)
         ord_t = getattr(a, "ord", None)                 # ordinal policy heads: the rank table (static, like every pointer here)
-        if front and ord_t is not None:
+        if front and self.loss_mode == "bc":
+            self._bc_launch(w, B, inv_b)                # the imitation loss writes losses, dO3: the rest is indifferent
+        elif front and ord_t is not None:
             # one entry point for the four modes: hp NULL = by-value scalars, stats row NULL = no diagnostics
             stats = self._loss_stats()
             srow, sscr = self._stats_ws(w, B) if stats else (None, None)

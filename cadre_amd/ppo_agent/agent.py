@@ -514,7 +514,7 @@ class CadreAgent(object):
         v, a, e = losses.tolist()
         return v, a, e
 
-    def update_policy_from_storages(self, batches, sync=True, mlp_grads_ready=None, stats_row=None):
+    def update_policy_from_storages(self, batches, sync=True, mlp_grads_ready=None, stats_row=None, evaluate=False):
         """Fast path of the learner section: `batches` = [(steer_storage, steer_idx, steer_adv,
         throttle_storage, throttle_idx, throttle_adv), ...] one entry per worker (equal sizes).
         Same math as feed_forward_generator -> update_policy, but the minibatch gather writes
@@ -522,7 +522,8 @@ class CadreAgent(object):
         unless `sync` (one host sync per round instead of one per minibatch).  `mlp_grads_ready`
         (callable, optional) is invoked between the MLP-tower backward and the LSTM backward, when the
         gradients of arena[P0:] are final (Shared_grad_buffers.reduce_bucket_async starts their all-reduce
-        there, beside the LSTM backward).  `stats_row`: as in update_policy."""
+        there, beside the LSTM backward).  `stats_row`: as in update_policy.  `evaluate` (imitation loss only, see
+        imitate_from_storages): forward + the evaluation form of the loss on the gathered rows, no gradient."""
         nW = len(batches)
         Bw = batches[0][1].numel()
         B = nW * Bw
@@ -551,7 +552,7 @@ class CadreAgent(object):
                         hip.ptr(w["actions" + u][hd]), hip.ptr(w["commands" + u][hd]), hip.ptr(w["old_values" + u][hd]),
                         hip.ptr(w["returns" + u][hd]), hip.ptr(w["old_logp" + u][hd]), hip.ptr(w["adv" + u][hd]), st),
                         "cadre_gather_minibatch")
-            return self._finish_update(w, B, nW, srt, sync, mlp_grads_ready, stats_row=stats_row)
+            return self._finish_update(w, B, nW, srt, sync, mlp_grads_ready, evaluate=evaluate, stats_row=stats_row)
         # ONE gather launch for all workers and both heads: a device table of the storages' pointers (built once per set
         # of storages / advantage tensors) and one host-to-device copy of the 2*nW index vectors
         pairs = [(stor, adv) for (ss, si, sa, ts, ti, ta) in batches for (stor, adv) in ((ss, sa), (ts, ta))]
@@ -595,16 +596,16 @@ class CadreAgent(object):
                 hip.ptr(w["actions"]), hip.ptr(w["commands"]), hip.ptr(w["old_values"]),
                 hip.ptr(w["returns"]), hip.ptr(w["old_logp"]), hip.ptr(w["adv"]), hip.ptr(w["pos"]), hip.ptr(w["seg"]), st),
                 "cadre_gather_sorted_multi")
-            return self._finish_update(w, B, nW, srt, sync, mlp_grads_ready, placed=True, stats_row=stats_row)
+            return self._finish_update(w, B, nW, srt, sync, mlp_grads_ready, evaluate=evaluate, placed=True, stats_row=stats_row)
         hip.check(L.cadre_gather_minibatch_multi(
             hip.ptr(table), 2 * nW, s0._ldo, s0.seq_length, s0._ldh, hip.ptr(stage[1]), Bw, a.D, a.D, B,
             hip.ptr(w[Xk]), w[Xk].stride(0), a.DP, hip.ptr(w[hk]), hip.ptr(w[ck]), w[hk].stride(0), a.DP,
             hip.ptr(w["actions" + u]), hip.ptr(w["commands" + u]), hip.ptr(w["old_values" + u]),
             hip.ptr(w["returns" + u]), hip.ptr(w["old_logp" + u]), hip.ptr(w["adv" + u]), st),
             "cadre_gather_minibatch_multi")
-        return self._finish_update(w, B, nW, srt, sync, mlp_grads_ready, stats_row=stats_row)
+        return self._finish_update(w, B, nW, srt, sync, mlp_grads_ready, evaluate=evaluate, stats_row=stats_row)
 
-    def _finish_update(self, w, B, nW, srt, sync, mlp_grads_ready=None, placed=False, stats_row=None):
+    def _finish_update(self, w, B, nW, srt, sync, mlp_grads_ready=None, placed=False, stats_row=None, evaluate=False):
         """Row sort by command (sorted mode; placed: the gather already put every row at its sorted position), the fused update
         and the loss hand-back."""
         L, st, a = hip.lib(), hip.stream(), self.arena
@@ -619,11 +620,33 @@ class CadreAgent(object):
                 hip.ptr(w["actions"]), hip.ptr(w["commands"]), hip.ptr(w["old_values"]),
                 hip.ptr(w["returns"]), hip.ptr(w["old_logp"]), hip.ptr(w["adv"]), 2, w["X"].stride(0), w["h0"].stride(0), st),
                 "cadre_permute_minibatch")
+        if evaluate:                                     # imitate_from_storages(evaluate=True): forward + loss only
+            losses, _ = self.learner.bc_evaluate(B, float(nW) / B, sorted_rows=srt, stats_row=stats_row)
+            return tuple(losses.tolist()) if sync else losses.clone()
         losses = self.learner.update(B, float(nW) / B, sorted_rows=srt, mlp_grads_ready=mlp_grads_ready, stats_row=stats_row)
         self.arena.attach_grads(self.model_dict)
         if sync:
             return tuple(losses.tolist())
         return losses.clone()
+
+    def imitate_from_storages(self, batches, stats_row=None, sync=True, label_smoothing=None, bc_coeff=None, evaluate=False):
+        """One behaviour-cloning step on demonstration rows: update_policy_from_storages (the same gather, sorted or
+        unsorted, one launch, then the update) with the learner's loss switched to the imitation loss (PPOLearnerHIP.set_loss)
+        for the duration of the call; the mode that was selected before is restored on exit.  `batches` as there, with the
+        storages of a DemoSet (cadre_amd.imitation) and the row weights in the place of the advantages: storage.action is the
+        demonstrated bin (-1: no label for that head), storage.returns the critic's target.  Gradients of all 16 nets are in
+        `.grad` afterwards; the caller takes the optimiser step (chief_step / learner.clip_adam).
+        `label_smoothing` / `bc_coeff`: None keeps the learner's current imitation settings.  `stats_row`: device float32
+        [2][>= hip.BC_STATS_FIELDS] that receives the step's imitation statistics (accuracy, NLL, entropy, |v - R|, weight
+        sum, rows counted).  `evaluate`: the evaluation form — losses and statistics only, no gradient, nothing moves."""
+        lrn = self.learner
+        prev = (lrn.loss_mode,) + lrn._bc
+        eps, coeff = lrn._bc
+        lrn.set_loss("bc", eps if label_smoothing is None else label_smoothing, coeff if bc_coeff is None else bc_coeff)
+        try:
+            return self.update_policy_from_storages(batches, sync=sync, stats_row=stats_row, evaluate=bool(evaluate))
+        finally:
+            lrn.loss_mode, lrn._bc = prev[0], prev[1:]
 
     def update_model(self, shared_model_list):
         """agent.py:239-243 (weight pull).  Same arena -> nothing to copy."""

@@ -21,7 +21,8 @@ class RolloutStorage(object):
     _insert_tables = {}          # insert_batch: device pointer tables of storage sets, keyed by the pointers
     _finish_tables = {}          # finish_rollouts: likewise
 
-    def __init__(self, num_steps, mini_batch_num, feature_dims, seq_length, hidden_size, use_gae, gamma, tau):
+    def __init__(self, num_steps, mini_batch_num, feature_dims, seq_length, hidden_size, use_gae, gamma, tau, device="cpu"):
+        """`device` (not in the reference, which allocates on the CPU and moves with .to()): allocate there at once."""
         T = num_steps
         self.mini_batch_num = mini_batch_num
         self.num_steps = T
@@ -35,7 +36,7 @@ class RolloutStorage(object):
         self._tl_used = False        # a time-limit flag was ever written: the finishing stage then reads time_limits
         self._ldo = _rup(feature_dims, PAD)
         self._ldh = _rup(hidden_size, PAD)
-        self._alloc(torch.device("cpu"))
+        self._alloc(torch.device(device))
 
     def _alloc(self, device):
         T = self.num_steps

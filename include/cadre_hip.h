@@ -558,6 +558,44 @@ int cadre_sample_rows_ord(const float* O3, int64_t ldo, int64_t z_str, const int
                           int32_t C, const float* q, int32_t K_steer, int32_t K_throttle, int64_t* action, float* logp,
                           float* value, const int32_t* ord, void* stream);
 
+/* ---------------------------------------------------------------- behaviour cloning (csrc/imitation.hip)
+ * cadre_bc_loss: the imitation loss where cadre_ppo_loss_ord stands in the update — the same addressing of logits, values,
+ * dlogits and dvalues, the same grid, the same `scratch` (arrival counter zero on entry and left zero, partials combined by
+ * the last arriving workgroup in workgroup order: two launches on the same inputs give the same bits), the same `poison`
+ * and the same rank table `ord` (NULL, or ord[h][0] = -1: the plain categorical head).  Sample arrays [2 heads][B]:
+ * actions (the demonstrated bin), commands, returns (the critic's regression target), weights (NULL: 1).
+ * For head h, row b, command c in range, the own net's normalised logits lg_k and probabilities p_k (the statements of the
+ * PPO kernel), K = n_out of the head, e = label_smoothing and t_k = (1 - e) [k = a] + e / K:
+ *   ce_b = -sum_k t_k lg_k     H_b = -sum_k p_k lg_k     vl_b = (v - R)^2
+ *   losses[0] = value_coeff 0.5 sum w_b vl_b inv_b   losses[1] = bc_coeff sum w_b ce_b inv_b   losses[2] = ent_coeff sum w_b H_b inv_b
+ * (total = losses[0] + losses[1] - losses[2]), and
+ *   dlogits = w_b inv_b (bc_coeff (p_k - t_k) + ent_coeff p_k (lg_k + H_b))   in bin space (an ordinal head: through ord_backward)
+ *   dvalues = value_coeff w_b inv_b (v - R)
+ * for the own net; columns >= K and the other C - 1 nets of the head get exact zeros (whole rows of ldl columns).
+ * A row whose command is out of range or whose action is outside 0 .. K - 1 (-1 is the "no label for this head" marker)
+ * adds nothing for that head and gets exact zeros in all C nets.
+ * dlogits == NULL && dvalues == NULL: the evaluation form, losses and statistics only (exactly one NULL is refused).
+ * stats_row (may be NULL) float [2][F], F >= CADRE_BC_STATS_FIELDS, per head, means over inv_b in the same fixed order:
+ *   0 top-1 accuracy (the lowest index among the largest p_k equals a)   1 mean -lg_a (unweighted, unsmoothed)
+ *   2 mean H   3 mean |v - R|   4 sum w inv_b   5 rows counted inv_b
+ * stats_scratch: 2 * ceil(B / 16) * CADRE_BC_STATS_FIELDS floats.  Refused before any launch: bad B, C or n_out,
+ * ldl < n_out or > 64, NULL required pointers, label_smoothing outside [0, 1), exactly one of dlogits / dvalues NULL. */
+#define CADRE_BC_STATS_FIELDS 6
+int cadre_bc_loss(const float* logits, int64_t ldl, int64_t l_ns, const float* values, int64_t ldv, int64_t v_ns,
+                  const int64_t* actions, const int32_t* commands, const float* returns, const float* weights,
+                  int32_t B, int32_t C, int32_t n_out_steer, int32_t n_out_throttle, float label_smoothing,
+                  float bc_coeff, float value_coeff, float ent_coeff, float inv_b, float* losses, float* dlogits,
+                  float* dvalues, float* scratch, const int32_t* poison, float* stats_row, int32_t F,
+                  float* stats_scratch, const int32_t* ord, void* stream);
+/* cadre_demo_rows: the observation rows of a demonstration set in one launch.  latent f32 [n_frames][ld_lat >= 512] (each
+ * distinct frame encoded once), window int32 [T][S], meas f64 [n_frames][3] -> obs f32 [T][S][ldo]:
+ *   obs[t][s][0:512] = latent[window[t][s]] | [512:530] = the frame's three measurements as f32, six times
+ *   (cadre_append_measurements) | zeros up to the pitch.
+ * A window index outside 0 .. n_frames - 1 reads nothing and gives NaN in columns 0 .. 529.  16 bytes per lane: both
+ * pitches are multiples of 4 floats, both bases 16-byte aligned, 532 <= ldo <= 1024.  Rows past T are not touched. */
+int cadre_demo_rows(const float* latent, int64_t ld_lat, int32_t n_frames, const int32_t* window, const double* meas,
+                    int32_t T, int32_t S, float* obs, int64_t ldo, void* stream);
+
 /* ---------------------------------------------------------------- ensemble evaluation (csrc/ensemble.hip)
  * eval.py:53-63 for N environments and M snapshots.  A group of Mg agents (Mg * C <= 16) shares one stacked arena with
  * Mg * C commands: agent j's net (head h, command c) is arena net h * Mg * C + j * C + c, and O3 [2 * 2 Mg C][z_str] is
