@@ -152,6 +152,14 @@ SYMBOLS = {
     "cadre_bc_loss": [vp, i64, i64, vp, i64, i64, vp, vp, vp, vp, i32, i32, i32, i32, f32, f32, f32, f32, f32, vp, vp, vp,
                       vp, vp, vp, i32, vp, vp, vp],
     "cadre_demo_rows": [vp, i64, i32, vp, vp, i32, i32, vp, i64, vp],
+    # demonstration term inside the PPO step: logits, ldl, l_ns, values, ldv, v_ns, actions, commands, old_values, returns,
+    # old_logp, adv (PPO rows: advantage, demonstration rows: weight), row_kind, B, C, K_steer, K_throttle, hp (may be NULL),
+    # clip, value_coeff, clip_coeff, ent_coeff, inv_b, label_smoothing, demo_coeff, demo_value_coeff, inv_bd, losses[3],
+    # demo_losses[2], dlogits, dvalues, scratch, demo scratch, poison, PPO stats row (may be NULL), F, stats scratch, target_kl,
+    # stop, demo stats row (may be NULL), demo F, ord (may be NULL), stream / pos (NULL: identity), B, B_ppo, row_kind, stream
+    "cadre_ppo_demo_loss": [vp, i64, i64, vp, i64, i64, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, vp, f32, f32, f32, f32,
+                            f32, f32, f32, f32, f32, vp, vp, vp, vp, vp, vp, vp, vp, i32, vp, f32, vp, vp, i32, vp, vp],
+    "cadre_mix_row_kinds": [vp, i32, i32, vp, vp],
 }
 # entry points of the A/B build only (include/cadre_hip_ab.h; CADRE_BUILD_AB=1 python -m cadre_amd.build, then
 # CADRE_HIP_LIB=.../libcadre_hip_ab.so): bound when the loaded library has them
@@ -206,6 +214,10 @@ def lib():
 # the hyper-parameter block of the `_hp` entry points (CADRE_HP_* of include/cadre_hip.h): field name -> index
 HP_FIELDS = 16
 HP = dict(lr=0, clip=1, value_coeff=2, clip_coeff=3, ent_coeff=4, max_grad_norm=5, desired_kl=6, lr_min=7, lr_max=8, lr_factor=9)
+# two of the block's reserved fields, read by cadre_ppo_demo_loss only (the enumerators CADRE_HP_DEMO_COEFF /
+# CADRE_HP_DEMO_VALUE_COEFF of the header); HP_INDEX: every named field, what PPOLearnerHIP.set_hyper looks names up in
+HP_DEMO_COEFF, HP_DEMO_VALUE_COEFF = 10, 11
+HP_INDEX = dict(HP, demo_coeff=HP_DEMO_COEFF, demo_value_coeff=HP_DEMO_VALUE_COEFF)
 PPO_STATS_LR = 7      # CADRE_PPO_STATS_LR: field of head 0 of a stats row that cadre_grad_norms_hp fills with the step's lr
 
 PPO_STATS_FIELDS = 8  # CADRE_PPO_STATS_FIELDS (include/cadre_hip.h): loss diagnostics per head before the gradient norms

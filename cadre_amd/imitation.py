@@ -23,6 +23,7 @@ from . import hip, replay
 GAE_MAX_T = 3000          # rows per cadre_gae_multi launch (include/cadre_hip.h)
 PRETRAIN_KEYS = ("episodes", "epochs", "minibatch", "lr", "label_smoothing", "balance", "validation_fraction",
                  "max_grad_norm", "return_scale", "seed")
+DEMO_MIX_KEYS = ("episodes", "coeff", "value_coeff", "blocks", "label_smoothing", "balance", "return_scale", "seed")
 
 
 # ----------------------------------------------------------------------------- host helpers
@@ -342,9 +343,8 @@ def pretrain_from_config(agent, cfg, gamma, max_grad_norm, shared_grad_buffers=N
     world = shared_grad_buffers.dist_world() if shared_grad_buffers is not None else 0
     records = None
     if rank == 0:
-        src = cfg["episodes"]
-        paths = replay.list_episodes(src) if isinstance(src, (str, os.PathLike)) else list(src)
-        demo = DemoSet.from_episodes(agent, paths, gamma, balance=cfg["balance"], return_scale=cfg["return_scale"])
+        # (a set train_cfg["demo_mix"] built from the same records and parameters is shared: frames are encoded once)
+        demo = demo_set_for(agent, cfg["episodes"], gamma, cfg["balance"], cfg["return_scale"])
         val = None
         if cfg["validation_fraction"] is not None and len(demo.episodes) >= 2:
             demo, val = demo.split(cfg["validation_fraction"], cfg["seed"])
@@ -356,3 +356,119 @@ def pretrain_from_config(agent, cfg, gamma, max_grad_norm, shared_grad_buffers=N
         dist.broadcast(agent.arena.params, src=0)
         agent.learner.invalidate_parameter_caches()
     return records
+
+
+# ----------------------------------------------------------------------------- train_cfg["demo_mix"]: DAPG-style mixing
+def _episode_paths(src):
+    return replay.list_episodes(src) if isinstance(src, (str, os.PathLike)) else list(src)
+
+
+def _demo_key(src, gamma, balance, return_scale):
+    paths = _episode_paths(src)
+    if not all(isinstance(p, (str, os.PathLike)) for p in paths):
+        return None                                      # loaded record dicts: nothing to key a shared set on
+    return (tuple(os.fspath(p) for p in paths), float(gamma), balance, float(return_scale))
+
+
+def demo_set_for(agent, src, gamma, balance, return_scale, keep=False):
+    """The DemoSet of record directory / path list `src` with these parameters.  keep: the set stays with the agent, so a
+    later call that names the same records and parameters (train_cfg.pretrain beside train_cfg.demo_mix) gets the same
+    object instead of encoding every frame again."""
+    key = _demo_key(src, gamma, balance, return_scale)
+    kept = agent.__dict__.setdefault("_demo_sets", {})
+    if key is not None and key in kept:
+        return kept[key]
+    demo = DemoSet.from_episodes(agent, _episode_paths(src), gamma, balance=balance, return_scale=return_scale)
+    if keep and key is not None:
+        kept[key] = demo
+    return demo
+
+
+class DemoMixer(object):
+    """The demonstration rows of each mixed PPO step (CadreAgent.update_policy_from_storages(..., demo=)).
+    entries(Bw, episode, step) -> `blocks` entries of Bw demonstration rows each, of the form DemoSet.batch returns.
+    The draw is STATELESS: the row indices are a pure function of (seed, rank, episode, step, Bw, blocks, len(demo_set)),
+    drawn from a private torch.Generator seeded from exactly those values — never from the global CPU generator, whose
+    stream belongs to the PPO sampler and act().  A resumed run therefore draws the rows the uninterrupted run would have
+    drawn, with nothing added to a checkpoint (the DemoSet is rebuilt from the record directory).  Sampling is a prefix of
+    a permutation of the set, or with replacement when blocks * Bw exceeds its size.
+    coeff / value_coeff / label_smoothing ride along for the training loop (demo_mix_config)."""
+
+    def __init__(self, demo_set, blocks=1, seed=0, rank=0, coeff=1.0, value_coeff=0.0, label_smoothing=0.0):
+        if isinstance(blocks, bool) or int(blocks) != blocks or int(blocks) < 1:
+            raise ValueError("DemoMixer: blocks=%r" % (blocks,))
+        if len(demo_set) < 1:
+            raise ValueError("DemoMixer: an empty demonstration set")
+        self.demo, self.blocks, self.seed, self.rank = demo_set, int(blocks), int(seed), int(rank)
+        self.coeff, self.value_coeff, self.label_smoothing = coeff, float(value_coeff), float(label_smoothing)
+
+    def indices(self, Bw, episode, step):
+        """int64 [blocks * Bw] row indices of the draw with this key."""
+        Bw, T = int(Bw), len(self.demo)
+        if Bw < 1 or int(episode) < 0 or int(step) < 0:
+            raise ValueError("DemoMixer: Bw=%r, episode=%r, step=%r" % (Bw, episode, step))
+        key = [self.seed & 0xFFFFFFFFFFFFFFFF, self.rank, int(episode), int(step), Bw, self.blocks, T]
+        lo, hi = np.random.SeedSequence(key).generate_state(2, dtype=np.uint32)
+        g = torch.Generator()
+        g.manual_seed(((int(hi) << 32) | int(lo)) & 0x7FFFFFFFFFFFFFFF)
+        n = self.blocks * Bw
+        if n > T:
+            return torch.randint(0, T, (n,), generator=g, dtype=torch.int64)
+        return torch.randperm(T, generator=g)[:n]
+
+    def entries(self, Bw, episode, step):
+        idx = self.indices(Bw, episode, step)
+        Bw = int(Bw)
+        return [self.demo.batch(idx[i * Bw:(i + 1) * Bw])[0] for i in range(self.blocks)]
+
+
+def demo_mix_config(train_cfg_value):
+    """train_cfg["demo_mix"]: absent / None -> None; else a dict {"episodes": DIR or a list of record paths (required),
+    "coeff": a number, ("linear", start, end) or a callable of episode / max_episode (ppo_agent.train.schedule_value; 1.0),
+    "value_coeff" (0.0), "blocks" (1), "label_smoothing" (0.0), "balance" ("command"), "return_scale" (1.0), "seed" (0)} ->
+    the dict with defaults filled in.  value_coeff defaults to 0 because the Monte-Carlo returns of a demonstrator and the
+    GAE returns of the rollouts (under reward scaling) live on different scales: whoever sets it also sets return_scale."""
+    cfg = train_cfg_value
+    if cfg is None:
+        return None
+    if not isinstance(cfg, dict):
+        raise ValueError("train_cfg.demo_mix: expected None or a dict (got %r)" % (cfg,))
+    unknown = sorted(set(cfg) - set(DEMO_MIX_KEYS))
+    if unknown or "episodes" not in cfg:
+        raise ValueError("train_cfg.demo_mix: needs episodes; known keys %r (unknown: %r)" % (DEMO_MIX_KEYS, unknown))
+    coeff = cfg.get("coeff", 1.0)
+    if not callable(coeff):
+        ok = (isinstance(coeff, (tuple, list)) and len(coeff) == 3 and coeff[0] == "linear"
+              and all(_is_number(v) for v in coeff[1:])) or _is_number(coeff)
+        if not ok:
+            raise ValueError("train_cfg.demo_mix: coeff must be a number, (\"linear\", start, end) or a callable (got %r)" % (coeff,))
+        coeff = tuple(coeff) if isinstance(coeff, (tuple, list)) else float(coeff)
+    blocks = cfg.get("blocks", 1)
+    for name in ("value_coeff", "label_smoothing", "return_scale"):
+        if name in cfg and not _is_number(cfg[name]):
+            raise ValueError("train_cfg.demo_mix: %s=%r is not a finite number" % (name, cfg[name]))
+    if isinstance(blocks, bool) or not isinstance(blocks, (int, np.integer)) or blocks < 1:
+        raise ValueError("train_cfg.demo_mix: blocks must be an integer >= 1 (got %r)" % (blocks,))
+    seed = cfg.get("seed", 0)
+    if isinstance(seed, bool) or not isinstance(seed, (int, np.integer)):
+        raise ValueError("train_cfg.demo_mix: seed must be an integer (got %r)" % (seed,))
+    out = dict(episodes=cfg["episodes"], coeff=coeff, value_coeff=float(cfg.get("value_coeff", 0.0)), blocks=int(blocks),
+               label_smoothing=float(cfg.get("label_smoothing", 0.0)), balance=cfg.get("balance", "command"),
+               return_scale=float(cfg.get("return_scale", 1.0)), seed=int(seed))
+    if not 0.0 <= out["label_smoothing"] < 1.0:
+        raise ValueError("train_cfg.demo_mix: need 0 <= label_smoothing < 1 (got %r)" % (cfg["label_smoothing"],))
+    if out["balance"] not in (None, "command"):
+        raise ValueError("train_cfg.demo_mix: balance must be \"command\" or None (got %r)" % (out["balance"],))
+    return out
+
+
+def _is_number(v):
+    return (not isinstance(v, bool)) and isinstance(v, (int, float, np.integer, np.floating)) and bool(np.isfinite(v))
+
+
+def demo_mixer_from_config(agent, cfg, gamma, rank=0):
+    """train_cfg["demo_mix"] (already through demo_mix_config) -> a DemoMixer over the DemoSet of its records.  The set is
+    kept with the agent (demo_set_for(keep=True)) so that train_cfg.pretrain on the same records shares it."""
+    demo = demo_set_for(agent, cfg["episodes"], gamma, cfg["balance"], cfg["return_scale"], keep=True)
+    return DemoMixer(demo, blocks=cfg["blocks"], seed=cfg["seed"], rank=rank, coeff=cfg["coeff"],
+                     value_coeff=cfg["value_coeff"], label_smoothing=cfg["label_smoothing"])

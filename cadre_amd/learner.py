@@ -108,17 +108,38 @@ class PPOLearnerHIP:
         # launch, everything behind it unchanged.  The mode and its two scalars are part of the hipGraph keys.
         self.loss_mode = "ppo"
         self._bc = (0.0, 1.0)      # (label_smoothing, bc_coeff) of the imitation loss
+        # "ppo+demo": cadre_ppo_demo_loss — PPO rows and demonstration rows in one minibatch (DAPG-style mixing)
+        self._demo = (0.0, 0.0, 0.0)   # (label_smoothing, demo_coeff, demo_value_coeff) of the mixed loss
+        self._demo_rows = None     # B_ppo: the leading unsorted rows of the minibatch that are PPO rows (set_demo_rows)
         hip.lib()
 
     # ------------------------------------------------------------------ loss selection
-    def set_loss(self, mode, label_smoothing=0.0, bc_coeff=1.0):
+    def set_loss(self, mode, label_smoothing=0.0, bc_coeff=1.0, demo_coeff=None, demo_value_coeff=None):
         """"ppo" (default): the clipped-surrogate loss.  "bc": behaviour cloning — cross-entropy against the demonstrated bin
         (workspace `actions`; -1 = no label for that head) with `label_smoothing` in [0, 1) and weight `bc_coeff`, the critic
         regressed on workspace `returns`, the learner's own value_coeff / ent_coeff, per-row weights from the `adv` slot;
         old_values / old_logp are not read.  The imitation statistics of a step (hip.BC_STATS_FIELDS per head) are in
-        workspace(B)["bc_stats"].  By-value scalars only: refused together with the device-hyper block."""
-        if mode not in ("ppo", "bc"):
-            raise ValueError("set_loss: mode %r (known: 'ppo', 'bc')" % (mode,))
+        workspace(B)["bc_stats"].  By-value scalars only: refused together with the device-hyper block.
+        "ppo+demo": the clipped-surrogate loss on the first set_demo_rows() unsorted rows of the minibatch and the imitation
+        loss (weight `demo_coeff`, critic weight `demo_value_coeff`, `label_smoothing`, no entropy term, mean over the
+        demonstration rows) on the rest, in ONE launch (cadre_ppo_demo_loss).  Diagnostics, the KL gate, the adaptive lr and
+        rank consensus work as in "ppo" and see the PPO rows only; a stopped step skips the whole update, the demonstration
+        term included.  In device-hyper mode the two demo coefficients live in the block (set_hyper(demo_coeff=, ...)):
+        a changed value needs no new graph.  None keeps the current coefficient.  The demo losses / statistics of a step are
+        in workspace(B)["demo_losses"] / ["demo_stats"]."""
+        if mode not in ("ppo", "bc", "ppo+demo"):
+            raise ValueError("set_loss: mode %r (known: 'ppo', 'bc', 'ppo+demo')" % (mode,))
+        if mode == "ppo+demo":
+            eps = float(label_smoothing)
+            dc = self._demo[1] if demo_coeff is None else float(demo_coeff)
+            dvc = self._demo[2] if demo_value_coeff is None else float(demo_value_coeff)
+            if not 0.0 <= eps < 1.0:
+                raise ValueError("set_loss: label_smoothing must be in [0, 1) (got %r)" % (label_smoothing,))
+            if not (np.isfinite(dc) and np.isfinite(dvc)):
+                raise ValueError("set_loss: demo_coeff=%r, demo_value_coeff=%r" % (demo_coeff, demo_value_coeff))
+            self._demo = (eps, dc, dvc)
+            if self._hp_on:
+                self.set_hyper(demo_coeff=dc, demo_value_coeff=dvc)
         if mode == "bc":
             eps, coeff = float(label_smoothing), float(bc_coeff)
             if not 0.0 <= eps < 1.0:
@@ -128,6 +149,46 @@ class PPOLearnerHIP:
             self._check_bc_modes()
             self._bc = (eps, coeff)
         self.loss_mode = mode
+
+    def set_demo_rows(self, B_ppo):
+        """"ppo+demo": unsorted rows 0 .. B_ppo - 1 of the next minibatches are PPO rows, the rest demonstration rows."""
+        if B_ppo is not None and int(B_ppo) < 0:
+            raise ValueError("set_demo_rows: B_ppo=%r" % (B_ppo,))
+        self._demo_rows = None if B_ppo is None else int(B_ppo)
+
+    def _demo_launch(self, w, B, inv_b, sorted_rows):
+        """cadre_mix_row_kinds + cadre_ppo_demo_loss on the tower outputs in workspace(B), in the place of the PPO loss."""
+        a, S = self.a, self.S
+        L, st = hip.lib(), hip.stream()
+        O3, dO3, NP = w["O3"], w["dO3"], a.NP
+        B_ppo = self._demo_rows
+        if B_ppo is None or B_ppo > B:
+            raise hip.CadreHipError("the 'ppo+demo' loss needs set_demo_rows(B_ppo) with 0 <= B_ppo <= B (got %r, B = %d)" % (B_ppo, B))
+        if "row_kind" not in w:
+            nblk = (B + 15) // 16
+            w["row_kind"] = torch.zeros(2, B, dtype=torch.int32, device=a.device)
+            w["demo_losses"] = torch.zeros(2, device=a.device)
+            w["demo_stats"] = torch.zeros(2, hip.BC_STATS_FIELDS, device=a.device)
+            w["demo_scratch"] = torch.zeros(2 * nblk * (2 + hip.BC_STATS_FIELDS), device=a.device)
+        hip.check(L.cadre_mix_row_kinds(hip.ptr(w["pos"]) if sorted_rows else None, B, B_ppo, hip.ptr(w["row_kind"]), st),
+                  "cadre_mix_row_kinds")
+        stats = self._loss_stats()
+        srow, sscr = self._stats_ws(w, B) if stats else (None, None)
+        eps, dc, dvc = self._demo
+        inv_bd = 1.0 / (B - B_ppo) if B > B_ppo else 1.0
+        ord_t = getattr(a, "ord", None)
+        hip.check(L.cadre_ppo_demo_loss(hip.ptr(O3), NP, 2 * B * NP, hip.ptr(O3[1]), NP, 2 * B * NP,
+                                        hip.ptr(w["actions"]), hip.ptr(w["commands"]), hip.ptr(w["old_values"]),
+                                        hip.ptr(w["returns"]), hip.ptr(w["old_logp"]), hip.ptr(w["adv"]),
+                                        hip.ptr(w["row_kind"]), B, a.C, a.n_out[0], a.n_out[1],
+                                        hip.ptr(self._hp) if self._hp_on else None, self.clip, self.vc, self.cc, self.ec, inv_b,
+                                        eps, dc, dvc, inv_bd, hip.ptr(w["losses"]), hip.ptr(w["demo_losses"]),
+                                        hip.ptr(dO3), hip.ptr(dO3[1]), hip.ptr(w["loss_scratch"]), hip.ptr(w["demo_scratch"]),
+                                        hip.ptr(w["sync"][a.Z * S:]), hip.ptr(srow), srow.shape[1] if stats else 0,
+                                        hip.ptr(sscr), self._loss_tkl(),
+                                        hip.ptr(self._stop) if (stats and self.target_kl is not None) else None,
+                                        hip.ptr(w["demo_stats"]), hip.BC_STATS_FIELDS, hip.ptr(ord_t), st),
+                  "cadre_ppo_demo_loss")
 
     def _check_bc_modes(self):
         if self._hp_on:
@@ -241,7 +302,12 @@ class PPOLearnerHIP:
         key = key + ((("ord",),) if getattr(self.a, "ord", None) is not None else ())
         key = key + ((("consensus",),) if self.consensus else ())
         # the imitation loss is a mode (("bc", label_smoothing, bc_coeff)): its graphs hold cadre_bc_loss and its scalars
-        return key + ((("bc",) + self._bc,) if self.loss_mode == "bc" else ())
+        key = key + ((("bc",) + self._bc,) if self.loss_mode == "bc" else ())
+        # the mixed loss is a mode: label_smoothing and B_ppo are by value always, the two coefficients unless they live in the
+        # block (device-hyper mode: a decaying coefficient replays one graph)
+        if self.loss_mode == "ppo+demo":
+            key = key + ((("demo", self._demo[0], self._demo_rows) + (() if self._hp_on else self._demo[1:])),)
+        return key
 
     # ------------------------------------------------------------------ device-resident hyper-parameters
     def _drop_update_graphs(self, hp=False):
@@ -288,6 +354,7 @@ class PPOLearnerHIP:
         m = self._hp_host
         m[hip.HP["clip"]], m[hip.HP["value_coeff"]] = self._clip, self._vc
         m[hip.HP["clip_coeff"]], m[hip.HP["ent_coeff"]] = self._cc, self._ec
+        m[hip.HP_DEMO_COEFF], m[hip.HP_DEMO_VALUE_COEFF] = self._demo[1], self._demo[2]
         if np.isnan(m[hip.HP["lr"]]):
             m[hip.HP["lr"]] = 3e-4
         self._hp_on = True
@@ -313,19 +380,21 @@ class PPOLearnerHIP:
         moves it on the device (the value each step used is in the step's stats row), NaN after set_adaptive_lr(None) until
         the next clip_adam / set_hyper supplies one."""
         self._need_hp("hyper")
-        return float(self._hp_host[hip.HP[name]])
+        return float(self._hp_host[hip.HP_INDEX[name]])
 
     def _need_hp(self, what):
         if not self._hp_on:
             raise hip.CadreHipError("%s needs device-hyper mode: call set_device_hyper() first" % what)
 
-    def set_hyper(self, lr=None, clip=None, ent_coeff=None, value_coeff=None, clip_coeff=None, max_grad_norm=None):
+    def set_hyper(self, lr=None, clip=None, ent_coeff=None, value_coeff=None, clip_coeff=None, max_grad_norm=None,
+                  demo_coeff=None, demo_value_coeff=None):
         """New values for the given block fields: the mirror is updated and ONE asynchronous host-to-device copy (of the
         span of fields that changed) is enqueued on the current stream — no synchronisation, no new graph.  Steps enqueued
-        afterwards use the new values.  An explicit lr also resets the KL-adaptive controller's current value."""
+        afterwards use the new values.  An explicit lr also resets the KL-adaptive controller's current value.
+        demo_coeff / demo_value_coeff: the two coefficients of the "ppo+demo" loss (read by cadre_ppo_demo_loss only)."""
         self._need_hp("set_hyper")
         new = dict(lr=lr, clip=clip, ent_coeff=ent_coeff, value_coeff=value_coeff, clip_coeff=clip_coeff,
-                   max_grad_norm=max_grad_norm)
+                   max_grad_norm=max_grad_norm, demo_coeff=demo_coeff, demo_value_coeff=demo_value_coeff)
         idx = []
         for name, v in new.items():
             if v is None:
@@ -333,7 +402,7 @@ class PPOLearnerHIP:
             v = float(v)
             if not np.isfinite(v):
                 raise ValueError("set_hyper: %s=%r" % (name, v))
-            i = hip.HP[name]
+            i = hip.HP_INDEX[name]
             if v != self._hp_host[i]:             # (a NaN mirror entry — lr after the controller — always differs)
                 self._hp_host[i] = v
                 idx.append(i)
@@ -341,6 +410,7 @@ class PPOLearnerHIP:
         m = self._hp_host
         self._clip, self._vc = float(m[hip.HP["clip"]]), float(m[hip.HP["value_coeff"]])
         self._cc, self._ec = float(m[hip.HP["clip_coeff"]]), float(m[hip.HP["ent_coeff"]])
+        self._demo = (self._demo[0], float(m[hip.HP_DEMO_COEFF]), float(m[hip.HP_DEMO_VALUE_COEFF]))
         if any(hip.HP["clip"] <= i <= hip.HP["ent_coeff"] for i in idx):
             self._hp_moved = True
         if idx:
@@ -547,7 +617,7 @@ class PPOLearnerHIP:
                      a_z=(1, 0, cs * B * hid), b_z=(1, 0, zs), c_z=(1, 0, cs * B * NP), s_z=(1, 0, zs), seg=sg)
 
     # ------------------------------------------------------------------ update_policy
-    def update(self, B, inv_b, sorted_rows=False, mlp_grads_ready=None, stats_row=None):
+    def update(self, B, inv_b, sorted_rows=False, mlp_grads_ready=None, stats_row=None, demo_stats_row=None):
         """Forward + loss + backward for the packed minibatch in workspace(B).  Gradients of all 16
         nets are written (not accumulated) into arena.grads.  Returns the device tensor
         losses[3] = (value_loss*vc, action_loss*cc, ent_loss*ec) (agent.py:226-237).
@@ -561,9 +631,13 @@ class PPOLearnerHIP:
         the throttle nets' bucket arena[4 size_L:P0] is final when the step ends (the chief's all_reduce takes it).
         `stats_row` (device float32 [2][stats_fields()], needs set_update_modes(stats=True) or a target_kl): the step's
         diagnostics are copied there after the launch sequence (one device-to-device copy), and the next clip_adam writes its
-        per-model gradient norms into the same row."""
+        per-model gradient norms into the same row.  `demo_stats_row` ("ppo+demo" only; device float32
+        [2][>= hip.BC_STATS_FIELDS]) receives the imitation statistics of the demonstration rows; `stats_row` keeps its
+        meaning there (the diagnostics of the PPO rows)."""
         a = self.a
         bc = self.loss_mode == "bc"
+        if demo_stats_row is not None and self.loss_mode != "ppo+demo":
+            raise hip.CadreHipError("update(demo_stats_row=...) needs set_loss('ppo+demo')")
         if bc:
             self._check_bc_modes()
         if stats_row is not None and not bc and not self._loss_stats():
@@ -575,7 +649,7 @@ class PPOLearnerHIP:
         try:
             if mlp_grads_ready is None:
                 self._run("all", B, inv_b, sorted_rows)
-                return self._stats_out(B, stats_row)
+                return self._stats_out(B, stats_row, demo_stats_row)
             half = (a.Z // 2) * a.size_L
             for part, rng in (("front", (a.P0, a.total)), ("mid", (0, half)), ("back", None)):
                 self._run(part, B, inv_b, sorted_rows)
@@ -586,12 +660,14 @@ class PPOLearnerHIP:
                         mlp_grads_ready(*rng)
                     elif part == "front":                    # (a round-3 style hook without arguments: the MLP bucket only)
                         mlp_grads_ready()
-            return self._stats_out(B, stats_row)
+            return self._stats_out(B, stats_row, demo_stats_row)
         finally:
             self._skip_pack = False                          # (act / get_value outside an update always check the copies)
 
-    def _stats_out(self, B, stats_row):
+    def _stats_out(self, B, stats_row, demo_stats_row=None):
         w = self.workspace(B)
+        if demo_stats_row is not None:
+            demo_stats_row[:, :hip.BC_STATS_FIELDS].copy_(w["demo_stats"])
         if self.loss_mode == "bc":            # the imitation statistics; no gradient norms follow
             if stats_row is not None:
                 stats_row[:, :hip.BC_STATS_FIELDS].copy_(w["bc_stats"])
@@ -677,6 +753,8 @@ class PPOLearnerHIP:
         ord_t = getattr(a, "ord", None)                 # ordinal policy heads: the rank table (static, like every pointer here)
         if front and self.loss_mode == "bc":
             self._bc_launch(w, B, inv_b)                # the imitation loss writes losses, dO3: the rest is indifferent
+        elif front and self.loss_mode == "ppo+demo":
+            self._demo_launch(w, B, inv_b, sorted_rows)  # PPO rows + demonstration rows: two launches, the rest is indifferent
         elif front and ord_t is not None:
             # one entry point for the four modes: hp NULL = by-value scalars, stats row NULL = no diagnostics
             stats = self._loss_stats()

@@ -514,7 +514,9 @@ class CadreAgent(object):
         v, a, e = losses.tolist()
         return v, a, e
 
-    def update_policy_from_storages(self, batches, sync=True, mlp_grads_ready=None, stats_row=None, evaluate=False):
+    def update_policy_from_storages(self, batches, sync=True, mlp_grads_ready=None, stats_row=None, evaluate=False,
+                                    demo=None, demo_stats_row=None, demo_label_smoothing=None, demo_coeff=None,
+                                    demo_value_coeff=None):
         """Fast path of the learner section: `batches` = [(steer_storage, steer_idx, steer_adv,
         throttle_storage, throttle_idx, throttle_adv), ...] one entry per worker (equal sizes).
         Same math as feed_forward_generator -> update_policy, but the minibatch gather writes
@@ -523,7 +525,36 @@ class CadreAgent(object):
         (callable, optional) is invoked between the MLP-tower backward and the LSTM backward, when the
         gradients of arena[P0:] are final (Shared_grad_buffers.reduce_bucket_async starts their all-reduce
         there, beside the LSTM backward).  `stats_row`: as in update_policy.  `evaluate` (imitation loss only, see
-        imitate_from_storages): forward + the evaluation form of the loss on the gathered rows, no gradient."""
+        imitate_from_storages): forward + the evaluation form of the loss on the gathered rows, no gradient.
+        `demo` (DAPG-style mixing): a list of entries of the form DemoSet.batch(idx) returns, each with as many rows as a
+        worker entry.  They are appended to the gather table behind the workers' entries and the step runs the mixed loss
+        (PPOLearnerHIP.set_loss("ppo+demo"), for the duration of the call): total = the PPO loss, each worker's mean summed
+        as always, + demo_coeff * mean over ALL demonstration rows of w CE + demo_value_coeff * 0.5 * mean of w (v - R)^2.
+        The three floats returned are the PPO terms over the PPO rows; the two demo terms stay on the device in
+        learner.workspace(B)["demo_losses"], the imitation statistics go to `demo_stats_row` (device float32
+        [2][>= hip.BC_STATS_FIELDS]); `stats_row` receives the PPO rows' diagnostics.  demo_label_smoothing / demo_coeff /
+        demo_value_coeff: None keeps the learner's current settings (in device-hyper mode the coefficients are the block's)."""
+        if demo:
+            if evaluate:
+                raise ValueError("update_policy_from_storages: demo rows have no evaluation form here (imitate_from_storages(evaluate=True))")
+            lrn = self.learner
+            prev = (lrn.loss_mode, lrn._demo, lrn._demo_rows)
+            n_ppo = len(batches) * batches[0][1].numel()
+            lrn.set_loss("ppo+demo", lrn._demo[0] if demo_label_smoothing is None else demo_label_smoothing,
+                         demo_coeff=demo_coeff, demo_value_coeff=demo_value_coeff)
+            lrn.set_demo_rows(n_ppo)
+            try:
+                return self._update_from_storages(list(batches) + list(demo), sync, mlp_grads_ready, stats_row, False,
+                                                  demo_stats_row)
+            finally:
+                lrn.loss_mode, lrn._demo_rows = prev[0], prev[2]
+                if not lrn.device_hyper:
+                    lrn._demo = prev[1]
+        if demo_stats_row is not None:
+            raise ValueError("update_policy_from_storages: demo_stats_row without demo entries")
+        return self._update_from_storages(batches, sync, mlp_grads_ready, stats_row, evaluate)
+
+    def _update_from_storages(self, batches, sync, mlp_grads_ready, stats_row, evaluate, demo_stats_row=None):
         nW = len(batches)
         Bw = batches[0][1].numel()
         B = nW * Bw
@@ -552,7 +583,8 @@ class CadreAgent(object):
                         hip.ptr(w["actions" + u][hd]), hip.ptr(w["commands" + u][hd]), hip.ptr(w["old_values" + u][hd]),
                         hip.ptr(w["returns" + u][hd]), hip.ptr(w["old_logp" + u][hd]), hip.ptr(w["adv" + u][hd]), st),
                         "cadre_gather_minibatch")
-            return self._finish_update(w, B, nW, srt, sync, mlp_grads_ready, evaluate=evaluate, stats_row=stats_row)
+            return self._finish_update(w, B, nW, srt, sync, mlp_grads_ready, evaluate=evaluate, stats_row=stats_row,
+                                       demo_stats_row=demo_stats_row)
         # ONE gather launch for all workers and both heads: a device table of the storages' pointers (built once per set
         # of storages / advantage tensors) and one host-to-device copy of the 2*nW index vectors
         pairs = [(stor, adv) for (ss, si, sa, ts, ti, ta) in batches for (stor, adv) in ((ss, sa), (ts, ta))]
@@ -587,7 +619,8 @@ class CadreAgent(object):
         stage[1].copy_(stage[0], non_blocking=True)
         stage[2] = torch.cuda.Event()
         stage[2].record()
-        if srt and os.environ.get("CADRE_GATHER_SORTED", "1") != "0":
+        gs = getattr(self, "gather_sorted", None)     # None: CADRE_GATHER_SORTED decides (the default); True / False: this agent's switch
+        if srt and (os.environ.get("CADRE_GATHER_SORTED", "1") != "0" if gs is None else gs):
             # rows sorted by command: gather, stable counting sort and placement in ONE launch (round 6; CADRE_GATHER_SORTED=0:
             # gather into staging rows, then cadre_sort_rows_by_command + cadre_permute_minibatch)
             hip.check(L.cadre_gather_sorted_multi(
@@ -596,16 +629,19 @@ class CadreAgent(object):
                 hip.ptr(w["actions"]), hip.ptr(w["commands"]), hip.ptr(w["old_values"]),
                 hip.ptr(w["returns"]), hip.ptr(w["old_logp"]), hip.ptr(w["adv"]), hip.ptr(w["pos"]), hip.ptr(w["seg"]), st),
                 "cadre_gather_sorted_multi")
-            return self._finish_update(w, B, nW, srt, sync, mlp_grads_ready, evaluate=evaluate, placed=True, stats_row=stats_row)
+            return self._finish_update(w, B, nW, srt, sync, mlp_grads_ready, evaluate=evaluate, placed=True, stats_row=stats_row,
+                                       demo_stats_row=demo_stats_row)
         hip.check(L.cadre_gather_minibatch_multi(
             hip.ptr(table), 2 * nW, s0._ldo, s0.seq_length, s0._ldh, hip.ptr(stage[1]), Bw, a.D, a.D, B,
             hip.ptr(w[Xk]), w[Xk].stride(0), a.DP, hip.ptr(w[hk]), hip.ptr(w[ck]), w[hk].stride(0), a.DP,
             hip.ptr(w["actions" + u]), hip.ptr(w["commands" + u]), hip.ptr(w["old_values" + u]),
             hip.ptr(w["returns" + u]), hip.ptr(w["old_logp" + u]), hip.ptr(w["adv" + u]), st),
             "cadre_gather_minibatch_multi")
-        return self._finish_update(w, B, nW, srt, sync, mlp_grads_ready, evaluate=evaluate, stats_row=stats_row)
+        return self._finish_update(w, B, nW, srt, sync, mlp_grads_ready, evaluate=evaluate, stats_row=stats_row,
+                                       demo_stats_row=demo_stats_row)
 
-    def _finish_update(self, w, B, nW, srt, sync, mlp_grads_ready=None, placed=False, stats_row=None, evaluate=False):
+    def _finish_update(self, w, B, nW, srt, sync, mlp_grads_ready=None, placed=False, stats_row=None, evaluate=False,
+                       demo_stats_row=None):
         """Row sort by command (sorted mode; placed: the gather already put every row at its sorted position), the fused update
         and the loss hand-back."""
         L, st, a = hip.lib(), hip.stream(), self.arena
@@ -623,7 +659,9 @@ class CadreAgent(object):
         if evaluate:                                     # imitate_from_storages(evaluate=True): forward + loss only
             losses, _ = self.learner.bc_evaluate(B, float(nW) / B, sorted_rows=srt, stats_row=stats_row)
             return tuple(losses.tolist()) if sync else losses.clone()
-        losses = self.learner.update(B, float(nW) / B, sorted_rows=srt, mlp_grads_ready=mlp_grads_ready, stats_row=stats_row)
+        # (nW counts the demonstration entries of a mixed step too: nW / B = 1 / rows per worker minibatch either way)
+        kw = {} if demo_stats_row is None else dict(demo_stats_row=demo_stats_row)
+        losses = self.learner.update(B, float(nW) / B, sorted_rows=srt, mlp_grads_ready=mlp_grads_ready, stats_row=stats_row, **kw)
         self.arena.attach_grads(self.model_dict)
         if sync:
             return tuple(losses.tolist())

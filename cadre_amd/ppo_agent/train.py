@@ -310,6 +310,52 @@ def apply_schedules(agent, train_cfg, episode, max_episode=None):
     return vals
 
 
+def demo_mixer(agent, train_cfg, rollout_cfg, rank=0, fused_gather=True):
+    """train_cfg["demo_mix"] (absent / None: None, and nothing runs or is drawn): the DemoMixer of a run that keeps a
+    demonstration term inside every PPO step (cadre_amd.imitation.demo_mix_config for the keys).  The DemoSet is built
+    once, here, before train_cfg.pretrain runs — which shares it when it names the same records and parameters.  With
+    several ranks every rank draws its own rows (`rank` is part of the draw's seed) and the demonstration gradient is summed
+    over the ranks by the all-reduce that sums the PPO gradient."""
+    from ..imitation import demo_mix_config, demo_mixer_from_config
+    cfg = demo_mix_config(_get(train_cfg, "demo_mix"))
+    if cfg is None:
+        return None
+    if not fused_gather:
+        raise ValueError("train_cfg.demo_mix needs fused_gather=True: the demonstration rows enter through the storage "
+                         "gather of update_policy_from_storages, not through the tuple path")
+    return demo_mixer_from_config(agent, cfg, rollout_cfg.gamma, rank)
+
+
+def apply_demo_mix(agent, demo, episode, max_episode):
+    """The demonstration coefficient of `episode` (DemoMixer.coeff through schedule_value) into the learner's device
+    hyper-parameter block, beside apply_schedules: the learner goes to device-hyper mode, so a decaying coefficient replays
+    the captured graphs as they are.  Returns the coefficient set (None without a mixer)."""
+    if demo is None:
+        return None
+    v = schedule_value(demo.coeff, episode, max_episode)
+    agent.learner.set_device_hyper(True)
+    agent.learner.set_hyper(demo_coeff=v, demo_value_coeff=demo.value_coeff)
+    return v
+
+
+def _demo_kw(demo, Bw, episode, step, sec):
+    """Keyword arguments of update_policy_from_storages for step `step` of the section ({} without a mixer)."""
+    if demo is None:
+        return {}
+    kw = dict(demo=demo.entries(Bw, episode, step), demo_label_smoothing=demo.label_smoothing)
+    if sec is not None and sec.demo_rows is not None:
+        kw["demo_stats_row"] = sec.demo_rows[step]
+    return kw
+
+
+def demo_stats_line(episode, stats):
+    """The extra `log_stats` line of a run with train_cfg.demo_mix: the imitation statistics of the demonstration rows,
+    means over the section's steps."""
+    d = stats["demo"]
+    return ("Episode: {}, demo nll: {:.4f}/{:.4f}, demo accuracy: {:.4f}/{:.4f}, demo value error: {:.4f}/{:.4f}").format(
+        episode, d["nll"][0], d["nll"][1], d["accuracy"][0], d["accuracy"][1], d["value_error"][0], d["value_error"][1])
+
+
 def _section_hyper(agent, train_cfg, shared_grad_buffers, in_process_chief, optimizer):
     """Before a learner section: arm the KL-adaptive lr from train_cfg (the adapted lr carries over from the section before
     when the settings are the same).  Returns the lr the section hands to chief_step: the scheduled one when
@@ -337,8 +383,10 @@ class _SectionStats:
     """Device side of a section's diagnostics: one stats row per minibatch step, the explained variance of every storage,
     and the host-side dict filled after the section's single sync."""
 
-    def __init__(self, agent, n_steps, n_storages, consensus_world=0):
+    def __init__(self, agent, n_steps, n_storages, consensus_world=0, demo=False):
         lrn = agent.learner
+        # demonstration mixing: the imitation statistics of every step's demonstration rows
+        self.demo_rows = torch.zeros(n_steps, 2, hip.BC_STATS_FIELDS, device=agent.arena.device) if demo else None
         # rank consensus: the reduced (steer, throttle) approx_kl pair of every step, as cadre_kl_consensus read it
         self.world = consensus_world
         self.gkl = torch.zeros(n_steps, 2, device=agent.arena.device) if consensus_world else None
@@ -359,12 +407,16 @@ class _SectionStats:
     def finish(self, stats, gated, losses=None):
         """One device->host copy of (losses,) rows and explained variances; the host step count follows the device's."""
         parts = ([losses.double().reshape(-1)] if losses is not None else []) + [self.rows.double().reshape(-1), self.ev]
+        if self.demo_rows is not None:
+            parts.append(self.demo_rows.double().mean(0).reshape(-1))
         if self.gkl is not None:
             parts.append(self.gkl.double().reshape(-1))
         host = torch.cat(parts).cpu()
         nl = 0 if losses is None else losses.numel()
         tab = host[nl:nl + self.rows.numel()].view(self.rows.shape)
         ev = host[nl + self.rows.numel():nl + self.rows.numel() + self.ev.numel()].view(-1, 2)
+        o_demo = nl + self.rows.numel() + self.ev.numel()
+        dm = None if self.demo_rows is None else host[o_demo:o_demo + 2 * hip.BC_STATS_FIELDS].view(2, -1).tolist()
         gkl = None if self.gkl is None else host[host.numel() - self.gkl.numel():].view(-1, 2).tolist()
         applied = [bool(r[0, 6] != 0) for r in tab]
         n_applied = sum(applied)
@@ -394,6 +446,9 @@ class _SectionStats:
                          stopped_at_step=None if n_applied == len(applied) else applied.index(False))
             if gkl is not None:
                 stats["consensus_world"] = self.world
+            if dm is not None:                     # means over the section's steps, (steer, throttle)
+                stats["demo"] = dict(accuracy=(dm[0][0], dm[1][0]), nll=(dm[0][1], dm[1][1]), entropy=(dm[0][2], dm[1][2]),
+                                     value_error=(dm[0][3], dm[1][3]), weight=(dm[0][4], dm[1][4]), rows=(dm[0][5], dm[1][5]))
         return None if losses is None else host[:nl].view(losses.shape)
 
 
@@ -422,7 +477,8 @@ def stats_line(episode, stats):
 
 def learner_section(agent, steer_rollout, throttle_rollout, done, train_cfg, shared_grad_buffers,
                     optimizer=None, traffic_light=None, counter=None, shared_model_list=None, in_process_chief=True,
-                    fused_gather=True, losses_on_device=False, step_events=None, stats=None, reward_scaler=None):
+                    fused_gather=True, losses_on_device=False, step_events=None, stats=None, reward_scaler=None,
+                    demo=None, episode=0):
     """train.py:76-110.  Returns (value_loss_list, policy_loss_list, ent_loss_list).
     With `in_process_chief` (one process per GPU) the optimiser step runs right after the gradient
     all-reduce instead of waiting on a separate chief process.  `fused_gather` uses the storage ->
@@ -449,7 +505,13 @@ def learner_section(agent, steer_rollout, throttle_rollout, done, train_cfg, sha
     number of applied steps.
     `reward_scaler` (a ReturnScaler for one environment, single rank only): return-based reward scaling.  With it, or when
     a storage holds time-limit flags, the two storages are finished by RolloutStorage.finish_rollouts (see there);
-    otherwise by today's two compute_returns calls."""
+    otherwise by today's two compute_returns calls.
+    `demo` (a DemoMixer, needs fused_gather) with `episode`: every minibatch step also carries demo.entries(rows per
+    minibatch, episode, step) — the mixed loss of update_policy_from_storages(demo=); `stats` then holds "demo" (accuracy,
+    nll, entropy, value_error, weight, rows as (steer, throttle) means over the section's steps).  A step the KL gate
+    stops skips the demonstration term with the rest of the update."""
+    if demo is not None and not fused_gather:
+        raise ValueError("demo needs fused_gather=True")
     _check_scaler(reward_scaler, shared_grad_buffers, train_cfg)
     tkl = _target_kl(train_cfg, shared_grad_buffers, in_process_chief)
     cons = _consensus_on(train_cfg, shared_grad_buffers, in_process_chief)
@@ -458,12 +520,13 @@ def learner_section(agent, steer_rollout, throttle_rollout, done, train_cfg, sha
     sec = None
     if stats is not None or tkl is not None:
         sec = _SectionStats(agent, train_cfg["ppo_epoch"] * _steps_per_epoch(steer_rollout), 2,
-                            consensus_world=shared_grad_buffers.dist_world() if cons else 0)
+                            consensus_world=shared_grad_buffers.dist_world() if cons else 0,
+                            demo=demo is not None and stats is not None)
         agent.learner.set_update_modes(stats=True, target_kl=tkl, consensus=cons)
     try:
         out = _learner_section(agent, steer_rollout, throttle_rollout, done, train_cfg, shared_grad_buffers, optimizer,
                                traffic_light, counter, shared_model_list, in_process_chief, fused_gather, losses_on_device,
-                               step_events, use_adv_norm, sec, lr, reward_scaler, cons)
+                               step_events, use_adv_norm, sec, lr, reward_scaler, cons, demo, episode)
     finally:
         if sec is not None:
             agent.learner.set_update_modes()
@@ -484,7 +547,7 @@ def learner_section(agent, steer_rollout, throttle_rollout, done, train_cfg, sha
 
 def _learner_section(agent, steer_rollout, throttle_rollout, done, train_cfg, shared_grad_buffers, optimizer, traffic_light,
                      counter, shared_model_list, in_process_chief, fused_gather, losses_on_device, step_events, use_adv_norm,
-                     sec, lr, reward_scaler=None, cons=False):
+                     sec, lr, reward_scaler=None, cons=False, demo=None, episode=0):
     nv_s, nv_t = agent.get_value(done, steer_rollout.get_last(as_tensor=True), throttle_rollout.get_last(as_tensor=True))
     if reward_scaler is not None or steer_rollout._tl_used or throttle_rollout._tl_used:
         steer_adv, throttle_adv = RolloutStorage.finish_rollouts(
@@ -498,6 +561,7 @@ def _learner_section(agent, steer_rollout, throttle_rollout, done, train_cfg, sh
                                                         explained_variance=None if sec is None else sec.ev[1:2])
     dev_losses = []
     vl, pl, el = [], [], []
+    n_step = 0
     # several ranks, CADRE_GRAD_BUCKETS=1: gradient buckets leave as soon as they are final, beside the rest of the backward
     # (Shared_grad_buffers.overlap_hook) — only with the in-process chief, which collects them in chief_step, and only
     # when the agent's nets live in the arena behind `shared_grad_buffers` (a foreign worker arena is ADDED afterwards)
@@ -516,10 +580,11 @@ def _learner_section(agent, steer_rollout, throttle_rollout, done, train_cfg, sh
             if kind == "idx":
                 dev_losses.append(agent.update_policy_from_storages(
                     [(steer_rollout, a, steer_adv, throttle_rollout, b, throttle_adv)], sync=False, mlp_grads_ready=hook,
-                    stats_row=row))
+                    stats_row=row, **_demo_kw(demo, a.numel(), episode, n_step, sec)))
             else:
                 v, p, e = agent.update_policy(a, b, stats_row=row)
                 vl.append(v); pl.append(p); el.append(e)
+            n_step += 1
             if in_process_chief:
                 shared_grad_buffers.add_gradient(agent.model_dict)
                 # (the next writer of the gradient arena is the next fused update, which overwrites every element)
@@ -579,6 +644,7 @@ def train(rank, train_cfg, agent_cfg, env_cfg, rollout_cfg, traffic_light=None, 
         ck = _Checkpointer(env.work_dir, ck_interval, agent, [(steer_rollout, throttle_rollout)])
         if ck_resume is not None:                # (the environment is the caller's: it restarts through reset())
             first_episode = ck.resume(ck_resume)
+    demo = demo_mixer(agent, train_cfg, rollout_cfg, rank)          # (before the warm start, which shares its DemoSet)
     _pretrain(agent, train_cfg, rollout_cfg, shared_grad_buffers, rank, logger, ck_resume, shared_model_list, traffic_light)
     obs = env.reset()
     done = False
@@ -603,16 +669,19 @@ def train(rank, train_cfg, agent_cfg, env_cfg, rollout_cfg, traffic_light=None, 
             recorder.end_episode()
         stats = {} if log_stats else None
         apply_schedules(agent, train_cfg, episode)
+        apply_demo_mix(agent, demo, episode, train_cfg.max_episode)
         vl, pl, el = learner_section(agent, steer_rollout, throttle_rollout, done, train_cfg, shared_grad_buffers,
                                      traffic_light=traffic_light, counter=counter,
                                      shared_model_list=shared_model_list,
                                      in_process_chief=traffic_light is None, stats=stats,   # no chief process -> step in-process
-                                     reward_scaler=agent.reward_scaler)
+                                     reward_scaler=agent.reward_scaler, demo=demo, episode=episode)
         if episode % train_cfg.log_interval == 0 and rank == 0 and logger is not None:
             logger.log("Episode: {}, value loss: {:.4f}, policy loss: {:.4f}, entropy loss: {:.4f}".format(
                 episode, np.mean(vl), np.mean(pl), np.mean(el)))
             if log_stats:
                 logger.log(stats_line(episode, stats))
+                if demo is not None:
+                    logger.log(demo_stats_line(episode, stats))
         if episode % train_cfg.save_interval == 0 and rank == 0:
             agent.save_snapshot(os.path.join(model_dir, "ppo_model_{}.pt".format(episode)))
         if ck is not None:                       # (after the snapshot: building its nn.Modules draws from the generator)
@@ -626,7 +695,7 @@ def train(rank, train_cfg, agent_cfg, env_cfg, rollout_cfg, traffic_light=None, 
 
 # ----------------------------------------------------------------------------- N environments in one process
 def learner_section_multi(agent, rollouts, dones, train_cfg, shared_grad_buffers, optimizer=None, losses_on_device=False,
-                          stats=None, reward_scaler=None):
+                          stats=None, reward_scaler=None, demo=None, episode=0):
     """train.py:76-110 for N workers that share one agent (`num_processes = N` on one GPU, chief.py:13-21 semantics):
     rollouts = [(steer_rollout, throttle_rollout), ...] per worker, dones[i] = worker i's last `done`.  Bootstrap values
     of all workers in one pass (get_values), GAE + advantage normalisation per storage, then for each ppo_epoch and
@@ -640,7 +709,9 @@ def learner_section_multi(agent, rollouts, dones, train_cfg, shared_grad_buffers
     worker, all 2N storages in one launch after their GAE).  The diagnostics of a step are taken over the N workers'
     minibatches with the losses' denominator: like the losses, they are the SUM of the per-worker means.
     The 2N storages are finished by ONE RolloutStorage.finish_rollouts launch (bit-identical to 2N compute_returns calls
-    when no time-limit flag was written and `reward_scaler`, a ReturnScaler for N environments, is None)."""
+    when no time-limit flag was written and `reward_scaler`, a ReturnScaler for N environments, is None).
+    `demo` (a DemoMixer) with `episode`: as in learner_section — demo.blocks entries of one worker minibatch's size behind
+    the N workers' entries of every step."""
     _check_scaler(reward_scaler, shared_grad_buffers, train_cfg)
     tkl = _target_kl(train_cfg, shared_grad_buffers)
     cons = _consensus_on(train_cfg, shared_grad_buffers)
@@ -650,7 +721,8 @@ def learner_section_multi(agent, rollouts, dones, train_cfg, shared_grad_buffers
     sec = None
     if stats is not None or tkl is not None:
         sec = _SectionStats(agent, train_cfg["ppo_epoch"] * _steps_per_epoch(rollouts[0][0]), 2 * len(rollouts),
-                            consensus_world=shared_grad_buffers.dist_world() if cons else 0)
+                            consensus_world=shared_grad_buffers.dist_world() if cons else 0,
+                            demo=demo is not None and stats is not None)
     flat = RolloutStorage.finish_rollouts([x for pair in rollouts for x in pair], [v.detach() for pair in nv for v in pair],
                                           normalise=use_adv_norm, reward_scaler=reward_scaler,
                                           explained_variance=None if sec is None else sec.ev,
@@ -664,8 +736,9 @@ def learner_section_multi(agent, rollouts, dones, train_cfg, shared_grad_buffers
             idx = [(s.sample_indices(), t.sample_indices()) for s, t in rollouts]
             for j in range(len(idx[0][0])):
                 batches = [(s, idx[i][0][j], advs[i][0], t, idx[i][1][j], advs[i][1]) for i, (s, t) in enumerate(rollouts)]
-                dev_losses.append(agent.update_policy_from_storages(batches, sync=False,
-                                                                    stats_row=None if sec is None else sec.next_row()))
+                dev_losses.append(agent.update_policy_from_storages(
+                    batches, sync=False, stats_row=None if sec is None else sec.next_row(),
+                    **_demo_kw(demo, batches[0][1].numel(), episode, len(dev_losses), sec)))
                 shared_grad_buffers.add_gradient(agent.model_dict)
                 chief_step(shared_grad_buffers, optimizer, train_cfg["max_grad_norm"], lr=lr, zero_grads=False)
     finally:
@@ -749,6 +822,7 @@ def train_vec(rank, train_cfg, agent_cfg, env_cfg, rollout_cfg, num_envs, env_cl
         ck = _Checkpointer(envs[0].work_dir, ck_interval, agent, rollouts, callback)
         if ck_resume is not None:                # (the environments are the caller's: they restart through reset())
             first_episode = ck.resume(ck_resume)
+    demo = demo_mixer(agent, train_cfg, rollout_cfg, rank)          # (before the warm start, which shares its DemoSet)
     _pretrain(agent, train_cfg, rollout_cfg, shared_grad_buffers, rank, logger, ck_resume)
     obs = [env.reset() for env in envs]
     dones = [False] * num_envs
@@ -777,13 +851,16 @@ def train_vec(rank, train_cfg, agent_cfg, env_cfg, rollout_cfg, num_envs, env_cl
             callback("rollout", episode=episode, dones=list(dones), **state())
         stats = {} if log_stats else None
         apply_schedules(agent, train_cfg, episode)
+        apply_demo_mix(agent, demo, episode, train_cfg.max_episode)
         vl, pl, el = learner_section_multi(agent, rollouts, dones, train_cfg, shared_grad_buffers, optimizer=optimizer,
-                                           stats=stats, reward_scaler=agent.reward_scaler)
+                                           stats=stats, reward_scaler=agent.reward_scaler, demo=demo, episode=episode)
         if episode % train_cfg.log_interval == 0 and rank == 0 and logger is not None:
             logger.log("Episode: {}, value loss: {:.4f}, policy loss: {:.4f}, entropy loss: {:.4f}".format(
                 episode, np.mean(vl), np.mean(pl), np.mean(el)))
             if log_stats:
                 logger.log(stats_line(episode, stats))
+                if demo is not None:
+                    logger.log(demo_stats_line(episode, stats))
         if episode % train_cfg.save_interval == 0 and rank == 0:
             agent.save_snapshot(os.path.join(model_dir, "ppo_model_{}.pt".format(episode)))
         if ck is not None:                       # (after the snapshot: building its nn.Modules draws from the generator)

@@ -428,7 +428,7 @@ int cadre_grad_norms(const double* norms2, int32_t C, float* stats_row, int32_t 
 /* ---------------------------------------------------------------- device-resident hyper-parameters
  * The hyper-parameter block: a device array of CADRE_HP_FIELDS doubles (8-byte aligned) that the `_hp` entry points read
  * at RUN time, so a captured hipGraph follows whatever the block holds when it is replayed.  Fields past
- * CADRE_HP_LR_FACTOR are reserved and zero.  betas and eps stay by-value arguments.  The block is written by ordinary
+ * CADRE_HP_DEMO_VALUE_COEFF are reserved and zero.  betas and eps stay by-value arguments.  The block is written by ordinary
  * stream-ordered copies from the host, and by the KL-adaptive controller below. */
 #define CADRE_HP_FIELDS 16
 #define CADRE_HP_LR 0
@@ -441,6 +441,10 @@ int cadre_grad_norms(const double* norms2, int32_t C, float* stats_row, int32_t 
 #define CADRE_HP_LR_MIN 7
 #define CADRE_HP_LR_MAX 8
 #define CADRE_HP_LR_FACTOR 9
+/* Two of the reserved fields, read by cadre_ppo_demo_loss only and zero for everyone else: the weight of the demonstration
+ * cross-entropy and of the demonstration rows' value regression.  (Enumerators: the macros above are the ten fields every
+ * `_hp` entry point shares, the list the Python binding's HP table mirrors one to one.) */
+enum { CADRE_HP_DEMO_COEFF = 10, CADRE_HP_DEMO_VALUE_COEFF = 11 };
 /* cadre_ppo_loss / cadre_ppo_loss_stats with clip, value_coeff, clip_coeff, ent_coeff = (float)hp[CADRE_HP_*] (the same
  * kernel bodies, the scalars read once per thread before the row loop; the stats variant uses the same clip for its clip
  * fractions).  Equal values give results bit-identical to the by-value entry points.
@@ -595,6 +599,51 @@ int cadre_bc_loss(const float* logits, int64_t ldl, int64_t l_ns, const float* v
  * pitches are multiples of 4 floats, both bases 16-byte aligned, 532 <= ldo <= 1024.  Rows past T are not touched. */
 int cadre_demo_rows(const float* latent, int64_t ld_lat, int32_t n_frames, const int32_t* window, const double* meas,
                     int32_t T, int32_t S, float* obs, int64_t ldo, void* stream);
+
+/* ---------------------------------------------------------------- demonstration term inside the PPO step (csrc/demo_mix.hip)
+ * cadre_ppo_demo_loss: ONE loss launch for a minibatch that holds PPO rows and demonstration rows (DAPG-style mixing), where
+ * cadre_ppo_loss_ord / cadre_bc_loss stand in the update — the same addressing of logits, values, dlogits and dvalues, the
+ * same grid, the same `scratch` (4 + 6 * ceil(B / 16) floats; arrival counter zero on entry and left zero, partials combined
+ * by the last arriving workgroup in workgroup order: two launches on the same inputs give the same bits), the same `poison`
+ * and the same rank table `ord` (NULL, or ord[h][0] = -1: the plain categorical head).  Sample arrays [2 heads][B].
+ * row_kind int32 [2][B], per head: 0 a PPO row, anything else a demonstration row.
+ *   A PPO row runs exactly the statements of cadre_ppo_loss_ord with clip, value_coeff, clip_coeff, ent_coeff and inv_b
+ *   (1 / rows per worker minibatch); a row with a bad command behaves as there.
+ *   A demonstration row runs the statements of cadre_bc_loss with bc_coeff = demo_coeff, value_coeff = demo_value_coeff, no
+ *   entropy term and inv_bd (1 / demonstration rows per step) for inv_b: its weight w is read from the `adv` slot, its target
+ *   from `returns`, its label from `actions`; old_values and old_logp are not read.  With a command out of range or an action
+ *   outside 0 .. K - 1 (-1: no label for this head) it gets exact zeros in all C nets of the head and adds nothing to any sum.
+ * hp == NULL: every scalar is the by-value argument.  Otherwise clip, value_coeff, clip_coeff, ent_coeff are read from the
+ * block as in cadre_ppo_loss_ord and demo_coeff = (float)hp[CADRE_HP_DEMO_COEFF], demo_value_coeff =
+ * (float)hp[CADRE_HP_DEMO_VALUE_COEFF]; label_smoothing, inv_b and inv_bd stay by value.
+ *   losses[3]      the three PPO terms over the PPO rows only, as cadre_ppo_loss writes them
+ *   demo_losses[2] (demo_coeff sum w ce inv_bd,  demo_value_coeff 0.5 sum w (v - R)^2 inv_bd) over the demonstration rows
+ *   total = losses[0] + losses[1] - losses[2] + demo_losses[0] + demo_losses[1]; dlogits / dvalues are its derivative
+ * stats_row (may be NULL; then F, stats_scratch, target_kl, stop are ignored): the CADRE_PPO_STATS_FIELDS diagnostics of
+ * cadre_ppo_loss_stats per head over the PPO rows ONLY (means with inv_b), followed by the rule of cadre_ppo_loss_stats(_hp):
+ * the target_kl gate, `applied` and with hp the KL-adaptive lr see the policy's KL on its own rollouts, undiluted by
+ * demonstration rows.  stats_scratch: 12 * ceil(B / 16) floats.
+ * demo_stats_row (may be NULL) float [2][demo_F], demo_F >= CADRE_BC_STATS_FIELDS: the six statistics of cadre_bc_loss per head
+ * over the demonstration rows, means with inv_bd.
+ * demo_scratch (always required: the demo sums go through it): 2 * ceil(B / 16) * (2 + CADRE_BC_STATS_FIELDS) floats; it
+ * needs no initialisation.
+ * Refused before any launch: the argument checks of cadre_ppo_loss_ord and cadre_bc_loss, NULL row_kind, NULL demo_losses or
+ * demo_scratch, label_smoothing outside [0, 1), inv_bd not finite or <= 0 while anything needs it (hp != NULL, a non-zero
+ * demo coefficient, or a demo stats row). */
+int cadre_ppo_demo_loss(const float* logits, int64_t ldl, int64_t l_ns, const float* values, int64_t ldv, int64_t v_ns,
+                        const int64_t* actions, const int32_t* commands, const float* old_values, const float* returns,
+                        const float* old_logp, const float* adv, const int32_t* row_kind, int32_t B, int32_t C,
+                        int32_t n_out_steer, int32_t n_out_throttle, double* hp, float clip, float value_coeff,
+                        float clip_coeff, float ent_coeff, float inv_b, float label_smoothing, float demo_coeff,
+                        float demo_value_coeff, float inv_bd, float* losses, float* demo_losses, float* dlogits,
+                        float* dvalues, float* scratch, float* demo_scratch, const int32_t* poison, float* stats_row, int32_t F,
+                        float* stats_scratch, float target_kl, int32_t* stop, float* demo_stats_row, int32_t demo_F,
+                        const int32_t* ord, void* stream);
+/* cadre_mix_row_kinds: row_kind[h][pos[h][u]] = (u >= B_ppo) for both heads — the kinds of a minibatch whose unsorted rows
+ * B_ppo .. B - 1 are the demonstration rows.  pos int32 [2][B]: the sorted position of each unsorted row
+ * (cadre_gather_sorted_multi / cadre_sort_rows_by_command); NULL: the identity (unsorted layout).  A position outside
+ * 0 .. B - 1 writes nothing.  Refused before any launch: NULL row_kind, B < 1, B_ppo outside 0 .. B. */
+int cadre_mix_row_kinds(const int32_t* pos, int32_t B, int32_t B_ppo, int32_t* row_kind, void* stream);
 
 /* ---------------------------------------------------------------- ensemble evaluation (csrc/ensemble.hip)
  * eval.py:53-63 for N environments and M snapshots.  A group of Mg agents (Mg * C <= 16) shares one stacked arena with
