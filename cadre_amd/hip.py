@@ -160,6 +160,13 @@ SYMBOLS = {
     "cadre_ppo_demo_loss": [vp, i64, i64, vp, i64, i64, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, vp, f32, f32, f32, f32,
                             f32, f32, f32, f32, f32, vp, vp, vp, vp, vp, vp, vp, vp, i32, vp, f32, vp, vp, i32, vp, vp],
     "cadre_mix_row_kinds": [vp, i32, i32, vp, vp],
+    # PPG auxiliary phase: logits, ldl, l_ns, commands, pos (NULL: identity), row_id, B, C, K_steer, K_throttle, ord (may be
+    # NULL), table, R, stream / logits, ldl, l_ns, values, ldv, v_ns, commands, returns, pos (NULL: identity), row_id, table, R,
+    # B, C, K_steer, K_throttle, beta_clone, aux_value_coeff, inv_b, losses, dlogits, dvalues, scratch, poison, stats row (may
+    # be NULL), F, stats scratch, ord (may be NULL), stream
+    "cadre_aux_record": [vp, i64, i64, vp, vp, vp, i32, i32, i32, i32, vp, vp, i32, vp],
+    "cadre_aux_loss": [vp, i64, i64, vp, i64, i64, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, f32, f32, f32, vp, vp, vp,
+                       vp, vp, vp, i32, vp, vp, vp],
 }
 # entry points of the A/B build only (include/cadre_hip_ab.h; CADRE_BUILD_AB=1 python -m cadre_amd.build, then
 # CADRE_HIP_LIB=.../libcadre_hip_ab.so): bound when the loaded library has them
@@ -222,6 +229,7 @@ PPO_STATS_LR = 7      # CADRE_PPO_STATS_LR: field of head 0 of a stats row that 
 
 PPO_STATS_FIELDS = 8  # CADRE_PPO_STATS_FIELDS (include/cadre_hip.h): loss diagnostics per head before the gradient norms
 BC_STATS_FIELDS = 6   # CADRE_BC_STATS_FIELDS: accuracy, NLL, entropy, |v - R|, weight sum, rows counted (means over inv_b)
+AUX_STATS_FIELDS = 6  # CADRE_AUX_STATS_FIELDS: mean KL, max KL, mean |v - R|, mean entropy, mean (v - R)^2, rows counted
 
 RS_SCALE, RS_CARRY = 6, 8  # CADRE_RS_SCALE / CADRE_RS_CARRY: the return-statistics block (count, mean, M2 per head first)
 

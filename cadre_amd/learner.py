@@ -111,10 +111,15 @@ class PPOLearnerHIP:
         # "ppo+demo": cadre_ppo_demo_loss — PPO rows and demonstration rows in one minibatch (DAPG-style mixing)
         self._demo = (0.0, 0.0, 0.0)   # (label_smoothing, demo_coeff, demo_value_coeff) of the mixed loss
         self._demo_rows = None     # B_ppo: the leading unsorted rows of the minibatch that are PPO rows (set_demo_rows)
+        # "aux": cadre_aux_loss — the PPG auxiliary phase (critic at full weight, the policy held by a KL term against the
+        # distributions recorded in the table of set_aux_table)
+        self._aux = (1.0, 1.0)     # (beta_clone, aux_value_coeff)
+        self._aux_table = None     # device float32 [2][R][64]; its address and R are part of the hipGraph keys
         hip.lib()
 
     # ------------------------------------------------------------------ loss selection
-    def set_loss(self, mode, label_smoothing=0.0, bc_coeff=1.0, demo_coeff=None, demo_value_coeff=None):
+    def set_loss(self, mode, label_smoothing=0.0, bc_coeff=1.0, demo_coeff=None, demo_value_coeff=None, beta_clone=1.0,
+                 aux_value_coeff=1.0):
         """"ppo" (default): the clipped-surrogate loss.  "bc": behaviour cloning — cross-entropy against the demonstrated bin
         (workspace `actions`; -1 = no label for that head) with `label_smoothing` in [0, 1) and weight `bc_coeff`, the critic
         regressed on workspace `returns`, the learner's own value_coeff / ent_coeff, per-row weights from the `adv` slot;
@@ -126,9 +131,28 @@ class PPOLearnerHIP:
         rank consensus work as in "ppo" and see the PPO rows only; a stopped step skips the whole update, the demonstration
         term included.  In device-hyper mode the two demo coefficients live in the block (set_hyper(demo_coeff=, ...)):
         a changed value needs no new graph.  None keeps the current coefficient.  The demo losses / statistics of a step are
-        in workspace(B)["demo_losses"] / ["demo_stats"]."""
-        if mode not in ("ppo", "bc", "ppo+demo"):
-            raise ValueError("set_loss: mode %r (known: 'ppo', 'bc', 'ppo+demo')" % (mode,))
+        in workspace(B)["demo_losses"] / ["demo_stats"].
+        "aux": the PPG auxiliary loss (cadre_aux_loss) — aux_value_coeff * 0.5 * mean (v - R)^2 + beta_clone * mean
+        KL(pi_old || pi), pi_old read from the table of set_aux_table() at the rows in workspace(B)["aux_rows"] (int64 [2][B]:
+        the table row of each UNSORTED minibatch row; a static tensor the caller fills before the update).  The learner's own
+        value_coeff / ent_coeff / clip are not used; actions, old_values, old_logp and adv are not read.  The two scalars go
+        by value, yet the mode IS available in device-hyper mode: it reads nothing from the block and changes nothing in it
+        (the optimiser step keeps reading lr / max_grad_norm there; the KL-adaptive controller lives in the PPO loss kernel
+        and does not run).  Refused while set_update_modes(stats / target_kl / consensus) is armed.  The statistics of a step
+        (hip.AUX_STATS_FIELDS per head) are in workspace(B)["aux_stats"]."""
+        if mode not in ("ppo", "bc", "ppo+demo", "aux"):
+            raise ValueError("set_loss: mode %r (known: 'ppo', 'bc', 'ppo+demo', 'aux')" % (mode,))
+        if mode == "aux":
+            if any(isinstance(v, bool) for v in (beta_clone, aux_value_coeff)):
+                raise ValueError("set_loss: beta_clone=%r, aux_value_coeff=%r" % (beta_clone, aux_value_coeff))
+            try:
+                beta, avc = float(beta_clone), float(aux_value_coeff)
+            except (TypeError, ValueError):
+                raise ValueError("set_loss: beta_clone=%r, aux_value_coeff=%r" % (beta_clone, aux_value_coeff))
+            if not (np.isfinite(beta) and np.isfinite(avc)):
+                raise ValueError("set_loss: beta_clone=%r, aux_value_coeff=%r" % (beta_clone, aux_value_coeff))
+            self._check_aux_modes()
+            self._aux = (beta, avc)
         if mode == "ppo+demo":
             eps = float(label_smoothing)
             dc = self._demo[1] if demo_coeff is None else float(demo_coeff)
@@ -189,6 +213,63 @@ class PPOLearnerHIP:
                                         hip.ptr(self._stop) if (stats and self.target_kl is not None) else None,
                                         hip.ptr(w["demo_stats"]), hip.BC_STATS_FIELDS, hip.ptr(ord_t), st),
                   "cadre_ppo_demo_loss")
+
+    # ------------------------------------------------------------------ PPG auxiliary phase
+    def set_aux_table(self, table):
+        """The table of recorded distributions the "aux" loss and aux_record work on: device float32 [2][R][64], contiguous
+        (None: forget it).  Its address is baked into captured graphs, so it is part of their key."""
+        if table is not None:
+            if (not table.is_cuda or table.dtype != torch.float32 or table.dim() != 3 or table.shape[0] != 2
+                    or table.shape[2] != 64 or table.shape[1] < 1 or not table.is_contiguous()):
+                raise ValueError("set_aux_table: expected a contiguous device float32 tensor [2][R][64]")
+        self._aux_table = table
+
+    def _check_aux_modes(self):
+        # (self.consensus also covers an adaptive lr armed with consensus=True, which stays on between sections: the
+        #  optimiser step would then decide from a KL no auxiliary step reports)
+        if self.stats or self.target_kl is not None or self.consensus:
+            raise hip.CadreHipError("the auxiliary loss has no PPO diagnostics, KL gate or rank consensus: it runs outside "
+                                    "the learner section (call set_update_modes() first)")
+
+    def _aux_args(self, w, B, sorted_rows):
+        if self._aux_table is None:
+            raise hip.CadreHipError("the 'aux' loss needs set_aux_table(table) first")
+        if "aux_rows" not in w:
+            w["aux_rows"] = torch.zeros(2, B, dtype=torch.int64, device=self.a.device)
+            w["aux_stats"] = torch.zeros(2, hip.AUX_STATS_FIELDS, device=self.a.device)
+            w["aux_scratch"] = torch.zeros(2 * hip.AUX_STATS_FIELDS * ((B + 15) // 16), device=self.a.device)
+        return hip.ptr(w["pos"]) if sorted_rows else None, hip.ptr(w["aux_rows"]), hip.ptr(self._aux_table), self._aux_table.shape[1]
+
+    def _aux_launch(self, w, B, inv_b, sorted_rows):
+        """cadre_aux_loss on the tower outputs in workspace(B): losses[3], the stats row aux_stats [2][AUX_STATS_FIELDS] and
+        dO3 (dlogits and dvalues)."""
+        a, S = self.a, self.S
+        O3, dO3, NP = w["O3"], w["dO3"], a.NP
+        pos, rows, table, R = self._aux_args(w, B, sorted_rows)
+        beta, avc = self._aux
+        ord_t = getattr(a, "ord", None)
+        hip.check(hip.lib().cadre_aux_loss(hip.ptr(O3), NP, 2 * B * NP, hip.ptr(O3[1]), NP, 2 * B * NP, hip.ptr(w["commands"]),
+                                           hip.ptr(w["returns"]), pos, rows, table, R, B, a.C, a.n_out[0], a.n_out[1], beta,
+                                           avc, inv_b, hip.ptr(w["losses"]), hip.ptr(dO3), hip.ptr(dO3[1]),
+                                           hip.ptr(w["loss_scratch"]), hip.ptr(w["sync"][a.Z * S:]), hip.ptr(w["aux_stats"]),
+                                           hip.AUX_STATS_FIELDS, hip.ptr(w["aux_scratch"]), hip.ptr(ord_t), hip.stream()),
+                  "cadre_aux_loss")
+
+    def aux_record(self, B, sorted_rows=False):
+        """Forward only on the packed minibatch in workspace(B) (eagerly, no captured graph: the record pass runs once per
+        phase), then cadre_aux_record: the current policy's normalised log-probabilities of the minibatch rows go to the rows
+        workspace(B)["aux_rows"] of the table (set_aux_table).  No gradient is written, no parameter moves."""
+        if self.loss_mode != "aux":
+            raise hip.CadreHipError("aux_record needs set_loss('aux')")
+        self._check_aux_modes()
+        a = self.a
+        w = self.workspace(B)
+        pos, rows, table, R = self._aux_args(w, B, sorted_rows)
+        self._forward(w, B, (0, 1, a.Z), a.C, seg=w["seg"] if sorted_rows else None, fused_mlp=True)
+        ord_t = getattr(a, "ord", None)
+        hip.check(hip.lib().cadre_aux_record(hip.ptr(w["O3"]), a.NP, 2 * B * a.NP, hip.ptr(w["commands"]), pos, rows, B, a.C,
+                                             a.n_out[0], a.n_out[1], hip.ptr(ord_t), table, R, hip.stream()),
+                  "cadre_aux_record")
 
     def _check_bc_modes(self):
         if self._hp_on:
@@ -307,6 +388,10 @@ class PPOLearnerHIP:
         # block (device-hyper mode: a decaying coefficient replays one graph)
         if self.loss_mode == "ppo+demo":
             key = key + ((("demo", self._demo[0], self._demo_rows) + (() if self._hp_on else self._demo[1:])),)
+        # the auxiliary loss is a mode: both scalars by value, and the table's address and row count, which the graph holds
+        if self.loss_mode == "aux":
+            t = self._aux_table
+            key = key + ((("aux",) + self._aux + ((None, 0) if t is None else (t.data_ptr(), t.shape[1]))),)
         return key
 
     # ------------------------------------------------------------------ device-resident hyper-parameters
@@ -640,7 +725,12 @@ class PPOLearnerHIP:
             raise hip.CadreHipError("update(demo_stats_row=...) needs set_loss('ppo+demo')")
         if bc:
             self._check_bc_modes()
-        if stats_row is not None and not bc and not self._loss_stats():
+        aux = self.loss_mode == "aux"
+        if aux:
+            self._check_aux_modes()
+            if self._aux_table is None:
+                raise hip.CadreHipError("the 'aux' loss needs set_aux_table(table) first")
+        if stats_row is not None and not bc and not aux and not self._loss_stats():
             raise hip.CadreHipError("update(stats_row=...) needs set_update_modes(stats=True) (or a target_kl)")
         # The packed W_hh copies are current iff this learner's own fused optimiser step produced the parameters that are
         # in the arena now (a chief in another process, a broadcast or a checkpoint load change them behind our back: then
@@ -671,6 +761,10 @@ class PPOLearnerHIP:
         if self.loss_mode == "bc":            # the imitation statistics; no gradient norms follow
             if stats_row is not None:
                 stats_row[:, :hip.BC_STATS_FIELDS].copy_(w["bc_stats"])
+            return w["losses"]
+        if self.loss_mode == "aux":           # the auxiliary statistics; no gradient norms follow
+            if stats_row is not None:
+                stats_row[:, :hip.AUX_STATS_FIELDS].copy_(w["aux_stats"])
             return w["losses"]
         self._last_stats = w.get("stats")
         if stats_row is not None:
@@ -755,6 +849,8 @@ class PPOLearnerHIP:
             self._bc_launch(w, B, inv_b)                # the imitation loss writes losses, dO3: the rest is indifferent
         elif front and self.loss_mode == "ppo+demo":
             self._demo_launch(w, B, inv_b, sorted_rows)  # PPO rows + demonstration rows: two launches, the rest is indifferent
+        elif front and self.loss_mode == "aux":
+            self._aux_launch(w, B, inv_b, sorted_rows)  # critic + KL clone against the recorded table: the rest is indifferent
         elif front and ord_t is not None:
             # one entry point for the four modes: hp NULL = by-value scalars, stats row NULL = no diagnostics
             stats = self._loss_stats()

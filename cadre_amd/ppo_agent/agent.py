@@ -567,6 +567,14 @@ class CadreAgent(object):
         if any(b[1].numel() != Bw or b[4].numel() != Bw for b in batches):
             raise ValueError("update_policy_from_storages: every worker's steer and throttle minibatch must have the same "
                              "number of rows (the losses are the sum of per-worker means over equal minibatches)")
+        aux = self.learner.loss_mode == "aux"          # the auxiliary loss / record: the step's indices are its table rows
+        if aux:
+            if nW != 1:
+                raise ValueError("the auxiliary loss takes exactly one gather entry (got %d)" % nW)
+            # a STATIC workspace tensor: the staging ring below hands out a different device pointer each step, and a
+            # captured graph would replay a stale one
+            self.learner._aux_args(w, B, srt)          # (refuses without a table; allocates the tensor)
+            aux_rows = w["aux_rows"]
         s0 = batches[0][0]
         geo = (s0._ldo, s0.seq_length, s0._ldh)
         if any((st_._ldo, st_.seq_length, st_._ldh) != geo for b in batches for st_ in (b[0], b[3])):
@@ -575,6 +583,8 @@ class CadreAgent(object):
             for i, (ss, si, sa, ts, ti, ta) in enumerate(batches):
                 for hd, (stor, idx, adv) in enumerate(((ss, si, sa), (ts, ti, ta))):
                     idx_d = idx.reshape(-1).to(self.device)
+                    if aux:
+                        aux_rows[hd].copy_(idx_d)
                     hip.check(L.cadre_gather_minibatch(
                         hip.ptr(stor._obs), stor._ldo, stor.seq_length, hip.ptr(stor._hn), hip.ptr(stor._cn), stor._ldh,
                         hip.ptr(stor.action), hip.ptr(stor.value_preds), hip.ptr(stor.returns),
@@ -617,6 +627,8 @@ class CadreAgent(object):
             stage[0][2 * i].copy_(si.reshape(-1))
             stage[0][2 * i + 1].copy_(ti.reshape(-1))
         stage[1].copy_(stage[0], non_blocking=True)
+        if aux:
+            aux_rows.copy_(stage[1])                  # (nW = 1: the index pair [steer; throttle] is row_id, head-major)
         stage[2] = torch.cuda.Event()
         stage[2].record()
         gs = getattr(self, "gather_sorted", None)     # None: CADRE_GATHER_SORTED decides (the default); True / False: this agent's switch
@@ -656,6 +668,8 @@ class CadreAgent(object):
                 hip.ptr(w["actions"]), hip.ptr(w["commands"]), hip.ptr(w["old_values"]),
                 hip.ptr(w["returns"]), hip.ptr(w["old_logp"]), hip.ptr(w["adv"]), 2, w["X"].stride(0), w["h0"].stride(0), st),
                 "cadre_permute_minibatch")
+        if evaluate and self.learner.loss_mode == "aux":   # aux_record_from_storages: forward + the record launch only
+            return self.learner.aux_record(B, sorted_rows=srt)
         if evaluate:                                     # imitate_from_storages(evaluate=True): forward + loss only
             losses, _ = self.learner.bc_evaluate(B, float(nW) / B, sorted_rows=srt, stats_row=stats_row)
             return tuple(losses.tolist()) if sync else losses.clone()
@@ -685,6 +699,56 @@ class CadreAgent(object):
             return self.update_policy_from_storages(batches, sync=sync, stats_row=stats_row, evaluate=bool(evaluate))
         finally:
             lrn.loss_mode, lrn._bc = prev[0], prev[1:]
+
+    # ------------------------------------------------------------------ PPG auxiliary phase (cadre_amd.phasic)
+    def _aux_mode(self, table, beta_clone=None, value_coeff=None):
+        """Switch the learner to the auxiliary loss on `table`; returns what `finally` needs to put the old mode back."""
+        lrn = self.learner
+        prev = (lrn.loss_mode, lrn._aux, lrn._aux_table)
+        try:
+            lrn.set_aux_table(table)
+            lrn.set_loss("aux", beta_clone=lrn._aux[0] if beta_clone is None else beta_clone,
+                         aux_value_coeff=lrn._aux[1] if value_coeff is None else value_coeff)
+        except Exception:
+            lrn.loss_mode, lrn._aux, lrn._aux_table = prev
+            raise
+        return prev
+
+    @staticmethod
+    def _aux_entry(entry):
+        if len(entry) != 1:
+            raise ValueError("the auxiliary phase takes exactly one gather entry (got %d): its index pair is the table's row ids"
+                             % len(entry))
+        return list(entry)
+
+    def aux_record_from_storages(self, entry, table):
+        """Record pass of the auxiliary phase: the gather of update_policy_from_storages (sorted or unsorted) for the ONE
+        entry `entry` = [(steer_storage, steer_idx, steer_adv, throttle_storage, throttle_idx, throttle_adv)], the forward,
+        then cadre_aux_record: table[head][idx] <- the current policy's normalised log-probabilities of row idx.  `table`:
+        device float32 [2][R][64] with R >= every index + 1 (AuxBuffer.table).  Nothing moves; the loss mode that was
+        selected before is restored on exit."""
+        batches = self._aux_entry(entry)
+        prev = self._aux_mode(table)
+        lrn = self.learner
+        try:
+            return self._update_from_storages(batches, False, None, None, True)
+        finally:
+            lrn.loss_mode, lrn._aux, lrn._aux_table = prev
+
+    def aux_from_storages(self, entry, table, stats_row=None, sync=True, beta_clone=None, value_coeff=None):
+        """One step of the auxiliary phase on the ONE entry `entry` (as in aux_record_from_storages): the update's launch
+        chain with the loss switched to cadre_aux_loss (PPOLearnerHIP.set_loss("aux")) for the duration of the call —
+        value_coeff * 0.5 * mean (v - R)^2 against storage.returns + beta_clone * mean KL(table row || current policy).
+        Gradients of all 16 nets are in `.grad` afterwards; the caller takes the optimiser step.  beta_clone / value_coeff:
+        None keeps the learner's current settings.  `stats_row`: device float32 [2][>= hip.AUX_STATS_FIELDS] that receives
+        the step's statistics (mean KL, max KL, |v - R|, entropy, (v - R)^2, rows counted).  Returns (value term, KL term, 0)."""
+        batches = self._aux_entry(entry)
+        prev = self._aux_mode(table, beta_clone, value_coeff)
+        lrn = self.learner
+        try:
+            return self._update_from_storages(batches, sync, None, stats_row, False)
+        finally:
+            lrn.loss_mode, lrn._aux, lrn._aux_table = prev
 
     def update_model(self, shared_model_list):
         """agent.py:239-243 (weight pull).  Same arena -> nothing to copy."""

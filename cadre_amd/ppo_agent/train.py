@@ -356,6 +356,40 @@ def demo_stats_line(episode, stats):
         episode, d["nll"][0], d["nll"][1], d["accuracy"][0], d["accuracy"][1], d["value_error"][0], d["value_error"][1])
 
 
+def _aux_runner(agent, train_cfg, shared_grad_buffers, rank, in_process_chief, ck_interval, first_episode,
+                shared_model_list=None):
+    """train_cfg["aux_phase"] (absent / None: None — nothing runs, nothing is allocated, nothing is drawn): the PPG auxiliary
+    phase every `interval` rollouts (cadre_amd.phasic.aux_config for the keys, aux_runner for what is refused at start-up)."""
+    cfg = _get(train_cfg, "aux_phase")
+    if cfg is None:
+        return None
+    if shared_model_list is not None and arena_of(shared_model_list) is not agent.arena:      # (as for train_cfg.pretrain)
+        raise hip.CadreHipError("train_cfg.aux_phase: shared_model_list lives in another parameter arena than the agent's nets; "
+                                "the phase steps the agent's own arena")
+    from ..phasic import aux_runner
+    return aux_runner(agent, cfg, shared_grad_buffers, rank, in_process_chief, ck_interval, first_episode)
+
+
+def _aux_after_section(aux, agent, train_cfg, episode, rollouts, shared_grad_buffers, optimizer, log):
+    """After the learner section of `episode`: its rollouts go to the phase's buffer and, every interval-th episode, the
+    phase runs with the optimiser settings of the section's steps.  Returns the phase's records when it ran, else None."""
+    if aux is None:
+        return None
+    lrn = agent.learner
+    lr = _get(train_cfg, "lr")
+    if lrn.device_hyper and np.isfinite(lrn.hyper("lr")):   # (the block's lr: a schedule's value, or what the section set)
+        lr = lrn.hyper("lr")
+    s0 = rollouts[0][0]
+    return aux.after_section(episode, rollouts, len(rollouts) * (s0.num_steps // s0.mini_batch_num), shared_grad_buffers,
+                             optimizer, train_cfg["max_grad_norm"], lr, log=log)
+
+
+def aux_stats_line(episode, records):
+    """The extra `log_stats` line of an episode whose auxiliary phase ran: first against last epoch."""
+    from ..phasic import aux_summary_line
+    return aux_summary_line(episode, records)
+
+
 def _section_hyper(agent, train_cfg, shared_grad_buffers, in_process_chief, optimizer):
     """Before a learner section: arm the KL-adaptive lr from train_cfg (the adapted lr carries over from the section before
     when the settings are the same).  Returns the lr the section hands to chief_step: the scheduled one when
@@ -646,6 +680,8 @@ def train(rank, train_cfg, agent_cfg, env_cfg, rollout_cfg, traffic_light=None, 
             first_episode = ck.resume(ck_resume)
     demo = demo_mixer(agent, train_cfg, rollout_cfg, rank)          # (before the warm start, which shares its DemoSet)
     _pretrain(agent, train_cfg, rollout_cfg, shared_grad_buffers, rank, logger, ck_resume, shared_model_list, traffic_light)
+    aux = _aux_runner(agent, train_cfg, shared_grad_buffers, rank, traffic_light is None, ck_interval, first_episode,
+                      shared_model_list)
     obs = env.reset()
     done = False
     log_stats = bool(_get(train_cfg, "log_stats", False))
@@ -675,13 +711,19 @@ def train(rank, train_cfg, agent_cfg, env_cfg, rollout_cfg, traffic_light=None, 
                                      shared_model_list=shared_model_list,
                                      in_process_chief=traffic_light is None, stats=stats,   # no chief process -> step in-process
                                      reward_scaler=agent.reward_scaler, demo=demo, episode=episode)
-        if episode % train_cfg.log_interval == 0 and rank == 0 and logger is not None:
+        log_now = episode % train_cfg.log_interval == 0 and rank == 0 and logger is not None
+        # (the auxiliary phase: before the log line, the snapshot and the checkpoint, which then see its result)
+        aux_records = _aux_after_section(aux, agent, train_cfg, episode, [(steer_rollout, throttle_rollout)],
+                                         shared_grad_buffers, None, logger if log_now else None)
+        if log_now:
             logger.log("Episode: {}, value loss: {:.4f}, policy loss: {:.4f}, entropy loss: {:.4f}".format(
                 episode, np.mean(vl), np.mean(pl), np.mean(el)))
             if log_stats:
                 logger.log(stats_line(episode, stats))
                 if demo is not None:
                     logger.log(demo_stats_line(episode, stats))
+                if aux_records:
+                    logger.log(aux_stats_line(episode, aux_records))
         if episode % train_cfg.save_interval == 0 and rank == 0:
             agent.save_snapshot(os.path.join(model_dir, "ppo_model_{}.pt".format(episode)))
         if ck is not None:                       # (after the snapshot: building its nn.Modules draws from the generator)
@@ -781,7 +823,11 @@ def train_vec(rank, train_cfg, agent_cfg, env_cfg, rollout_cfg, num_envs, env_cl
     or before the loop returns; the callback then gets "checkpoint" (episode, path).  train_cfg["resume_from"] (a path):
     after agent, storages, scaler and environments are built, the checkpoint is restored and the loop continues at its
     episode + 1 (schedules see that episode).  Environment state is not part of a checkpoint: the environments are the
-    caller's and restart through reset().  With both keys absent nothing of this runs."""
+    caller's and restart through reset().  With both keys absent nothing of this runs.
+    train_cfg["aux_phase"] (absent / None: nothing runs, is allocated or drawn; single rank only): the PPG auxiliary phase
+    (cadre_amd.phasic) — after every learner section its storages are appended to an AuxBuffer, and after every interval-th
+    episode, before the log line, snapshot and checkpoint, aux_phase runs over the buffer's rows with the section's optimiser
+    settings; checkpoint_interval must be a multiple of the interval."""
     if env_cls is None:
         from env_wrapper import EnvWrapper as env_cls        # needs the CARLA stack (reference env_wrapper.py)
     if logger is None:
@@ -824,6 +870,7 @@ def train_vec(rank, train_cfg, agent_cfg, env_cfg, rollout_cfg, num_envs, env_cl
             first_episode = ck.resume(ck_resume)
     demo = demo_mixer(agent, train_cfg, rollout_cfg, rank)          # (before the warm start, which shares its DemoSet)
     _pretrain(agent, train_cfg, rollout_cfg, shared_grad_buffers, rank, logger, ck_resume)
+    aux = _aux_runner(agent, train_cfg, shared_grad_buffers, rank, True, ck_interval, first_episode)
     obs = [env.reset() for env in envs]
     dones = [False] * num_envs
     log_stats = bool(_get(train_cfg, "log_stats", False))
@@ -854,13 +901,19 @@ def train_vec(rank, train_cfg, agent_cfg, env_cfg, rollout_cfg, num_envs, env_cl
         apply_demo_mix(agent, demo, episode, train_cfg.max_episode)
         vl, pl, el = learner_section_multi(agent, rollouts, dones, train_cfg, shared_grad_buffers, optimizer=optimizer,
                                            stats=stats, reward_scaler=agent.reward_scaler, demo=demo, episode=episode)
-        if episode % train_cfg.log_interval == 0 and rank == 0 and logger is not None:
+        log_now = episode % train_cfg.log_interval == 0 and rank == 0 and logger is not None
+        # (the auxiliary phase: before the log line, the snapshot and the checkpoint, which then see its result)
+        aux_records = _aux_after_section(aux, agent, train_cfg, episode, rollouts, shared_grad_buffers, optimizer,
+                                         logger if log_now else None)
+        if log_now:
             logger.log("Episode: {}, value loss: {:.4f}, policy loss: {:.4f}, entropy loss: {:.4f}".format(
                 episode, np.mean(vl), np.mean(pl), np.mean(el)))
             if log_stats:
                 logger.log(stats_line(episode, stats))
                 if demo is not None:
                     logger.log(demo_stats_line(episode, stats))
+                if aux_records:
+                    logger.log(aux_stats_line(episode, aux_records))
         if episode % train_cfg.save_interval == 0 and rank == 0:
             agent.save_snapshot(os.path.join(model_dir, "ppo_model_{}.pt".format(episode)))
         if ck is not None:                       # (after the snapshot: building its nn.Modules draws from the generator)

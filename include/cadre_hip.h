@@ -645,6 +645,52 @@ int cadre_ppo_demo_loss(const float* logits, int64_t ldl, int64_t l_ns, const fl
  * 0 .. B - 1 writes nothing.  Refused before any launch: NULL row_kind, B < 1, B_ppo outside 0 .. B. */
 int cadre_mix_row_kinds(const int32_t* pos, int32_t B, int32_t B_ppo, int32_t* row_kind, void* stream);
 
+/* ---------------------------------------------------------------- PPG auxiliary phase (csrc/phasic.hip)
+ * Extra critic epochs over the rows of past rollouts, with the policy held by a KL term against its own distributions as
+ * recorded when the phase began (Cobbe et al. 2020, "Phasic Policy Gradient", the shared-trunk variant of section 3.5).
+ * Both entry points address a minibatch through three arrays: commands int32 [2][B] in WORKSPACE order (the possibly
+ * command-sorted layout of the update), pos int32 [2][B] = the workspace position of UNSORTED row u (cadre_gather_sorted_multi /
+ * cadre_sort_rows_by_command; NULL: the identity) and row_id int64 [2][B] = the table row of unsorted row u, head-major.
+ * table float [2][R][64]: per head and buffer row the normalised log-probabilities of the recorded policy, -inf in columns >= K.
+ * One wave per row, 16 rows per workgroup, grid (ceil(B / 16), 2): the layout of cadre_bc_loss.
+ *
+ * cadre_aux_record: for head h and unsorted row u with b = pos[h][u], c = commands[h][b] in 0 .. C - 1 and
+ * r = row_id[h][u] in 0 .. R - 1:   table[h][r][k] = lg_k = x_k - logsumexp(x)   (k < K; -inf for K <= k < 64)
+ * with x the own net's logits at workspace row b (an ordinal head: through ord_logits) and lg formed by exactly the statements
+ * of the loss kernels.  A row with b, c or r out of range writes nothing.  Two rows of one launch with the same r race (both
+ * values are then stored by plain stores; launches in one stream are ordered).  Refused before any launch: NULL logits,
+ * commands, row_id or table, B < 1, C < 1, n_out outside 1 .. 64, ldl < n_out or > 64, R < 1. */
+int cadre_aux_record(const float* logits, int64_t ldl, int64_t l_ns, const int32_t* commands, const int32_t* pos,
+                     const int64_t* row_id, int32_t B, int32_t C, int32_t n_out_steer, int32_t n_out_throttle,
+                     const int32_t* ord, float* table, int32_t R, void* stream);
+/* cadre_aux_loss: the auxiliary loss where cadre_ppo_loss_ord / cadre_bc_loss stand in the update — the same addressing of
+ * logits, values, dlogits and dvalues, the same `scratch` (4 + 6 * ceil(B / 16) floats; arrival counter zero on entry and left
+ * zero, partials combined by the last arriving workgroup in workgroup order: two launches on the same inputs give the same
+ * bits), the same `poison` and rank table `ord`.  returns float [2][B] in workspace order (the critic's regression target).
+ * For head h, a row that counts (b, c, r in range as above), lo = table[h][r], lg / p of the current policy as above and
+ * p_old formed from lo by the statements that form p from lg (max, expf, sum, divide: equal bits in give equal bits out):
+ *   kl_b = sum_k p_old,k (lo_k - lg_k)   (not clamped at zero; a bin with p_old,k == 0 adds nothing)     vl_b = (v - R)^2
+ *   losses[0] = aux_value_coeff 0.5 sum vl_b inv_b   losses[1] = beta_clone sum kl_b inv_b   losses[2] = 0
+ *   (total = losses[0] + losses[1]; a non-zero *poison adds NaN to all three)
+ *   dlogits = beta_clone inv_b (p_k - p_old,k)   in bin space (an ordinal head: through ord_backward)
+ *   dvalues = aux_value_coeff inv_b (v - R)
+ * for the own net; columns >= K and the other C - 1 nets of the head get exact zeros (whole rows of ldl columns).  A row whose
+ * command or row_id is out of range adds nothing and gets exact zeros in all C nets; a row whose position b is out of range is
+ * skipped.  A row recorded by cadre_aux_record from the logits it is trained on has kl_b == 0 and dlogits == 0 exactly.
+ * stats_row (may be NULL) float [2][F], F >= CADRE_AUX_STATS_FIELDS, per head, partials combined in workgroup order:
+ *   0 mean kl_b   1 max kl_b (fmaxf in the same order; 0 when no row counted)   2 mean |v - R|
+ *   3 mean entropy of the current policy   4 mean (v - R)^2   5 rows counted   — the means and field 5 times inv_b, as in
+ *   cadre_bc_loss.  stats_scratch: 2 * ceil(B / 16) * CADRE_AUX_STATS_FIELDS floats.
+ * Refused before any launch: NULL logits, values, commands, returns, row_id, table, losses, dlogits, dvalues or scratch,
+ * B < 1, C < 1, n_out outside 1 .. 64, ldl < n_out or > 64, R < 1, a stats row with F too small or no stats scratch. */
+#define CADRE_AUX_STATS_FIELDS 6
+int cadre_aux_loss(const float* logits, int64_t ldl, int64_t l_ns, const float* values, int64_t ldv, int64_t v_ns,
+                   const int32_t* commands, const float* returns, const int32_t* pos, const int64_t* row_id,
+                   const float* table, int32_t R, int32_t B, int32_t C, int32_t n_out_steer, int32_t n_out_throttle,
+                   float beta_clone, float aux_value_coeff, float inv_b, float* losses, float* dlogits, float* dvalues,
+                   float* scratch, const int32_t* poison, float* stats_row, int32_t F, float* stats_scratch,
+                   const int32_t* ord, void* stream);
+
 /* ---------------------------------------------------------------- ensemble evaluation (csrc/ensemble.hip)
  * eval.py:53-63 for N environments and M snapshots.  A group of Mg agents (Mg * C <= 16) shares one stacked arena with
  * Mg * C commands: agent j's net (head h, command c) is arena net h * Mg * C + j * C + c, and O3 [2 * 2 Mg C][z_str] is
