@@ -167,6 +167,11 @@ SYMBOLS = {
     "cadre_aux_record": [vp, i64, i64, vp, vp, vp, i32, i32, i32, i32, vp, vp, i32, vp],
     "cadre_aux_loss": [vp, i64, i64, vp, i64, i64, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, f32, f32, f32, vp, vp, vp,
                        vp, vp, vp, i32, vp, vp, vp],
+    # sample reuse: logits, ldl, l_ns, values, ldv, v_ns, commands, actions, pos (NULL: identity), row_id, B, C, K_steer,
+    # K_throttle, ord (may be NULL), logp_now, value_now, R, stream / row table, n, T, gamma, gamma_tau, normalise, state (may be
+    # NULL), clip_r, rho_bar, c_bar, stream
+    "cadre_reuse_record": [vp, i64, i64, vp, i64, i64, vp, vp, vp, vp, i32, i32, i32, i32, vp, vp, vp, i32, vp],
+    "cadre_vtrace_multi": [vp, i32, i32, f32, f32, i32, vp, f32, f32, f32, vp],
 }
 # entry points of the A/B build only (include/cadre_hip_ab.h; CADRE_BUILD_AB=1 python -m cadre_amd.build, then
 # CADRE_HIP_LIB=.../libcadre_hip_ab.so): bound when the loaded library has them
@@ -230,8 +235,9 @@ PPO_STATS_LR = 7      # CADRE_PPO_STATS_LR: field of head 0 of a stats row that 
 PPO_STATS_FIELDS = 8  # CADRE_PPO_STATS_FIELDS (include/cadre_hip.h): loss diagnostics per head before the gradient norms
 BC_STATS_FIELDS = 6   # CADRE_BC_STATS_FIELDS: accuracy, NLL, entropy, |v - R|, weight sum, rows counted (means over inv_b)
 AUX_STATS_FIELDS = 6  # CADRE_AUX_STATS_FIELDS: mean KL, max KL, mean |v - R|, mean entropy, mean (v - R)^2, rows counted
+VTRACE_DIAG_FIELDS = 4  # CADRE_VTRACE_DIAG_FIELDS: mean ratio, share truncated, max |log ratio|, effective-sample share
 
-RS_SCALE, RS_CARRY = 6, 8  # CADRE_RS_SCALE / CADRE_RS_CARRY: the return-statistics block (count, mean, M2 per head first)
+RS_SCALE, RS_CARRY = 6, 8 # CADRE_RS_SCALE / CADRE_RS_CARRY: the return-statistics block (count, mean, M2 per head first)
 
 CAPTURE_MAX_RANGES = 65535        # CADRE_CAPTURE_MAX_RANGES
 CAPTURE_BAD_RANGE = 2 ** 64 - 1   # CADRE_CAPTURE_BAD_RANGE: digest slot of a record the launch found malformed

@@ -271,6 +271,33 @@ class PPOLearnerHIP:
                                              a.n_out[0], a.n_out[1], hip.ptr(ord_t), table, R, hip.stream()),
                   "cadre_aux_record")
 
+    # ------------------------------------------------------------------ sample reuse (cadre_amd.reuse)
+    def reuse_record(self, B, logp_now, value_now, sorted_rows=False):
+        """Forward only on the packed minibatch in workspace(B) (eagerly, as aux_record: the record pass runs once per
+        section), then cadre_reuse_record: the current nets' log-probability of each row's stored action and critic output
+        go to rows workspace(B)["reuse_rows"] (int64 [2][B], the table row of each UNSORTED minibatch row) of `logp_now` /
+        `value_now`, device float32 [2][R] (trailing unit dimensions allowed), contiguous.  The forward is the update's own,
+        so a step that gathers the same rows in the same order finds ratio == 1 exactly.  No gradient is written, no
+        parameter moves; the loss mode plays no part."""
+        for t in (logp_now, value_now):
+            if (not t.is_cuda or t.dtype != torch.float32 or t.dim() < 2 or t.shape[0] != 2 or t.shape[1] < 1
+                    or t.numel() != 2 * t.shape[1] or not t.is_contiguous()):
+                raise ValueError("reuse_record: expected contiguous device float32 tables [2][R]")
+        if logp_now.shape[1] != value_now.shape[1]:
+            raise ValueError("reuse_record: logp_now and value_now differ in rows")
+        a = self.a
+        w = self.workspace(B)
+        if "reuse_rows" not in w:
+            raise hip.CadreHipError("reuse_record: workspace(B)['reuse_rows'] is filled by the gather (reuse_record_from_storages)")
+        self._forward(w, B, (0, 1, a.Z), a.C, seg=w["seg"] if sorted_rows else None, fused_mlp=True)
+        O3, NP = w["O3"], a.NP
+        ord_t = getattr(a, "ord", None)
+        hip.check(hip.lib().cadre_reuse_record(hip.ptr(O3), NP, 2 * B * NP, hip.ptr(O3[1]), NP, 2 * B * NP,
+                                               hip.ptr(w["commands"]), hip.ptr(w["actions"]),
+                                               hip.ptr(w["pos"]) if sorted_rows else None, hip.ptr(w["reuse_rows"]), B, a.C,
+                                               a.n_out[0], a.n_out[1], hip.ptr(ord_t), hip.ptr(logp_now), hip.ptr(value_now),
+                                               logp_now.shape[1], hip.stream()), "cadre_reuse_record")
+
     def _check_bc_modes(self):
         if self._hp_on:
             raise hip.CadreHipError("the imitation loss takes its scalars by value: it is not available in device-hyper mode "

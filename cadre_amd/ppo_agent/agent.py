@@ -554,7 +554,7 @@ class CadreAgent(object):
             raise ValueError("update_policy_from_storages: demo_stats_row without demo entries")
         return self._update_from_storages(batches, sync, mlp_grads_ready, stats_row, evaluate)
 
-    def _update_from_storages(self, batches, sync, mlp_grads_ready, stats_row, evaluate, demo_stats_row=None):
+    def _update_from_storages(self, batches, sync, mlp_grads_ready, stats_row, evaluate, demo_stats_row=None, record=None):
         nW = len(batches)
         Bw = batches[0][1].numel()
         B = nW * Bw
@@ -575,6 +575,11 @@ class CadreAgent(object):
             # captured graph would replay a stale one
             self.learner._aux_args(w, B, srt)          # (refuses without a table; allocates the tensor)
             aux_rows = w["aux_rows"]
+        if record is not None:                         # reuse_record_from_storages: the step's indices are the tables' rows
+            aux = True
+            if "reuse_rows" not in w:                  # (static, as aux_rows)
+                w["reuse_rows"] = torch.zeros(2, B, dtype=torch.int64, device=self.device)
+            aux_rows = w["reuse_rows"]
         s0 = batches[0][0]
         geo = (s0._ldo, s0.seq_length, s0._ldh)
         if any((st_._ldo, st_.seq_length, st_._ldh) != geo for b in batches for st_ in (b[0], b[3])):
@@ -594,7 +599,7 @@ class CadreAgent(object):
                         hip.ptr(w["returns" + u][hd]), hip.ptr(w["old_logp" + u][hd]), hip.ptr(w["adv" + u][hd]), st),
                         "cadre_gather_minibatch")
             return self._finish_update(w, B, nW, srt, sync, mlp_grads_ready, evaluate=evaluate, stats_row=stats_row,
-                                       demo_stats_row=demo_stats_row)
+                                       demo_stats_row=demo_stats_row, record=record)
         # ONE gather launch for all workers and both heads: a device table of the storages' pointers (built once per set
         # of storages / advantage tensors) and one host-to-device copy of the 2*nW index vectors
         pairs = [(stor, adv) for (ss, si, sa, ts, ti, ta) in batches for (stor, adv) in ((ss, sa), (ts, ta))]
@@ -642,7 +647,7 @@ class CadreAgent(object):
                 hip.ptr(w["returns"]), hip.ptr(w["old_logp"]), hip.ptr(w["adv"]), hip.ptr(w["pos"]), hip.ptr(w["seg"]), st),
                 "cadre_gather_sorted_multi")
             return self._finish_update(w, B, nW, srt, sync, mlp_grads_ready, evaluate=evaluate, placed=True, stats_row=stats_row,
-                                       demo_stats_row=demo_stats_row)
+                                       demo_stats_row=demo_stats_row, record=record)
         hip.check(L.cadre_gather_minibatch_multi(
             hip.ptr(table), 2 * nW, s0._ldo, s0.seq_length, s0._ldh, hip.ptr(stage[1]), Bw, a.D, a.D, B,
             hip.ptr(w[Xk]), w[Xk].stride(0), a.DP, hip.ptr(w[hk]), hip.ptr(w[ck]), w[hk].stride(0), a.DP,
@@ -650,10 +655,10 @@ class CadreAgent(object):
             hip.ptr(w["returns" + u]), hip.ptr(w["old_logp" + u]), hip.ptr(w["adv" + u]), st),
             "cadre_gather_minibatch_multi")
         return self._finish_update(w, B, nW, srt, sync, mlp_grads_ready, evaluate=evaluate, stats_row=stats_row,
-                                       demo_stats_row=demo_stats_row)
+                                       demo_stats_row=demo_stats_row, record=record)
 
     def _finish_update(self, w, B, nW, srt, sync, mlp_grads_ready=None, placed=False, stats_row=None, evaluate=False,
-                       demo_stats_row=None):
+                       demo_stats_row=None, record=None):
         """Row sort by command (sorted mode; placed: the gather already put every row at its sorted position), the fused update
         and the loss hand-back."""
         L, st, a = hip.lib(), hip.stream(), self.arena
@@ -668,6 +673,8 @@ class CadreAgent(object):
                 hip.ptr(w["actions"]), hip.ptr(w["commands"]), hip.ptr(w["old_values"]),
                 hip.ptr(w["returns"]), hip.ptr(w["old_logp"]), hip.ptr(w["adv"]), 2, w["X"].stride(0), w["h0"].stride(0), st),
                 "cadre_permute_minibatch")
+        if record is not None:                           # reuse_record_from_storages: forward + the record launch only
+            return self.learner.reuse_record(B, record[0], record[1], sorted_rows=srt)
         if evaluate and self.learner.loss_mode == "aux":   # aux_record_from_storages: forward + the record launch only
             return self.learner.aux_record(B, sorted_rows=srt)
         if evaluate:                                     # imitate_from_storages(evaluate=True): forward + loss only
@@ -749,6 +756,18 @@ class CadreAgent(object):
             return self._update_from_storages(batches, sync, None, stats_row, False)
         finally:
             lrn.loss_mode, lrn._aux, lrn._aux_table = prev
+
+    # ------------------------------------------------------------------ sample reuse (cadre_amd.reuse)
+    def reuse_record_from_storages(self, entry, logp_now, value_now):
+        """Record pass of sample reuse: the gather of update_policy_from_storages (sorted or unsorted) for the ONE entry
+        `entry` = [(steer_storage, idx, steer_adv, throttle_storage, idx, throttle_adv)], the update's forward, then
+        cadre_reuse_record: logp_now[head][idx] <- the current policy's log-probability of row idx's stored action,
+        value_now[head][idx] <- the current critic's output.  Tables: device float32 [2][R] with R >= every index + 1
+        (ReuseWindow's).  Nothing moves and the loss mode is not touched."""
+        if len(entry) != 1:
+            raise ValueError("the record pass takes exactly one gather entry (got %d): its index pair is the tables' row ids"
+                             % len(entry))
+        return self._update_from_storages(list(entry), False, None, None, True, record=(logp_now, value_now))
 
     def update_model(self, shared_model_list):
         """agent.py:239-243 (weight pull).  Same arena -> nothing to copy."""

@@ -224,6 +224,13 @@ def _scale_stats(stats, reward_scaler):
         stats["reward_scale"] = tuple(reward_scaler.scale().tolist())
 
 
+def _reuse_stats(stats, reuse):
+    """stats["reuse"] of a section that ran with a window: `filled` and, per head, the mean ratio, truncated share,
+    max |log ratio| and effective-sample share of the refresh, averaged over the stale storages (ReuseWindow.summary)."""
+    if stats is not None and reuse is not None:
+        stats["reuse"] = reuse.summary()
+
+
 # ----------------------------------------------------------------------------- hyper-parameter schedules, KL-adaptive lr
 SCHEDULED = ("lr", "clip", "ent_coeff")
 
@@ -384,6 +391,21 @@ def _aux_after_section(aux, agent, train_cfg, episode, rollouts, shared_grad_buf
                              optimizer, train_cfg["max_grad_norm"], lr, log=log)
 
 
+def _reuse_runner(agent, train_cfg, shared_grad_buffers, rank, in_process_chief, ck_interval, ck_resume,
+                  shared_model_list=None):
+    """train_cfg["sample_reuse"] (absent / None: None — nothing runs, nothing is allocated, nothing is drawn): the last M
+    rollouts ride in every PPO step under V-trace (cadre_amd.reuse.reuse_config for the keys, reuse_runner for what is
+    refused at start-up).  The window is allocated before the first section and appended to after every section."""
+    cfg = _get(train_cfg, "sample_reuse")
+    if cfg is None:
+        return None
+    if shared_model_list is not None and arena_of(shared_model_list) is not agent.arena:      # (as for train_cfg.aux_phase)
+        raise hip.CadreHipError("train_cfg.sample_reuse: shared_model_list lives in another parameter arena than the agent's "
+                                "nets; the record pass evaluates the agent's own arena")
+    from ..reuse import reuse_runner
+    return reuse_runner(agent, cfg, shared_grad_buffers, rank, in_process_chief, True, ck_interval, ck_resume)
+
+
 def aux_stats_line(episode, records):
     """The extra `log_stats` line of an episode whose auxiliary phase ran: first against last epoch."""
     from ..phasic import aux_summary_line
@@ -506,13 +528,16 @@ def stats_line(episode, stats):
         line += ", lr: {:.3e}".format(rows[-1]["lr"])
     if "reward_scale" in stats:                        # reward scaling: the scales the section's scan used
         line += ", reward scale: {:.4e}/{:.4e}".format(*stats["reward_scale"])
+    if "reuse" in stats:                               # sample reuse: the importance weights of the section's refresh
+        from ..reuse import reuse_stats_text
+        line += reuse_stats_text(stats)
     return line
 
 
 def learner_section(agent, steer_rollout, throttle_rollout, done, train_cfg, shared_grad_buffers,
                     optimizer=None, traffic_light=None, counter=None, shared_model_list=None, in_process_chief=True,
                     fused_gather=True, losses_on_device=False, step_events=None, stats=None, reward_scaler=None,
-                    demo=None, episode=0):
+                    demo=None, episode=0, reuse=None):
     """train.py:76-110.  Returns (value_loss_list, policy_loss_list, ent_loss_list).
     With `in_process_chief` (one process per GPU) the optimiser step runs right after the gradient
     all-reduce instead of waiting on a separate chief process.  `fused_gather` uses the storage ->
@@ -543,9 +568,13 @@ def learner_section(agent, steer_rollout, throttle_rollout, done, train_cfg, sha
     `demo` (a DemoMixer, needs fused_gather) with `episode`: every minibatch step also carries demo.entries(rows per
     minibatch, episode, step) — the mixed loss of update_policy_from_storages(demo=); `stats` then holds "demo" (accuracy,
     nll, entropy, value_error, weight, rows as (steer, throttle) means over the section's steps).  A step the KL gate
-    stops skips the demonstration term with the rest of the update."""
+    stops skips the demonstration term with the rest of the update.
+    `reuse` (a cadre_amd.reuse.ReuseWindow for one environment, needs fused_gather and the in-process chief) with
+    `episode`: sample reuse, as in learner_section_multi."""
     if demo is not None and not fused_gather:
         raise ValueError("demo needs fused_gather=True")
+    if reuse is not None and not (fused_gather and in_process_chief):
+        raise ValueError("reuse needs fused_gather=True and the in-process chief")
     _check_scaler(reward_scaler, shared_grad_buffers, train_cfg)
     tkl = _target_kl(train_cfg, shared_grad_buffers, in_process_chief)
     cons = _consensus_on(train_cfg, shared_grad_buffers, in_process_chief)
@@ -560,7 +589,7 @@ def learner_section(agent, steer_rollout, throttle_rollout, done, train_cfg, sha
     try:
         out = _learner_section(agent, steer_rollout, throttle_rollout, done, train_cfg, shared_grad_buffers, optimizer,
                                traffic_light, counter, shared_model_list, in_process_chief, fused_gather, losses_on_device,
-                               step_events, use_adv_norm, sec, lr, reward_scaler, cons, demo, episode)
+                               step_events, use_adv_norm, sec, lr, reward_scaler, cons, demo, episode, reuse)
     finally:
         if sec is not None:
             agent.learner.set_update_modes()
@@ -569,10 +598,12 @@ def learner_section(agent, steer_rollout, throttle_rollout, done, train_cfg, sha
     if losses_on_device:
         sec.finish(stats, tkl is not None)
         _scale_stats(stats, reward_scaler)
+        _reuse_stats(stats, reuse)
         return out
     dev_losses, (vl, pl, el) = out
     host = sec.finish(stats, tkl is not None, losses=torch.stack(dev_losses) if dev_losses else None)
     _scale_stats(stats, reward_scaler)
+    _reuse_stats(stats, reuse)
     if host is not None:
         for v, p, e in host.tolist():
             vl.append(v); pl.append(p); el.append(e)
@@ -581,7 +612,7 @@ def learner_section(agent, steer_rollout, throttle_rollout, done, train_cfg, sha
 
 def _learner_section(agent, steer_rollout, throttle_rollout, done, train_cfg, shared_grad_buffers, optimizer, traffic_light,
                      counter, shared_model_list, in_process_chief, fused_gather, losses_on_device, step_events, use_adv_norm,
-                     sec, lr, reward_scaler=None, cons=False, demo=None, episode=0):
+                     sec, lr, reward_scaler=None, cons=False, demo=None, episode=0, reuse=None):
     nv_s, nv_t = agent.get_value(done, steer_rollout.get_last(as_tensor=True), throttle_rollout.get_last(as_tensor=True))
     if reward_scaler is not None or steer_rollout._tl_used or throttle_rollout._tl_used:
         steer_adv, throttle_adv = RolloutStorage.finish_rollouts(
@@ -593,6 +624,8 @@ def _learner_section(agent, steer_rollout, throttle_rollout, done, train_cfg, sh
                                                   explained_variance=None if sec is None else sec.ev[0:1])
         throttle_adv = throttle_rollout.compute_returns(nv_t.detach(), normalise=use_adv_norm,
                                                         explained_variance=None if sec is None else sec.ev[1:2])
+    if reuse is not None:
+        reuse.refresh(use_adv_norm, reward_scaler)
     dev_losses = []
     vl, pl, el = [], [], []
     n_step = 0
@@ -600,20 +633,21 @@ def _learner_section(agent, steer_rollout, throttle_rollout, done, train_cfg, sh
     # (Shared_grad_buffers.overlap_hook) — only with the in-process chief, which collects them in chief_step, and only
     # when the agent's nets live in the arena behind `shared_grad_buffers` (a foreign worker arena is ADDED afterwards)
     hook = shared_grad_buffers.overlap_hook(arena_of(agent.model_dict)) if in_process_chief else None
-    for _ in range(train_cfg["ppo_epoch"]):
+    for epoch in range(train_cfg["ppo_epoch"]):
         if fused_gather:
             idx_s, idx_t = steer_rollout.sample_indices(), throttle_rollout.sample_indices()   # steer draws first
             steps = [("idx", a, b) for a, b in zip(idx_s, idx_t)]
         else:
             steps = [("tup", a, b) for a, b in zip(steer_rollout.feed_forward_generator(steer_adv),
                                                      throttle_rollout.feed_forward_generator(throttle_adv))]
-        for kind, a, b in steps:
+        for j, (kind, a, b) in enumerate(steps):
             if step_events is not None:
                 step_events.append(torch.cuda.Event(enable_timing=True)); step_events[-1].record()
             row = None if sec is None else sec.next_row()
             if kind == "idx":
+                stale = [] if reuse is None else reuse.entries(episode, epoch, j, a.numel())
                 dev_losses.append(agent.update_policy_from_storages(
-                    [(steer_rollout, a, steer_adv, throttle_rollout, b, throttle_adv)], sync=False, mlp_grads_ready=hook,
+                    [(steer_rollout, a, steer_adv, throttle_rollout, b, throttle_adv)] + stale, sync=False, mlp_grads_ready=hook,
                     stats_row=row, **_demo_kw(demo, a.numel(), episode, n_step, sec)))
             else:
                 v, p, e = agent.update_policy(a, b, stats_row=row)
@@ -682,6 +716,8 @@ def train(rank, train_cfg, agent_cfg, env_cfg, rollout_cfg, traffic_light=None, 
     _pretrain(agent, train_cfg, rollout_cfg, shared_grad_buffers, rank, logger, ck_resume, shared_model_list, traffic_light)
     aux = _aux_runner(agent, train_cfg, shared_grad_buffers, rank, traffic_light is None, ck_interval, first_episode,
                       shared_model_list)
+    reuse = _reuse_runner(agent, train_cfg, shared_grad_buffers, rank, traffic_light is None, ck_interval, ck_resume,
+                          shared_model_list)
     obs = env.reset()
     done = False
     log_stats = bool(_get(train_cfg, "log_stats", False))
@@ -710,11 +746,14 @@ def train(rank, train_cfg, agent_cfg, env_cfg, rollout_cfg, traffic_light=None, 
                                      traffic_light=traffic_light, counter=counter,
                                      shared_model_list=shared_model_list,
                                      in_process_chief=traffic_light is None, stats=stats,   # no chief process -> step in-process
-                                     reward_scaler=agent.reward_scaler, demo=demo, episode=episode)
+                                     reward_scaler=agent.reward_scaler, demo=demo, episode=episode,
+                                     **({} if reuse is None else dict(reuse=reuse.window_for([(steer_rollout, throttle_rollout)]))))
         log_now = episode % train_cfg.log_interval == 0 and rank == 0 and logger is not None
         # (the auxiliary phase: before the log line, the snapshot and the checkpoint, which then see its result)
         aux_records = _aux_after_section(aux, agent, train_cfg, episode, [(steer_rollout, throttle_rollout)],
                                          shared_grad_buffers, None, logger if log_now else None)
+        if reuse is not None:                    # (after the PPG buffer took its copy: the two are independent)
+            reuse.after_section([(steer_rollout, throttle_rollout)], [done])
         if log_now:
             logger.log("Episode: {}, value loss: {:.4f}, policy loss: {:.4f}, entropy loss: {:.4f}".format(
                 episode, np.mean(vl), np.mean(pl), np.mean(el)))
@@ -737,7 +776,7 @@ def train(rank, train_cfg, agent_cfg, env_cfg, rollout_cfg, traffic_light=None, 
 
 # ----------------------------------------------------------------------------- N environments in one process
 def learner_section_multi(agent, rollouts, dones, train_cfg, shared_grad_buffers, optimizer=None, losses_on_device=False,
-                          stats=None, reward_scaler=None, demo=None, episode=0):
+                          stats=None, reward_scaler=None, demo=None, episode=0, reuse=None):
     """train.py:76-110 for N workers that share one agent (`num_processes = N` on one GPU, chief.py:13-21 semantics):
     rollouts = [(steer_rollout, throttle_rollout), ...] per worker, dones[i] = worker i's last `done`.  Bootstrap values
     of all workers in one pass (get_values), GAE + advantage normalisation per storage, then for each ppo_epoch and
@@ -753,7 +792,16 @@ def learner_section_multi(agent, rollouts, dones, train_cfg, shared_grad_buffers
     The 2N storages are finished by ONE RolloutStorage.finish_rollouts launch (bit-identical to 2N compute_returns calls
     when no time-limit flag was written and `reward_scaler`, a ReturnScaler for N environments, is None).
     `demo` (a DemoMixer) with `episode`: as in learner_section — demo.blocks entries of one worker minibatch's size behind
-    the N workers' entries of every step."""
+    the N workers' entries of every step.
+    `reuse` (a cadre_amd.reuse.ReuseWindow for N environments) with `episode`: sample reuse.  After the live storages are
+    finished, reuse.refresh() re-evaluates the window's rows under the current nets and runs the V-trace scan; every step's
+    entries are then the N live ones followed by reuse.entries(episode, epoch, step, rows per minibatch), one per stale
+    storage pair, ahead of any demonstration entries (whose n_ppo counts the stale rows).  Losses and gradients are the SUM
+    over (1 + filled) N per-worker means, the convention above: the gradient scale grows with the window, to which Adam is
+    indifferent up to max_grad_norm, whose clip engages earlier.  approx_kl keeps its meaning (movement within this
+    update: a stale row's old_logp is its log-probability at the start of the update); explained variance and the KL
+    gate are untouched.  `stats` gains "reuse" (see _reuse_stats; one more small device-to-host copy).  The caller appends
+    the section's rollouts to the window afterwards (reuse.append)."""
     _check_scaler(reward_scaler, shared_grad_buffers, train_cfg)
     tkl = _target_kl(train_cfg, shared_grad_buffers)
     cons = _consensus_on(train_cfg, shared_grad_buffers)
@@ -770,14 +818,18 @@ def learner_section_multi(agent, rollouts, dones, train_cfg, shared_grad_buffers
                                           explained_variance=None if sec is None else sec.ev,
                                           **_scaler_consensus(cons, reward_scaler, shared_grad_buffers))
     advs = [(flat[2 * i], flat[2 * i + 1]) for i in range(len(rollouts))]
+    if reuse is not None:
+        reuse.refresh(use_adv_norm, reward_scaler)
     if sec is not None:
         agent.learner.set_update_modes(stats=True, target_kl=tkl, consensus=cons)
     dev_losses = []
     try:
-        for _ in range(train_cfg["ppo_epoch"]):
+        for epoch in range(train_cfg["ppo_epoch"]):
             idx = [(s.sample_indices(), t.sample_indices()) for s, t in rollouts]
             for j in range(len(idx[0][0])):
                 batches = [(s, idx[i][0][j], advs[i][0], t, idx[i][1][j], advs[i][1]) for i, (s, t) in enumerate(rollouts)]
+                if reuse is not None:
+                    batches += reuse.entries(episode, epoch, j, batches[0][1].numel())
                 dev_losses.append(agent.update_policy_from_storages(
                     batches, sync=False, stats_row=None if sec is None else sec.next_row(),
                     **_demo_kw(demo, batches[0][1].numel(), episode, len(dev_losses), sec)))
@@ -790,10 +842,12 @@ def learner_section_multi(agent, rollouts, dones, train_cfg, shared_grad_buffers
     if sec is not None and not losses_on_device:
         host = sec.finish(stats, tkl is not None, losses=losses)
         _scale_stats(stats, reward_scaler)
+        _reuse_stats(stats, reuse)
         return tuple(list(c) for c in zip(*host.tolist()))
     if sec is not None:
         sec.finish(stats, tkl is not None)
         _scale_stats(stats, reward_scaler)
+        _reuse_stats(stats, reuse)
     if losses_on_device:
         return losses
     vl, pl, el = [], [], []
@@ -871,6 +925,7 @@ def train_vec(rank, train_cfg, agent_cfg, env_cfg, rollout_cfg, num_envs, env_cl
     demo = demo_mixer(agent, train_cfg, rollout_cfg, rank)          # (before the warm start, which shares its DemoSet)
     _pretrain(agent, train_cfg, rollout_cfg, shared_grad_buffers, rank, logger, ck_resume)
     aux = _aux_runner(agent, train_cfg, shared_grad_buffers, rank, True, ck_interval, first_episode)
+    reuse = _reuse_runner(agent, train_cfg, shared_grad_buffers, rank, True, ck_interval, ck_resume)
     obs = [env.reset() for env in envs]
     dones = [False] * num_envs
     log_stats = bool(_get(train_cfg, "log_stats", False))
@@ -900,11 +955,14 @@ def train_vec(rank, train_cfg, agent_cfg, env_cfg, rollout_cfg, num_envs, env_cl
         apply_schedules(agent, train_cfg, episode)
         apply_demo_mix(agent, demo, episode, train_cfg.max_episode)
         vl, pl, el = learner_section_multi(agent, rollouts, dones, train_cfg, shared_grad_buffers, optimizer=optimizer,
-                                           stats=stats, reward_scaler=agent.reward_scaler, demo=demo, episode=episode)
+                                           stats=stats, reward_scaler=agent.reward_scaler, demo=demo, episode=episode,
+                                           **({} if reuse is None else dict(reuse=reuse.window_for(rollouts))))
         log_now = episode % train_cfg.log_interval == 0 and rank == 0 and logger is not None
         # (the auxiliary phase: before the log line, the snapshot and the checkpoint, which then see its result)
         aux_records = _aux_after_section(aux, agent, train_cfg, episode, rollouts, shared_grad_buffers, optimizer,
                                          logger if log_now else None)
+        if reuse is not None:                    # (after the PPG buffer took its copy: the two are independent)
+            reuse.after_section(rollouts, dones)
         if log_now:
             logger.log("Episode: {}, value loss: {:.4f}, policy loss: {:.4f}, entropy loss: {:.4f}".format(
                 episode, np.mean(vl), np.mean(pl), np.mean(el)))

@@ -838,6 +838,51 @@ int cadre_insert_rows_tl(const void* dst_table, const int32_t* slot, int32_t n_d
                          int32_t D, int32_t Hd, int32_t T, const float* feat, int64_t ldf, const int64_t* action,
                          const float* logp, const float* value, const float* rm, const int32_t* cmd, void* stream);
 
+/* ---------------------------------------------------------------- sample reuse (csrc/reuse.hip)
+ * The rows of the last few rollouts ride in the PPO step as further worker entries (GePPO, Queeney et al. 2021, with the
+ * V-trace targets of Espeholt et al. 2018).  The GePPO surrogate with rho = pi / mu and clip centre pi_k / mu equals
+ * (pi_k / mu) min(r A, clip(r, 1 - eps, 1 + eps) A) with r = pi / pi_k, so the cadre_ppo_loss* kernels compute it once a stale
+ * row's old_logp is its log-probability under the policy at the start of the update (cadre_reuse_record) and its advantage
+ * carries the truncated weight min(rho_bar, pi_k / mu) (cadre_vtrace_multi).
+ *
+ * cadre_reuse_record: the addressing and grid of cadre_aux_record, plus values (row pitch ldv, net stride v_ns) and actions
+ * int64 [2][B] in workspace order as cadre_ppo_loss reads them.  For head h and unsorted row u with b = pos[h][u],
+ * c = commands[h][b] in 0 .. C - 1 and r = row_id[h][u] in 0 .. R - 1:
+ *   value_now[h][r] = values[net h C + c][b]                              (the same bits)
+ *   logp_now[h][r]  = lg_a = x_a - logsumexp(x),  a = actions[h][b]       (only when a is in 0 .. K - 1)
+ * with x the own net's logits at workspace row b (an ordinal head: through ord_logits) and lg_a formed by exactly the
+ * statements that form lp in the loss kernels: the same logits fed to cadre_ppo_loss* with old_logp := logp_now give
+ * lp - old_logp == 0 and ratio == 1 exactly.  logp_now, value_now: float [2][R].  An action out of range (the bootstrap row of
+ * a storage has none) writes the value only; a row with b, c or r out of range writes nothing.  Two rows of one launch with the
+ * same r race as in cadre_aux_record.  Refused before any launch: NULL logits, values, commands, actions, row_id, logp_now or
+ * value_now, B < 1, C < 1, n_out outside 1 .. 64, ldl < n_out or > 64, ldv < 1, R < 1.
+ *
+ * cadre_vtrace_multi: cadre_gae_multi for stale storages.  row_table: device array of n records of eleven pointers
+ * {rewards [T+1], masks [T+1], time_limits [T+1] or NULL, value_now [T+1], boot_keep [1], behaviour_logp [T], logp_now [T],
+ * returns [T], advantages [T], ratio [T], diag [CADRE_VTRACE_DIAG_FIELDS]}, all f32; storage k belongs to head k & 1.
+ * 2 <= T <= 3000 (five arrays of T + 1 floats in LDS, as cadre_gae_multi).  Rewards are read as cadre_gae_multi reads them
+ * (state, clip_r).  V = value_now with V[T] = boot_keep != 0 ? value_now[T] : 0 (a select; value_now[T] is overwritten with it).
+ * Per row  ratio_t = expf(logp_now[t] - behaviour_logp[t])  (stored),  rho_t = fminf(rho_bar, ratio_t),
+ * cw_t = fminf(c_bar, ratio_t).  For t = T - 1 .. 0, acc = 0 at the start, one rounded fp32 operation per statement, no FMA:
+ *   t1 = gamma V[t+1]   t2 = t1 m[t]   t3 = r[t] + t2   delta = t3 - V[t]   u1 = gamma_tau m[t]
+ *   a2 = u1 acc   A = delta + a2   A = A keep[t]                  (policy advantage: GAE with the V-trace-corrected tail)
+ *   rd = rho_t delta   uc = u1 cw_t   u2 = uc acc   acc = rd + u2   acc = acc keep[t]
+ *   returns[t] = acc + V[t]                                        (the V-trace value target v_s)
+ *   p = A + V[t]   a_t = p - V[t]                                  (the round trip cadre_gae_multi's advantage makes)
+ * The a_t are normalised per storage as cadre_gae_multi normalises (double sums, unbiased std, + 1e-8f; cut rows count), and
+ * the last statement is advantages[t] = a_norm_t rho_t (a_t rho_t with normalise == 0).  With logp_now == behaviour_logp,
+ * rho_bar >= 1 and c_bar >= 1 every factor is exactly 1 and returns, advantages and value_now[T] are cadre_gae_multi's bits.
+ * diag, sums in double, stored as float: 0 mean ratio   1 share of rows with ratio > rho_bar   2 max |logp_now - behaviour_logp|
+ * 3 effective-sample share (sum rho)^2 / (T sum rho^2).
+ * Refused before any launch: what cadre_gae_multi refuses; rho_bar or c_bar not finite or not > 0. */
+#define CADRE_VTRACE_DIAG_FIELDS 4
+int cadre_reuse_record(const float* logits, int64_t ldl, int64_t l_ns, const float* values, int64_t ldv, int64_t v_ns,
+                       const int32_t* commands, const int64_t* actions, const int32_t* pos, const int64_t* row_id, int32_t B,
+                       int32_t C, int32_t n_out_steer, int32_t n_out_throttle, const int32_t* ord, float* logp_now,
+                       float* value_now, int32_t R, void* stream);
+int cadre_vtrace_multi(const void* row_table, int32_t n, int32_t T, float gamma, float gamma_tau, int32_t normalise,
+                       const double* state, float clip_r, float rho_bar, float c_bar, void* stream);
+
 /* ---------------------------------------------------------------- rank consensus (csrc/consensus.hip)
  * Decisions that several data-parallel ranks must take identically.  The caller sums the inputs over the ranks first (one
  * small all-reduce); every rank then runs the same kernel on the same reduced bits.  Sums, not means: R ranks with N workers
