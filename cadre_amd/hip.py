@@ -172,6 +172,17 @@ SYMBOLS = {
     # NULL), clip_r, rho_bar, c_bar, stream
     "cadre_reuse_record": [vp, i64, i64, vp, i64, i64, vp, vp, vp, vp, i32, i32, i32, i32, vp, vp, vp, i32, vp],
     "cadre_vtrace_multi": [vp, i32, i32, f32, f32, i32, vp, f32, f32, f32, vp],
+    # exploration suggestions: events pointer table, slots, codes, n, T, stream / {events, masks, time_limits or 0, suggest}
+    # table, n, T, Z, horizon, stream / suggest pointer table, n_src, idx, Bw, T, pos (NULL: identity), Bt, kind, stream /
+    # logits, ldl, l_ns, values, ldv, v_ns, actions, commands, old_values, returns, old_logp, adv, kind, prior, Z, B, C, K_steer,
+    # K_throttle, hp (may be NULL), clip, value_coeff, clip_coeff, ent_coeff, inv_b, sug_coeff, losses[3], sug_losses[1],
+    # dlogits, dvalues, scratch, suggestion scratch, poison, PPO stats row (may be NULL), F, stats scratch, target_kl, stop,
+    # suggestion stats row (may be NULL), its F, ord, stream
+    "cadre_suggest_note": [vp, vp, vp, i32, i32, vp],
+    "cadre_suggest_mark": [vp, i32, i32, i32, vp, vp],
+    "cadre_suggest_rows": [vp, i32, vp, i32, i32, vp, i32, vp, vp],
+    "cadre_ppo_sug_loss": [vp, i64, i64, vp, i64, i64, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, vp, f32, f32,
+                           f32, f32, f32, f32, vp, vp, vp, vp, vp, vp, vp, vp, i32, vp, f32, vp, vp, i32, vp, vp],
 }
 # entry points of the A/B build only (include/cadre_hip_ab.h; CADRE_BUILD_AB=1 python -m cadre_amd.build, then
 # CADRE_HIP_LIB=.../libcadre_hip_ab.so): bound when the loaded library has them
@@ -230,11 +241,14 @@ HP = dict(lr=0, clip=1, value_coeff=2, clip_coeff=3, ent_coeff=4, max_grad_norm=
 # CADRE_HP_DEMO_VALUE_COEFF of the header); HP_INDEX: every named field, what PPOLearnerHIP.set_hyper looks names up in
 HP_DEMO_COEFF, HP_DEMO_VALUE_COEFF = 10, 11
 HP_INDEX = dict(HP, demo_coeff=HP_DEMO_COEFF, demo_value_coeff=HP_DEMO_VALUE_COEFF)
+# a third reserved field (the enumerator CADRE_HP_SUGGEST_COEFF), read by cadre_ppo_sug_loss only; set_hyper(suggest_coeff=)
+HP_SUGGEST_COEFF = 12
 PPO_STATS_LR = 7      # CADRE_PPO_STATS_LR: field of head 0 of a stats row that cadre_grad_norms_hp fills with the step's lr
 
 PPO_STATS_FIELDS = 8  # CADRE_PPO_STATS_FIELDS (include/cadre_hip.h): loss diagnostics per head before the gradient norms
 BC_STATS_FIELDS = 6   # CADRE_BC_STATS_FIELDS: accuracy, NLL, entropy, |v - R|, weight sum, rows counted (means over inv_b)
 AUX_STATS_FIELDS = 6  # CADRE_AUX_STATS_FIELDS: mean KL, max KL, mean |v - R|, mean entropy, mean (v - R)^2, rows counted
+SUG_STATS_FIELDS = 4  # CADRE_SUG_STATS_FIELDS: marked rows, mean KL over the minibatch, max KL, mean p[prior's mode] over marked rows
 VTRACE_DIAG_FIELDS = 4  # CADRE_VTRACE_DIAG_FIELDS: mean ratio, share truncated, max |log ratio|, effective-sample share
 
 RS_SCALE, RS_CARRY = 6, 8 # CADRE_RS_SCALE / CADRE_RS_CARRY: the return-statistics block (count, mean, M2 per head first)

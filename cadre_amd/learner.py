@@ -115,11 +115,16 @@ class PPOLearnerHIP:
         # distributions recorded in the table of set_aux_table)
         self._aux = (1.0, 1.0)     # (beta_clone, aux_value_coeff)
         self._aux_table = None     # device float32 [2][R][64]; its address and R are part of the hipGraph keys
+        # "ppo+suggest": cadre_ppo_sug_loss — the PPO loss plus KL(pi || prior of the row's terminal event) on marked rows
+        self._sug_coeff = 0.0
+        self._sug_tables = None    # (prior: device float32 [2][Z + 1][64], Z); the address and Z are part of the hipGraph keys
+        self._sug_ord = None       # the rank table of two categorical heads (the entry point wants one), when the arena has none
+        self._last_sug_stats = None  # workspace(B)["sug_stats"] of the "ppo+suggest" update that ran last
         hip.lib()
 
     # ------------------------------------------------------------------ loss selection
     def set_loss(self, mode, label_smoothing=0.0, bc_coeff=1.0, demo_coeff=None, demo_value_coeff=None, beta_clone=1.0,
-                 aux_value_coeff=1.0):
+                 aux_value_coeff=1.0, suggest_coeff=None):
         """"ppo" (default): the clipped-surrogate loss.  "bc": behaviour cloning — cross-entropy against the demonstrated bin
         (workspace `actions`; -1 = no label for that head) with `label_smoothing` in [0, 1) and weight `bc_coeff`, the critic
         regressed on workspace `returns`, the learner's own value_coeff / ent_coeff, per-row weights from the `adv` slot;
@@ -139,9 +144,28 @@ class PPOLearnerHIP:
         by value, yet the mode IS available in device-hyper mode: it reads nothing from the block and changes nothing in it
         (the optimiser step keeps reading lr / max_grad_norm there; the KL-adaptive controller lives in the PPO loss kernel
         and does not run).  Refused while set_update_modes(stats / target_kl / consensus) is armed.  The statistics of a step
-        (hip.AUX_STATS_FIELDS per head) are in workspace(B)["aux_stats"]."""
-        if mode not in ("ppo", "bc", "ppo+demo", "aux"):
-            raise ValueError("set_loss: mode %r (known: 'ppo', 'bc', 'ppo+demo', 'aux')" % (mode,))
+        (hip.AUX_STATS_FIELDS per head) are in workspace(B)["aux_stats"].
+        "ppo+suggest": the clipped-surrogate loss plus, on the rows whose kind in workspace(B)["sug_kind"] (int32 [2][B] in
+        workspace order, a static tensor that cadre_suggest_rows fills before the update) is z >= 1, `suggest_coeff` times
+        KL(pi || prior z of the head) from the table of set_suggest_tables(), the mean taken over the minibatch rows
+        (cadre_ppo_sug_loss, ONE launch).  Diagnostics, the KL gate, the adaptive lr and rank consensus work as in "ppo" and
+        see what they see there.  In device-hyper mode the coefficient lives in the block (set_hyper(suggest_coeff=)): a
+        changed value needs no new graph.  None keeps the current coefficient.  The suggestion loss / statistics of a step
+        (hip.SUG_STATS_FIELDS per head) are in workspace(B)["sug_losses"] / ["sug_stats"]."""
+        if mode not in ("ppo", "bc", "ppo+demo", "aux", "ppo+suggest"):
+            raise ValueError("set_loss: mode %r (known: 'ppo', 'bc', 'ppo+demo', 'aux', 'ppo+suggest')" % (mode,))
+        if mode == "ppo+suggest":
+            if isinstance(suggest_coeff, bool):
+                raise ValueError("set_loss: suggest_coeff=%r" % (suggest_coeff,))
+            try:
+                sc = self._sug_coeff if suggest_coeff is None else float(suggest_coeff)
+            except (TypeError, ValueError):
+                raise ValueError("set_loss: suggest_coeff=%r" % (suggest_coeff,))
+            if not np.isfinite(sc):
+                raise ValueError("set_loss: suggest_coeff=%r" % (suggest_coeff,))
+            self._sug_coeff = sc
+            if self._hp_on:
+                self.set_hyper(suggest_coeff=sc)
         if mode == "aux":
             if any(isinstance(v, bool) for v in (beta_clone, aux_value_coeff)):
                 raise ValueError("set_loss: beta_clone=%r, aux_value_coeff=%r" % (beta_clone, aux_value_coeff))
@@ -213,6 +237,58 @@ class PPOLearnerHIP:
                                         hip.ptr(self._stop) if (stats and self.target_kl is not None) else None,
                                         hip.ptr(w["demo_stats"]), hip.BC_STATS_FIELDS, hip.ptr(ord_t), st),
                   "cadre_ppo_demo_loss")
+
+    # ------------------------------------------------------------------ exploration suggestions
+    def set_suggest_tables(self, prior, Z=None):
+        """The prior table of the "ppo+suggest" loss: device float32 [2][Z + 1][64], contiguous, RAW log-priors in columns < K
+        per (head, kind), row 0 unused (None: forget it).  Z: the number of kinds, 1 .. 8 (None: from the shape).  The
+        table's address is baked into captured graphs, so it is part of their key."""
+        if prior is None:
+            self._sug_tables = None
+            return
+        if (not prior.is_cuda or prior.dtype != torch.float32 or prior.dim() != 3 or prior.shape[0] != 2
+                or prior.shape[2] != 64 or not prior.is_contiguous()):
+            raise ValueError("set_suggest_tables: expected a contiguous device float32 tensor [2][Z + 1][64]")
+        Z = prior.shape[1] - 1 if Z is None else Z
+        if isinstance(Z, bool) or not isinstance(Z, int) or not 1 <= Z <= 8 or prior.shape[1] != Z + 1:
+            raise ValueError("set_suggest_tables: Z=%r with a table of %d rows per head (Z in 1 .. 8, Z + 1 rows)"
+                             % (Z, prior.shape[1]))
+        self._sug_tables = (prior, Z)
+
+    def _sug_ws(self, w, B):
+        """The static tensors of the "ppo+suggest" loss in workspace(B); sug_kind is zeroed once, here."""
+        if "sug_kind" not in w:
+            dev = self.a.device
+            w["sug_kind"] = torch.zeros(2, B, dtype=torch.int32, device=dev)
+            w["sug_losses"] = torch.zeros(1, device=dev)
+            w["sug_stats"] = torch.zeros(2, hip.SUG_STATS_FIELDS, device=dev)
+            w["sug_scratch"] = torch.zeros(2 * 4 * ((B + 15) // 16), device=dev)
+        return w["sug_kind"]
+
+    def _sug_launch(self, w, B, inv_b):
+        """cadre_ppo_sug_loss on the tower outputs in workspace(B), in the place of the PPO loss."""
+        a, S = self.a, self.S
+        O3, dO3, NP = w["O3"], w["dO3"], a.NP
+        if self._sug_tables is None:
+            raise hip.CadreHipError("the 'ppo+suggest' loss needs set_suggest_tables(prior, Z) first")
+        prior, Z = self._sug_tables
+        self._sug_ws(w, B)
+        ord_t = getattr(a, "ord", None)
+        if ord_t is None:
+            if self._sug_ord is None:
+                self._sug_ord = torch.full((2, 64), -1, dtype=torch.int32, device=a.device)
+            ord_t = self._sug_ord
+        stats = self._loss_stats()
+        srow, sscr = self._stats_ws(w, B) if stats else (None, None)
+        hip.check(hip.lib().cadre_ppo_sug_loss(
+            hip.ptr(O3), NP, 2 * B * NP, hip.ptr(O3[1]), NP, 2 * B * NP, hip.ptr(w["actions"]), hip.ptr(w["commands"]),
+            hip.ptr(w["old_values"]), hip.ptr(w["returns"]), hip.ptr(w["old_logp"]), hip.ptr(w["adv"]), hip.ptr(w["sug_kind"]),
+            hip.ptr(prior), Z, B, a.C, a.n_out[0], a.n_out[1], hip.ptr(self._hp) if self._hp_on else None, self.clip, self.vc,
+            self.cc, self.ec, inv_b, self._sug_coeff, hip.ptr(w["losses"]), hip.ptr(w["sug_losses"]), hip.ptr(dO3),
+            hip.ptr(dO3[1]), hip.ptr(w["loss_scratch"]), hip.ptr(w["sug_scratch"]), hip.ptr(w["sync"][a.Z * S:]), hip.ptr(srow),
+            srow.shape[1] if stats else 0, hip.ptr(sscr), self._loss_tkl(),
+            hip.ptr(self._stop) if (stats and self.target_kl is not None) else None, hip.ptr(w["sug_stats"]),
+            hip.SUG_STATS_FIELDS, hip.ptr(ord_t), hip.stream()), "cadre_ppo_sug_loss")
 
     # ------------------------------------------------------------------ PPG auxiliary phase
     def set_aux_table(self, table):
@@ -419,6 +495,12 @@ class PPOLearnerHIP:
         if self.loss_mode == "aux":
             t = self._aux_table
             key = key + ((("aux",) + self._aux + ((None, 0) if t is None else (t.data_ptr(), t.shape[1]))),)
+        # the suggestion loss is a mode: the prior table's address and Z, which the graph holds, and the coefficient unless it
+        # lives in the block
+        if self.loss_mode == "ppo+suggest":
+            t = self._sug_tables
+            key = key + ((("suggest",) + ((None, 0) if t is None else (t[0].data_ptr(), t[1])) +
+                          (() if self._hp_on else (self._sug_coeff,))),)
         return key
 
     # ------------------------------------------------------------------ device-resident hyper-parameters
@@ -467,6 +549,7 @@ class PPOLearnerHIP:
         m[hip.HP["clip"]], m[hip.HP["value_coeff"]] = self._clip, self._vc
         m[hip.HP["clip_coeff"]], m[hip.HP["ent_coeff"]] = self._cc, self._ec
         m[hip.HP_DEMO_COEFF], m[hip.HP_DEMO_VALUE_COEFF] = self._demo[1], self._demo[2]
+        m[hip.HP_SUGGEST_COEFF] = self._sug_coeff
         if np.isnan(m[hip.HP["lr"]]):
             m[hip.HP["lr"]] = 3e-4
         self._hp_on = True
@@ -492,21 +575,23 @@ class PPOLearnerHIP:
         moves it on the device (the value each step used is in the step's stats row), NaN after set_adaptive_lr(None) until
         the next clip_adam / set_hyper supplies one."""
         self._need_hp("hyper")
-        return float(self._hp_host[hip.HP_INDEX[name]])
+        return float(self._hp_host[hip.HP_SUGGEST_COEFF if name == "suggest_coeff" else hip.HP_INDEX[name]])
 
     def _need_hp(self, what):
         if not self._hp_on:
             raise hip.CadreHipError("%s needs device-hyper mode: call set_device_hyper() first" % what)
 
     def set_hyper(self, lr=None, clip=None, ent_coeff=None, value_coeff=None, clip_coeff=None, max_grad_norm=None,
-                  demo_coeff=None, demo_value_coeff=None):
+                  demo_coeff=None, demo_value_coeff=None, suggest_coeff=None):
         """New values for the given block fields: the mirror is updated and ONE asynchronous host-to-device copy (of the
         span of fields that changed) is enqueued on the current stream — no synchronisation, no new graph.  Steps enqueued
         afterwards use the new values.  An explicit lr also resets the KL-adaptive controller's current value.
-        demo_coeff / demo_value_coeff: the two coefficients of the "ppo+demo" loss (read by cadre_ppo_demo_loss only)."""
+        demo_coeff / demo_value_coeff: the two coefficients of the "ppo+demo" loss (read by cadre_ppo_demo_loss only).
+        suggest_coeff: the coefficient of the "ppo+suggest" loss (read by cadre_ppo_sug_loss only)."""
         self._need_hp("set_hyper")
         new = dict(lr=lr, clip=clip, ent_coeff=ent_coeff, value_coeff=value_coeff, clip_coeff=clip_coeff,
-                   max_grad_norm=max_grad_norm, demo_coeff=demo_coeff, demo_value_coeff=demo_value_coeff)
+                   max_grad_norm=max_grad_norm, demo_coeff=demo_coeff, demo_value_coeff=demo_value_coeff,
+                   suggest_coeff=suggest_coeff)
         idx = []
         for name, v in new.items():
             if v is None:
@@ -514,7 +599,7 @@ class PPOLearnerHIP:
             v = float(v)
             if not np.isfinite(v):
                 raise ValueError("set_hyper: %s=%r" % (name, v))
-            i = hip.HP_INDEX[name]
+            i = hip.HP_SUGGEST_COEFF if name == "suggest_coeff" else hip.HP_INDEX[name]
             if v != self._hp_host[i]:             # (a NaN mirror entry — lr after the controller — always differs)
                 self._hp_host[i] = v
                 idx.append(i)
@@ -523,6 +608,7 @@ class PPOLearnerHIP:
         self._clip, self._vc = float(m[hip.HP["clip"]]), float(m[hip.HP["value_coeff"]])
         self._cc, self._ec = float(m[hip.HP["clip_coeff"]]), float(m[hip.HP["ent_coeff"]])
         self._demo = (self._demo[0], float(m[hip.HP_DEMO_COEFF]), float(m[hip.HP_DEMO_VALUE_COEFF]))
+        self._sug_coeff = float(m[hip.HP_SUGGEST_COEFF])
         if any(hip.HP["clip"] <= i <= hip.HP["ent_coeff"] for i in idx):
             self._hp_moved = True
         if idx:
@@ -794,6 +880,8 @@ class PPOLearnerHIP:
                 stats_row[:, :hip.AUX_STATS_FIELDS].copy_(w["aux_stats"])
             return w["losses"]
         self._last_stats = w.get("stats")
+        if self.loss_mode == "ppo+suggest":
+            self._last_sug_stats = w.get("sug_stats")
         if stats_row is not None:
             stats_row.copy_(w["stats"])
             self._norm_row = stats_row
@@ -878,6 +966,8 @@ class PPOLearnerHIP:
             self._demo_launch(w, B, inv_b, sorted_rows)  # PPO rows + demonstration rows: two launches, the rest is indifferent
         elif front and self.loss_mode == "aux":
             self._aux_launch(w, B, inv_b, sorted_rows)  # critic + KL clone against the recorded table: the rest is indifferent
+        elif front and self.loss_mode == "ppo+suggest":
+            self._sug_launch(w, B, inv_b)               # PPO + the event priors on marked rows: the rest is indifferent
         elif front and ord_t is not None:
             # one entry point for the four modes: hp NULL = by-value scalars, stats row NULL = no diagnostics
             stats = self._loss_stats()

@@ -585,6 +585,9 @@ class CadreAgent(object):
         if any((st_._ldo, st_.seq_length, st_._ldh) != geo for b in batches for st_ in (b[0], b[3])):
             # storages of different geometry (feature pitch / window length): one gather launch per storage with its
             # own strides (cadre_gather_minibatch) — the one-launch table below assumes a single geometry
+            if self.learner.loss_mode == "ppo+suggest":
+                raise ValueError("the 'ppo+suggest' loss needs storages of one geometry: the kinds of the minibatch are placed "
+                                 "by one launch beside the one-launch gather")
             for i, (ss, si, sa, ts, ti, ta) in enumerate(batches):
                 for hd, (stor, idx, adv) in enumerate(((ss, si, sa), (ts, ti, ta))):
                     idx_d = idx.reshape(-1).to(self.device)
@@ -634,6 +637,14 @@ class CadreAgent(object):
         stage[1].copy_(stage[0], non_blocking=True)
         if aux:
             aux_rows.copy_(stage[1])                  # (nW = 1: the index pair [steer; throttle] is row_id, head-major)
+        if self.learner.loss_mode == "ppo+suggest" and record is None and not evaluate:
+            # the `suggest` arrays of the step's storages, source by source (0: a storage without marks, e.g. a stale entry
+            # of a ReuseWindow); the launch itself follows the gather / sort, which writes `pos`
+            sptrs = tuple(hip.ptr(getattr(stor, "suggest", None)) or 0 for stor, _ in pairs)
+            stable = cache.get(("suggest",) + sptrs)
+            if stable is None:
+                stable = cache[("suggest",) + sptrs] = torch.tensor(sptrs, dtype=torch.int64).to(self.device)
+            self._suggest_src = (stable, stage[1], Bw, s0.num_steps)
         stage[2] = torch.cuda.Event()
         stage[2].record()
         gs = getattr(self, "gather_sorted", None)     # None: CADRE_GATHER_SORTED decides (the default); True / False: this agent's switch
@@ -675,6 +686,11 @@ class CadreAgent(object):
                 "cadre_permute_minibatch")
         if record is not None:                           # reuse_record_from_storages: forward + the record launch only
             return self.learner.reuse_record(B, record[0], record[1], sorted_rows=srt)
+        if self.learner.loss_mode == "ppo+suggest" and not evaluate:
+            # the kinds of the minibatch's rows into the static workspace tensor the captured loss launch reads
+            stable, idx_d, Bw, T = self._suggest_src
+            hip.check(L.cadre_suggest_rows(hip.ptr(stable), 2 * nW, hip.ptr(idx_d), Bw, T, hip.ptr(w["pos"]) if srt else None, B,
+                                           hip.ptr(self.learner._sug_ws(w, B)), st), "cadre_suggest_rows")
         if evaluate and self.learner.loss_mode == "aux":   # aux_record_from_storages: forward + the record launch only
             return self.learner.aux_record(B, sorted_rows=srt)
         if evaluate:                                     # imitate_from_storages(evaluate=True): forward + loss only

@@ -66,10 +66,34 @@ class RolloutStorage(object):
         self._alloc(device)
         for k, v in old.items():
             getattr(self, k).copy_(v)
+        if getattr(self, "events", None) is not None:        # (exploration suggestions: the two tensors travel along)
+            self.events, self.suggest = self.events.to(device), self.suggest.to(device)
 
-    def insert(self, obs, action, action_log_probs, value_preds, rewards, masks, hidden_state, command, time_limit=False):
-        """storage.py:45-58.  `time_limit`: this row's episode was cut by a step budget, not ended (see finish_rollouts)."""
+    def _event_tensors(self):
+        """`events` int32 [T + 1] (the terminal-event code of each row, 0: none) and `suggest` int32 [T] (the kind
+        cadre_suggest_mark gives each row), allocated the first time an event argument is passed: a storage that never saw
+        one has neither attribute and keeps today's launches and tensors."""
+        if getattr(self, "events", None) is None:
+            self.events = torch.zeros(self.num_steps + 1, dtype=torch.int32, device=self.device)
+            self.suggest = torch.zeros(self.num_steps, dtype=torch.int32, device=self.device)
+        return self.events
+
+    @staticmethod
+    def _event_code(e):
+        if isinstance(e, bool) or not isinstance(e, int) or not 0 <= e < 2 ** 31:
+            raise ValueError("event code %r: expected a small non-negative integer (0: none)" % (e,))
+        return e
+
+    def insert(self, obs, action, action_log_probs, value_preds, rewards, masks, hidden_state, command, time_limit=False,
+               event=0):
+        """storage.py:45-58.  `time_limit`: this row's episode was cut by a step budget, not ended (see finish_rollouts).
+        `event`: the code of the terminal event this row ends with for this head (0: none; see cadre_amd.suggest).  Once a
+        storage has seen a code every insert writes the slot, zeros included: a stale code never survives the cursor's
+        drift."""
         s = self.step
+        event = self._event_code(event)
+        if event or getattr(self, "events", None) is not None:
+            self._event_tensors()[s] = event
         if time_limit or self._tl_used:          # (a storage that never saw a flag keeps the reference's launches)
             self.time_limits[s] = 1.0 if time_limit else 0.0
             self._tl_used = True
@@ -87,14 +111,24 @@ class RolloutStorage(object):
         self.step = (s + 1) % (self.num_steps + 1)
 
     @staticmethod
-    def insert_batch(storages, outputs, rewards, masks, commands, time_limits=None):
+    def insert_batch(storages, outputs, rewards, masks, commands, time_limits=None, events=None):
         """`insert` (storage.py:45-58) of one env step of N environments into their 2N storages in ONE launch
         (cadre_insert_rows; with `time_limits` its twin cadre_insert_rows_tl, which writes the flags in the same launch):
         time_limits = None, or per environment a bool or a (steer, throttle) pair of bools.  storages = [(steer_rollout, throttle_rollout), ...] per environment, outputs = what
         CadreAgent.act_batch returned for them, rewards / masks = [N][2] (steer, throttle) host values, commands = the N
         host-side commands.  The hidden state written is act()'s zeros.  The cursors (and their modulo-(T+1) drift) stay
-        host-side ints, exactly as `insert` keeps them."""
+        host-side ints, exactly as `insert` keeps them.
+        `events` (exploration suggestions): None, or per environment an int code or a (steer, throttle) pair of codes (0:
+        none).  All 2N codes of the step are written by ONE extra launch (cadre_suggest_note), which is not issued when
+        `events` is None and no storage has the tensor."""
         N = len(storages)
+        if events is not None and len(events) != N:
+            raise ValueError("insert_batch: %d storage pairs, %d event codes" % (N, len(events)))
+        ev = None
+        if events is not None:               # (checked before anything is launched)
+            if any(isinstance(e, (tuple, list)) and len(e) != 2 for e in events):
+                raise ValueError("insert_batch: an event entry is an int or a (steer, throttle) pair")
+            ev = [RolloutStorage._event_code(c) for e in events for c in (e if isinstance(e, (tuple, list)) else (e, e))]
         if time_limits is not None and len(time_limits) != N:
             raise ValueError("insert_batch: %d storage pairs, %d time-limit flags" % (N, len(time_limits)))
         if N < 1 or len(outputs) != N or len(rewards) != N or len(masks) != N or len(commands) != N:
@@ -150,6 +184,15 @@ class RolloutStorage(object):
         if tl is not None:
             for s in flat:
                 s._tl_used = True
+        if events is not None or any(getattr(s, "events", None) is not None for s in flat):
+            ev = [0] * (2 * N) if ev is None else ev
+            eptrs = tuple(hip.ptr(s._event_tensors()) for s in flat)
+            etable = tables.get(("events",) + eptrs)
+            if etable is None:
+                etable = tables[("events",) + eptrs] = torch.tensor(eptrs, dtype=torch.int64).to(dev)
+            codes = torch.tensor(ev, dtype=torch.int32).to(dev)
+            hip.check(hip.lib().cadre_suggest_note(hip.ptr(etable), hip.ptr(ints), hip.ptr(codes), 2 * N, s0.num_steps,
+                                                   hip.stream()), "cadre_suggest_note")
         for s in flat:
             s.step = (s.step + 1) % (s.num_steps + 1)
 
@@ -258,6 +301,32 @@ class RolloutStorage(object):
         if explained_variance is not None:
             RolloutStorage.explained_variance(storages, explained_variance)
         return [s.advantages for s in storages]
+
+    _mark_tables = {}
+
+    @staticmethod
+    def mark_suggestions(storages, Z, horizon):
+        """After finish_rollouts / compute_returns: `suggest` of every storage of a section from its `events`, masks and
+        time-limit flags in ONE launch (cadre_suggest_mark; see include/cadre_hip.h for the scan).  storages = the flat list
+        [steer_0, throttle_0, ...] (storage k belongs to head k & 1); horizon = device int32 [2][Z + 1].  A storage that
+        never recorded an event gets its two tensors here (all rows kind 0)."""
+        n = len(storages)
+        s0 = storages[0]
+        if n < 1 or any((s.num_steps, s.device) != (s0.num_steps, s0.device) for s in storages):
+            raise ValueError("mark_suggestions: every storage needs the same num_steps and device")
+        if horizon.dtype != torch.int32 or tuple(horizon.shape) != (2, Z + 1) or not horizon.is_contiguous() or horizon.device != s0.device:
+            raise ValueError("mark_suggestions: horizon must be a contiguous int32 [2][Z + 1] tensor on the storages' device")
+        rows = [[hip.ptr(s._event_tensors()), hip.ptr(s.masks), hip.ptr(s.time_limits) if s._tl_used else 0, hip.ptr(s.suggest)]
+                for s in storages]
+        key = tuple(p for row in rows for p in row)
+        tables = RolloutStorage._mark_tables
+        table = tables.get(key)
+        if table is None:
+            if len(tables) > 16:
+                tables.clear()
+            table = tables[key] = torch.tensor(rows, dtype=torch.int64).to(s0.device)
+        hip.check(hip.lib().cadre_suggest_mark(hip.ptr(table), n, s0.num_steps, Z, hip.ptr(horizon), hip.stream()),
+                  "cadre_suggest_mark")
 
     _ev_tables = {}
 

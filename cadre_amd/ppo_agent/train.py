@@ -345,6 +345,45 @@ def apply_demo_mix(agent, demo, episode, max_episode):
     return v
 
 
+def suggestions(agent, train_cfg, fused_gather=True, ck_interval=None, ck_resume=None):
+    """train_cfg["suggest"] (absent / None: None — nothing runs, nothing is allocated, nothing is drawn): the Suggestions of a
+    run with terminal-event priors in the PPO loss (cadre_amd.suggest.suggest_config for the keys, suggest_runner for what is
+    refused at start-up and why)."""
+    cfg = _get(train_cfg, "suggest")
+    if cfg is None:
+        return None
+    from ..suggest import suggest_runner
+    return suggest_runner(agent, cfg, fused_gather, _get(train_cfg, "demo_mix"), ck_interval, ck_resume)
+
+
+def apply_suggest(agent, suggest, episode, max_episode):
+    """The suggestion coefficient of `episode` (Suggestions.coeff through schedule_value) into the learner's device
+    hyper-parameter block, beside apply_demo_mix: a moving coefficient replays the captured graphs as they are.  Returns
+    the coefficient set (None without suggestions)."""
+    if suggest is None:
+        return None
+    v = schedule_value(suggest.coeff, episode, max_episode)
+    agent.learner.set_device_hyper(True)
+    agent.learner.set_hyper(suggest_coeff=v)
+    return v
+
+
+def _suggest_begin(agent, suggest, storages, stats, steps):
+    """After the storages of a section are finished: the mark launch, then the learner's loss becomes "ppo+suggest" for the
+    section.  Returns the loss mode to restore (None without suggestions)."""
+    if suggest is None:
+        return None
+    suggest.mark(storages)
+    return suggest.begin(agent.learner, steps if stats is not None else 0)
+
+
+def _suggest_stats(stats, suggest):
+    if stats is not None and suggest is not None:
+        summary = suggest.summary()
+        if summary is not None:
+            stats["suggest"] = summary
+
+
 def _demo_kw(demo, Bw, episode, step, sec):
     """Keyword arguments of update_policy_from_storages for step `step` of the section ({} without a mixer)."""
     if demo is None:
@@ -531,13 +570,16 @@ def stats_line(episode, stats):
     if "reuse" in stats:                               # sample reuse: the importance weights of the section's refresh
         from ..reuse import reuse_stats_text
         line += reuse_stats_text(stats)
+    if "suggest" in stats:                             # exploration suggestions: marked rows and the KL towards the priors
+        from ..suggest import suggest_stats_text
+        line += suggest_stats_text(stats)
     return line
 
 
 def learner_section(agent, steer_rollout, throttle_rollout, done, train_cfg, shared_grad_buffers,
                     optimizer=None, traffic_light=None, counter=None, shared_model_list=None, in_process_chief=True,
                     fused_gather=True, losses_on_device=False, step_events=None, stats=None, reward_scaler=None,
-                    demo=None, episode=0, reuse=None):
+                    demo=None, episode=0, reuse=None, suggest=None):
     """train.py:76-110.  Returns (value_loss_list, policy_loss_list, ent_loss_list).
     With `in_process_chief` (one process per GPU) the optimiser step runs right after the gradient
     all-reduce instead of waiting on a separate chief process.  `fused_gather` uses the storage ->
@@ -570,9 +612,13 @@ def learner_section(agent, steer_rollout, throttle_rollout, done, train_cfg, sha
     nll, entropy, value_error, weight, rows as (steer, throttle) means over the section's steps).  A step the KL gate
     stops skips the demonstration term with the rest of the update.
     `reuse` (a cadre_amd.reuse.ReuseWindow for one environment, needs fused_gather and the in-process chief) with
-    `episode`: sample reuse, as in learner_section_multi."""
+    `episode`: sample reuse, as in learner_section_multi.
+    `suggest` (a cadre_amd.suggest.Suggestions, needs fused_gather, excludes `demo`): exploration suggestions, as in
+    learner_section_multi."""
     if demo is not None and not fused_gather:
         raise ValueError("demo needs fused_gather=True")
+    if suggest is not None and (not fused_gather or demo is not None):
+        raise ValueError("suggest needs fused_gather=True and excludes demo (a row carries one kind array)")
     if reuse is not None and not (fused_gather and in_process_chief):
         raise ValueError("reuse needs fused_gather=True and the in-process chief")
     _check_scaler(reward_scaler, shared_grad_buffers, train_cfg)
@@ -589,7 +635,8 @@ def learner_section(agent, steer_rollout, throttle_rollout, done, train_cfg, sha
     try:
         out = _learner_section(agent, steer_rollout, throttle_rollout, done, train_cfg, shared_grad_buffers, optimizer,
                                traffic_light, counter, shared_model_list, in_process_chief, fused_gather, losses_on_device,
-                               step_events, use_adv_norm, sec, lr, reward_scaler, cons, demo, episode, reuse)
+                               step_events, use_adv_norm, sec, lr, reward_scaler, cons, demo, episode, reuse, suggest,
+                               stats)
     finally:
         if sec is not None:
             agent.learner.set_update_modes()
@@ -599,11 +646,13 @@ def learner_section(agent, steer_rollout, throttle_rollout, done, train_cfg, sha
         sec.finish(stats, tkl is not None)
         _scale_stats(stats, reward_scaler)
         _reuse_stats(stats, reuse)
+        _suggest_stats(stats, suggest)
         return out
     dev_losses, (vl, pl, el) = out
     host = sec.finish(stats, tkl is not None, losses=torch.stack(dev_losses) if dev_losses else None)
     _scale_stats(stats, reward_scaler)
     _reuse_stats(stats, reuse)
+    _suggest_stats(stats, suggest)
     if host is not None:
         for v, p, e in host.tolist():
             vl.append(v); pl.append(p); el.append(e)
@@ -612,7 +661,7 @@ def learner_section(agent, steer_rollout, throttle_rollout, done, train_cfg, sha
 
 def _learner_section(agent, steer_rollout, throttle_rollout, done, train_cfg, shared_grad_buffers, optimizer, traffic_light,
                      counter, shared_model_list, in_process_chief, fused_gather, losses_on_device, step_events, use_adv_norm,
-                     sec, lr, reward_scaler=None, cons=False, demo=None, episode=0, reuse=None):
+                     sec, lr, reward_scaler=None, cons=False, demo=None, episode=0, reuse=None, suggest=None, stats=None):
     nv_s, nv_t = agent.get_value(done, steer_rollout.get_last(as_tensor=True), throttle_rollout.get_last(as_tensor=True))
     if reward_scaler is not None or steer_rollout._tl_used or throttle_rollout._tl_used:
         steer_adv, throttle_adv = RolloutStorage.finish_rollouts(
@@ -626,6 +675,20 @@ def _learner_section(agent, steer_rollout, throttle_rollout, done, train_cfg, sh
                                                         explained_variance=None if sec is None else sec.ev[1:2])
     if reuse is not None:
         reuse.refresh(use_adv_norm, reward_scaler)
+    sug_prev = _suggest_begin(agent, suggest, [steer_rollout, throttle_rollout], stats,
+                              train_cfg["ppo_epoch"] * _steps_per_epoch(steer_rollout))
+    try:
+        return _learner_steps(agent, steer_rollout, throttle_rollout, steer_adv, throttle_adv, train_cfg, shared_grad_buffers,
+                              optimizer, traffic_light, counter, shared_model_list, in_process_chief, fused_gather,
+                              losses_on_device, step_events, sec, lr, demo, episode, reuse, suggest)
+    finally:
+        if suggest is not None:
+            agent.learner.loss_mode = sug_prev
+
+
+def _learner_steps(agent, steer_rollout, throttle_rollout, steer_adv, throttle_adv, train_cfg, shared_grad_buffers, optimizer,
+                   traffic_light, counter, shared_model_list, in_process_chief, fused_gather, losses_on_device, step_events, sec,
+                   lr, demo, episode, reuse, suggest):
     dev_losses = []
     vl, pl, el = [], [], []
     n_step = 0
@@ -649,6 +712,8 @@ def _learner_section(agent, steer_rollout, throttle_rollout, done, train_cfg, sh
                 dev_losses.append(agent.update_policy_from_storages(
                     [(steer_rollout, a, steer_adv, throttle_rollout, b, throttle_adv)] + stale, sync=False, mlp_grads_ready=hook,
                     stats_row=row, **_demo_kw(demo, a.numel(), episode, n_step, sec)))
+                if suggest is not None:
+                    suggest.collect(agent.learner)
             else:
                 v, p, e = agent.update_policy(a, b, stats_row=row)
                 vl.append(v); pl.append(p); el.append(e)
@@ -712,6 +777,7 @@ def train(rank, train_cfg, agent_cfg, env_cfg, rollout_cfg, traffic_light=None, 
         ck = _Checkpointer(env.work_dir, ck_interval, agent, [(steer_rollout, throttle_rollout)])
         if ck_resume is not None:                # (the environment is the caller's: it restarts through reset())
             first_episode = ck.resume(ck_resume)
+    suggest = suggestions(agent, train_cfg, True, ck_interval, ck_resume)      # (refusals first: before anything is loaded)
     demo = demo_mixer(agent, train_cfg, rollout_cfg, rank)          # (before the warm start, which shares its DemoSet)
     _pretrain(agent, train_cfg, rollout_cfg, shared_grad_buffers, rank, logger, ck_resume, shared_model_list, traffic_light)
     aux = _aux_runner(agent, train_cfg, shared_grad_buffers, rank, traffic_light is None, ck_interval, first_episode,
@@ -731,10 +797,13 @@ def train(rank, train_cfg, agent_cfg, env_cfg, rollout_cfg, traffic_light=None, 
             if recorder is not None:            # cadre_amd.replay.RolloutRecorder
                 recorder.step(raw, action, alp, values, reward, ad)
             tl = _time_limit_pair(info.get("time_limit", False))        # (key absent: no flag is ever written)
+            ev = ({}, {}) if suggest is None else tuple(dict(event=c) for c in suggest.codes(info))   # (key absent: today's call)
             steer_rollout.insert(feat, action[0], alp[0], values[0], reward[0],
-                                 torch.tensor([[0.0] if ad[0] else [1.0]]), hidden, command, time_limit=tl[0])
+                                 torch.tensor([[0.0] if ad[0] else [1.0]]), hidden, command, time_limit=tl[0],
+                                 **ev[0])
             throttle_rollout.insert(feat, action[1], alp[1], values[1], reward[1],
-                                    torch.tensor([[0.0] if ad[1] else [1.0]]), hidden, command, time_limit=tl[1])
+                                    torch.tensor([[0.0] if ad[1] else [1.0]]), hidden, command, time_limit=tl[1],
+                                    **ev[1])
             if done:
                 obs = env.reset()
         if recorder is not None:
@@ -742,12 +811,14 @@ def train(rank, train_cfg, agent_cfg, env_cfg, rollout_cfg, traffic_light=None, 
         stats = {} if log_stats else None
         apply_schedules(agent, train_cfg, episode)
         apply_demo_mix(agent, demo, episode, train_cfg.max_episode)
+        apply_suggest(agent, suggest, episode, train_cfg.max_episode)
         vl, pl, el = learner_section(agent, steer_rollout, throttle_rollout, done, train_cfg, shared_grad_buffers,
                                      traffic_light=traffic_light, counter=counter,
                                      shared_model_list=shared_model_list,
                                      in_process_chief=traffic_light is None, stats=stats,   # no chief process -> step in-process
                                      reward_scaler=agent.reward_scaler, demo=demo, episode=episode,
-                                     **({} if reuse is None else dict(reuse=reuse.window_for([(steer_rollout, throttle_rollout)]))))
+                                     **({} if reuse is None else dict(reuse=reuse.window_for([(steer_rollout, throttle_rollout)]))),
+                                     **({} if suggest is None else dict(suggest=suggest)))
         log_now = episode % train_cfg.log_interval == 0 and rank == 0 and logger is not None
         # (the auxiliary phase: before the log line, the snapshot and the checkpoint, which then see its result)
         aux_records = _aux_after_section(aux, agent, train_cfg, episode, [(steer_rollout, throttle_rollout)],
@@ -776,7 +847,7 @@ def train(rank, train_cfg, agent_cfg, env_cfg, rollout_cfg, traffic_light=None, 
 
 # ----------------------------------------------------------------------------- N environments in one process
 def learner_section_multi(agent, rollouts, dones, train_cfg, shared_grad_buffers, optimizer=None, losses_on_device=False,
-                          stats=None, reward_scaler=None, demo=None, episode=0, reuse=None):
+                          stats=None, reward_scaler=None, demo=None, episode=0, reuse=None, suggest=None):
     """train.py:76-110 for N workers that share one agent (`num_processes = N` on one GPU, chief.py:13-21 semantics):
     rollouts = [(steer_rollout, throttle_rollout), ...] per worker, dones[i] = worker i's last `done`.  Bootstrap values
     of all workers in one pass (get_values), GAE + advantage normalisation per storage, then for each ppo_epoch and
@@ -801,7 +872,15 @@ def learner_section_multi(agent, rollouts, dones, train_cfg, shared_grad_buffers
     indifferent up to max_grad_norm, whose clip engages earlier.  approx_kl keeps its meaning (movement within this
     update: a stale row's old_logp is its log-probability at the start of the update); explained variance and the KL
     gate are untouched.  `stats` gains "reuse" (see _reuse_stats; one more small device-to-host copy).  The caller appends
-    the section's rollouts to the window afterwards (reuse.append)."""
+    the section's rollouts to the window afterwards (reuse.append).
+    `suggest` (a cadre_amd.suggest.Suggestions; excludes `demo`): exploration suggestions.  After the storages are finished one
+    launch marks their rows from the recorded events (RolloutStorage.mark_suggestions), the learner's loss becomes
+    "ppo+suggest" for the section, and every step carries the kinds of its rows into the update's layout
+    (cadre_suggest_rows) before the update; the rows of stale `reuse` entries get kind 0.  Marks are rank-local, and the
+    gradient is summed by the exchange that sums the PPO gradient.  `stats` gains "suggest" (marked_rows, kl, max_kl,
+    p_mode as (steer, throttle) pairs over the section's steps; one more small device-to-host copy)."""
+    if suggest is not None and demo is not None:
+        raise ValueError("suggest excludes demo (a row carries one kind array)")
     _check_scaler(reward_scaler, shared_grad_buffers, train_cfg)
     tkl = _target_kl(train_cfg, shared_grad_buffers)
     cons = _consensus_on(train_cfg, shared_grad_buffers)
@@ -823,7 +902,10 @@ def learner_section_multi(agent, rollouts, dones, train_cfg, shared_grad_buffers
     if sec is not None:
         agent.learner.set_update_modes(stats=True, target_kl=tkl, consensus=cons)
     dev_losses = []
+    sug_prev = None
     try:
+        sug_prev = _suggest_begin(agent, suggest, [x for pair in rollouts for x in pair], stats,
+                                  train_cfg["ppo_epoch"] * _steps_per_epoch(rollouts[0][0]))
         for epoch in range(train_cfg["ppo_epoch"]):
             idx = [(s.sample_indices(), t.sample_indices()) for s, t in rollouts]
             for j in range(len(idx[0][0])):
@@ -833,21 +915,27 @@ def learner_section_multi(agent, rollouts, dones, train_cfg, shared_grad_buffers
                 dev_losses.append(agent.update_policy_from_storages(
                     batches, sync=False, stats_row=None if sec is None else sec.next_row(),
                     **_demo_kw(demo, batches[0][1].numel(), episode, len(dev_losses), sec)))
+                if suggest is not None:
+                    suggest.collect(agent.learner)
                 shared_grad_buffers.add_gradient(agent.model_dict)
                 chief_step(shared_grad_buffers, optimizer, train_cfg["max_grad_norm"], lr=lr, zero_grads=False)
     finally:
         if sec is not None:
             agent.learner.set_update_modes()
+        if sug_prev is not None:
+            agent.learner.loss_mode = sug_prev
     losses = torch.stack(dev_losses)
     if sec is not None and not losses_on_device:
         host = sec.finish(stats, tkl is not None, losses=losses)
         _scale_stats(stats, reward_scaler)
         _reuse_stats(stats, reuse)
+        _suggest_stats(stats, suggest)
         return tuple(list(c) for c in zip(*host.tolist()))
     if sec is not None:
         sec.finish(stats, tkl is not None)
         _scale_stats(stats, reward_scaler)
         _reuse_stats(stats, reuse)
+        _suggest_stats(stats, suggest)
     if losses_on_device:
         return losses
     vl, pl, el = [], [], []
@@ -922,6 +1010,7 @@ def train_vec(rank, train_cfg, agent_cfg, env_cfg, rollout_cfg, num_envs, env_cl
         ck = _Checkpointer(envs[0].work_dir, ck_interval, agent, rollouts, callback)
         if ck_resume is not None:                # (the environments are the caller's: they restart through reset())
             first_episode = ck.resume(ck_resume)
+    suggest = suggestions(agent, train_cfg, True, ck_interval, ck_resume)      # (refusals first: before anything is loaded)
     demo = demo_mixer(agent, train_cfg, rollout_cfg, rank)          # (before the warm start, which shares its DemoSet)
     _pretrain(agent, train_cfg, rollout_cfg, shared_grad_buffers, rank, logger, ck_resume)
     aux = _aux_runner(agent, train_cfg, shared_grad_buffers, rank, True, ck_interval, first_episode)
@@ -936,16 +1025,19 @@ def train_vec(rank, train_cfg, agent_cfg, env_cfg, rollout_cfg, num_envs, env_cl
         for _ in range(num_steps):
             commands = [o["command"] for o in obs]
             outs = agent.act_batch(obs)
-            rewards, masks, tls = [], [], []
+            rewards, masks, tls, evs = [], [], [], []
             for i, (env, out) in enumerate(zip(envs, outs)):
                 obs[i], reward, dones[i], info = env.step(agent.convert_action(out[1]))
                 ad = info["action_done"]
                 rewards.append(reward)
                 masks.append([0.0 if ad[0] else 1.0, 0.0 if ad[1] else 1.0])
                 tls.append(info.get("time_limit"))
+                if suggest is not None:
+                    evs.append(suggest.codes(info))
             RolloutStorage.insert_batch(rollouts, outs, rewards, masks, commands,
                                         time_limits=None if all(f is None for f in tls) else
-                                        [_time_limit_pair(False if f is None else f) for f in tls])
+                                        [_time_limit_pair(False if f is None else f) for f in tls],
+                                        **({} if suggest is None else dict(events=evs)))
             for i, env in enumerate(envs):
                 if dones[i]:
                     obs[i] = env.reset()
@@ -954,9 +1046,11 @@ def train_vec(rank, train_cfg, agent_cfg, env_cfg, rollout_cfg, num_envs, env_cl
         stats = {} if log_stats else None
         apply_schedules(agent, train_cfg, episode)
         apply_demo_mix(agent, demo, episode, train_cfg.max_episode)
+        apply_suggest(agent, suggest, episode, train_cfg.max_episode)
         vl, pl, el = learner_section_multi(agent, rollouts, dones, train_cfg, shared_grad_buffers, optimizer=optimizer,
                                            stats=stats, reward_scaler=agent.reward_scaler, demo=demo, episode=episode,
-                                           **({} if reuse is None else dict(reuse=reuse.window_for(rollouts))))
+                                           **({} if reuse is None else dict(reuse=reuse.window_for(rollouts))),
+                                           **({} if suggest is None else dict(suggest=suggest)))
         log_now = episode % train_cfg.log_interval == 0 and rank == 0 and logger is not None
         # (the auxiliary phase: before the log line, the snapshot and the checkpoint, which then see its result)
         aux_records = _aux_after_section(aux, agent, train_cfg, episode, rollouts, shared_grad_buffers, optimizer,

@@ -428,7 +428,7 @@ int cadre_grad_norms(const double* norms2, int32_t C, float* stats_row, int32_t 
 /* ---------------------------------------------------------------- device-resident hyper-parameters
  * The hyper-parameter block: a device array of CADRE_HP_FIELDS doubles (8-byte aligned) that the `_hp` entry points read
  * at RUN time, so a captured hipGraph follows whatever the block holds when it is replayed.  Fields past
- * CADRE_HP_DEMO_VALUE_COEFF are reserved and zero.  betas and eps stay by-value arguments.  The block is written by ordinary
+ * CADRE_HP_SUGGEST_COEFF are reserved and zero.  betas and eps stay by-value arguments.  The block is written by ordinary
  * stream-ordered copies from the host, and by the KL-adaptive controller below. */
 #define CADRE_HP_FIELDS 16
 #define CADRE_HP_LR 0
@@ -445,6 +445,9 @@ int cadre_grad_norms(const double* norms2, int32_t C, float* stats_row, int32_t 
  * cross-entropy and of the demonstration rows' value regression.  (Enumerators: the macros above are the ten fields every
  * `_hp` entry point shares, the list the Python binding's HP table mirrors one to one.) */
 enum { CADRE_HP_DEMO_COEFF = 10, CADRE_HP_DEMO_VALUE_COEFF = 11 };
+/* A third reserved field, read by cadre_ppo_sug_loss only and zero for everyone else: the weight of the exploration-suggestion
+ * KL term. */
+enum { CADRE_HP_SUGGEST_COEFF = 12 };
 /* cadre_ppo_loss / cadre_ppo_loss_stats with clip, value_coeff, clip_coeff, ent_coeff = (float)hp[CADRE_HP_*] (the same
  * kernel bodies, the scalars read once per thread before the row loop; the stats variant uses the same clip for its clip
  * fractions).  Equal values give results bit-identical to the by-value entry points.
@@ -690,6 +693,72 @@ int cadre_aux_loss(const float* logits, int64_t ldl, int64_t l_ns, const float* 
                    float beta_clone, float aux_value_coeff, float inv_b, float* losses, float* dlogits, float* dvalues,
                    float* scratch, const int32_t* poison, float* stats_row, int32_t F, float* stats_scratch,
                    const int32_t* ord, void* stream);
+
+/* ---------------------------------------------------------------- exploration suggestions (csrc/suggest.hip)
+ * Terminal-event priors in the PPO loss (Zhang et al. 2021, "End-to-End Urban Driving by Imitating a Reinforcement Learning
+ * Coach", the exploration loss): an episode that ends with a named event z marks the last rows before it, and a marked row
+ * adds KL(pi(.|s) || p_z) towards a prior p_z chosen for the event to its PPO terms.  A storage records a small integer code
+ * per row (events int32 [T + 1], 0: none), the mark launch turns the codes into a kind per row (suggest int32 [T]), the rows
+ * launch carries the kinds of a minibatch into the layout of the update, and the loss launch reads them there.
+ *
+ * cadre_suggest_note: events_k[slots[k]] = codes[k] for k < n, table = n device pointers (int64) to the `events` arrays; the
+ * 2N codes of one env step in one launch.  A NULL pointer or a slot outside 0 .. T writes nothing.  Refused before any launch:
+ * NULL table, slots or codes, n < 1, T < 1. */
+int cadre_suggest_note(const void* table, const int32_t* slots, const int32_t* codes, int32_t n, int32_t T, void* stream);
+/* cadre_suggest_mark: one launch for the n storages of a section, storage k belonging to head k & 1.  table = n records of
+ * four device pointers (int64) {events int32 [T + 1], masks float [T + 1], time_limits float [T + 1] or 0, suggest int32 [T]};
+ * Z event kinds, 1 <= Z <= 8; horizon int32 [2][Z + 1] = rows marked per (head, kind), entry 0 unused.  Per storage the result
+ * is that of this backward scan, all in integers:
+ *   cur = 0; left = 0
+ *   for t = T - 1 .. 0:
+ *     e = events[t]
+ *     if 1 <= e <= Z and horizon[head][e] > 0:  cur = e; left = horizon[head][e]          (the nearest following event wins)
+ *     elif masks[t] == 0 or (time_limits and time_limits[t] != 0):  cur = 0; left = 0     (row t ends an episode without an event)
+ *     suggest[t] = cur if left > 0 else 0
+ *     if left > 0: left -= 1
+ * A window never crosses an episode boundary; an event code outside 1 .. Z is ignored.  Refused before any launch: NULL table
+ * or horizon, n < 1, T < 1, Z outside 1 .. 8. */
+int cadre_suggest_mark(const void* table, int32_t n, int32_t T, int32_t Z, const int32_t* horizon, void* stream);
+/* cadre_suggest_rows: the kinds of a minibatch.  src_table = n_src device pointers (int64) to `suggest` arrays, source
+ * zi = 2 * worker + head, and idx int64 [n_src][Bw] as handed to cadre_gather_sorted_multi.  A source pointer of 0 is a storage
+ * without marks: its rows get kind 0.  kind int32 [2][Bt] in workspace order: row (worker, b) of head h goes to
+ * kind[h][pos[h * Bt + worker * Bw + b]]; pos NULL: the identity (the placement of cadre_mix_row_kinds).  An index outside
+ * 0 .. T - 1 or a position outside 0 .. Bt - 1 writes nothing.  Refused before any launch: NULL src_table, idx or kind, n_src
+ * odd or < 2, Bw < 1, T < 1, (n_src / 2) * Bw > Bt. */
+int cadre_suggest_rows(const void* src_table, int32_t n_src, const int64_t* idx, int32_t Bw, int32_t T, const int32_t* pos,
+                       int32_t Bt, int32_t* kind, void* stream);
+/* cadre_ppo_sug_loss: ONE loss launch where cadre_ppo_loss_ord stands in the update — the same addressing of logits, values,
+ * dlogits and dvalues, the same grid, the same `scratch` (4 + 6 * ceil(B / 16) floats; arrival counter zero on entry and left
+ * zero, partials combined by the last arriving workgroup in workgroup order: two launches on the same inputs give the same
+ * bits), the same `poison`, rank table `ord` (required, as there), hp-or-by-value scalars and stats / target_kl / stop.
+ * kind int32 [2][B] in workspace order; a kind outside 0 .. Z counts as 0.  prior float [2][Z + 1][64]: RAW log-priors in
+ * columns < K per (head, kind), row 0 unused.
+ *   A row of kind 0 runs exactly the statements of cadre_ppo_loss_ord.
+ *   A row of kind z >= 1 runs them too and, with lg the policy's normalised log-probabilities, p its probabilities and
+ *   lq = y - (max y + logf(sum expf(y - max y))) the prior row y normalised by the statements that normalise the policy row,
+ *     kl = sum_k p_k (lg_k - lq_k)          dlogits += sug_coeff inv_b p_j ((lg_j - lq_j) - kl)   in bin space
+ *   (an ordinal head: the sum of both gradients goes through ord_backward).  On a categorical head a row whose raw logits are
+ *   bit-equal to its prior row has kl == 0 and a suggestion gradient of exact zeros.
+ * The mean runs over the minibatch rows with inv_b, marked or not: the coefficient's meaning does not move with the count.
+ *   losses[3]      the PPO terms, as cadre_ppo_loss_ord writes them
+ *   sug_losses[1]  sug_coeff inv_b sum kl          total = losses[0] + losses[1] - losses[2] + sug_losses[0]
+ * sug_coeff is the by-value argument, or (float)hp[CADRE_HP_SUGGEST_COEFF] when hp is not NULL.
+ * stats_row: as in cadre_ppo_loss_ord — the PPO diagnostics, the KL gate and the adaptive lr see what they see without
+ * suggestions (approx_kl is about the PPO ratio).  sug_stats_row (may be NULL) float [2][sug_F], sug_F >= CADRE_SUG_STATS_FIELDS,
+ * per head: 0 marked rows   1 mean kl over the minibatch (sum kl inv_b)   2 max kl (0 when no row is marked)
+ *   3 mean probability the policy gives the prior's mode (lowest index among the largest entries) over the marked rows.
+ * sug_scratch (always required): 2 * ceil(B / 16) * 4 floats; it needs no initialisation.
+ * Refused before any launch: the argument checks of cadre_ppo_loss_ord, NULL kind, prior, sug_losses or sug_scratch, Z outside
+ * 1 .. 8, a sug_coeff that is not finite, sug_F too small. */
+#define CADRE_SUG_STATS_FIELDS 4
+int cadre_ppo_sug_loss(const float* logits, int64_t ldl, int64_t l_ns, const float* values, int64_t ldv, int64_t v_ns,
+                       const int64_t* actions, const int32_t* commands, const float* old_values, const float* returns,
+                       const float* old_logp, const float* adv, const int32_t* kind, const float* prior, int32_t Z, int32_t B,
+                       int32_t C, int32_t n_out_steer, int32_t n_out_throttle, double* hp, float clip, float value_coeff,
+                       float clip_coeff, float ent_coeff, float inv_b, float sug_coeff, float* losses, float* sug_losses,
+                       float* dlogits, float* dvalues, float* scratch, float* sug_scratch, const int32_t* poison,
+                       float* stats_row, int32_t F, float* stats_scratch, float target_kl, int32_t* stop, float* sug_stats_row,
+                       int32_t sug_F, const int32_t* ord, void* stream);
 
 /* ---------------------------------------------------------------- ensemble evaluation (csrc/ensemble.hip)
  * eval.py:53-63 for N environments and M snapshots.  A group of Mg agents (Mg * C <= 16) shares one stacked arena with
