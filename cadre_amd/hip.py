@@ -183,6 +183,18 @@ SYMBOLS = {
     "cadre_suggest_rows": [vp, i32, vp, i32, i32, vp, i32, vp, vp],
     "cadre_ppo_sug_loss": [vp, i64, i64, vp, i64, i64, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, vp, f32, f32,
                            f32, f32, f32, f32, vp, vp, vp, vp, vp, vp, vp, vp, i32, vp, f32, vp, vp, i32, vp, vp],
+    # frame-table storages: the four gathers with window ids (obs, win (NULL: materialised), n_frames, then the twin's
+    # arguments; the multi forms: records of eleven words, see the header) / obs pointer table, n, P, S, ldo, D, flags,
+    # win_local, count, stream / ..., flags, win_local, base, frames, ld, F_cap, win_dst, row0, stream
+    "cadre_gather_obs_ft": [vp, vp, i64, i64, i32, vp, i32, vp, i64, i32, vp],
+    "cadre_gather_minibatch_ft": [vp, vp, i64, i64, i32, vp, vp, i64, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32,
+                                  vp, i64, vp, vp, i64, vp, vp, vp, vp, vp, vp, vp],
+    "cadre_gather_minibatch_multi_ft": [vp, i32, i64, i32, i64, vp, i32, i32, i32, i32, vp, i64, i64, vp, vp, i64, i64,
+                                        vp, vp, vp, vp, vp, vp, vp],
+    "cadre_gather_sorted_multi_ft": [vp, i32, i64, i32, i64, vp, i32, i32, i32, i32, i32, vp, i64, i64, vp, vp, i64, i64,
+                                     vp, vp, vp, vp, vp, vp, vp, vp, vp],
+    "cadre_frames_scan": [vp, i32, i32, i32, i64, i32, vp, vp, vp, vp],
+    "cadre_frames_copy": [vp, i32, i32, i32, i64, i32, vp, vp, vp, vp, i64, i64, vp, vp, vp],
 }
 # entry points of the A/B build only (include/cadre_hip_ab.h; CADRE_BUILD_AB=1 python -m cadre_amd.build, then
 # CADRE_HIP_LIB=.../libcadre_hip_ab.so): bound when the loaded library has them

@@ -24,6 +24,8 @@ GAE_MAX_T = 3000          # rows per cadre_gae_multi launch (include/cadre_hip.h
 PRETRAIN_KEYS = ("episodes", "epochs", "minibatch", "lr", "label_smoothing", "balance", "validation_fraction",
                  "max_grad_norm", "return_scale", "seed")
 DEMO_MIX_KEYS = ("episodes", "coeff", "value_coeff", "blocks", "label_smoothing", "balance", "return_scale", "seed")
+# accepted beside the keys above by both dicts; in the parsed dict only when given (absent: the dict is what it always was)
+FRAME_KEYS = ("frame_table",)
 
 
 # ----------------------------------------------------------------------------- host helpers
@@ -94,10 +96,14 @@ class DemoSet(object):
     obs = the window of transition t, action = the demonstrated bin, command, masks, rewards, returns = the discounted
     Monte-Carlo return times return_scale; hn / cn, value_preds and action_log_probs are zeros — act() hands out the zero
     state), `weights` float32 [T][1] (the row weights, which travel through the minibatch gather in the advantage slot),
-    `episodes` [(first row, end row)], `commands` (host int array)."""
+    `episodes` [(first row, end row)], `commands` (host int array).
+    `frame_table` (from_episodes(frame_table=True)): the two storages are FrameStorages (cadre_amd.frames) — every recorded
+    frame's row once, `_frames` [n_frames][ldo], and the record's window indices, `_win` [T + 1][S], in place of the S = 8
+    times larger window rows; the sets `split` cuts share `_frames`.  Every step reads the same bits either way."""
 
     def __init__(self, steer, throttle, weights, episodes, commands, gamma, balance, return_scale):
         self.steer, self.throttle, self.weights = steer, throttle, weights
+        self.frame_table = getattr(steer, "_win", None) is not None
         self.episodes, self.commands = list(episodes), np.asarray(commands, dtype=np.int64)
         self.gamma, self.balance, self.return_scale = gamma, balance, return_scale
         self.T = steer.num_steps
@@ -114,8 +120,11 @@ class DemoSet(object):
         return steer, throttle
 
     @classmethod
-    def from_episodes(cls, agent, paths_or_dicts, gamma, balance="command", return_scale=1.0):
-        """paths_or_dicts: replay record paths (or loaded record dicts), one per episode, in order."""
+    def from_episodes(cls, agent, paths_or_dicts, gamma, balance="command", return_scale=1.0, frame_table=False):
+        """paths_or_dicts: replay record paths (or loaded record dicts), one per episode, in order.  frame_table: keep
+        frame rows and window indices (FrameStorage) instead of materialised window rows, which are then never allocated."""
+        if not isinstance(frame_table, bool):
+            raise ValueError("DemoSet.from_episodes: frame_table must be a bool (got %r)" % (frame_table,))
         eps = [replay.load_episode(p) if isinstance(p, (str, os.PathLike)) else p for p in paths_or_dicts]
         if not eps:
             raise ValueError("DemoSet.from_episodes: no episodes")
@@ -143,9 +152,20 @@ class DemoSet(object):
         del lat
         meas = torch.from_numpy(np.ascontiguousarray(np.concatenate([ep["measurements"] for ep in eps]), dtype=np.float64)).to(dev)
         window = torch.from_numpy(np.concatenate(win).astype(np.int32)).to(dev)
-        steer, throttle = cls._storages(T, agent.lstm_input, S, agent.lstm_input, gamma, dev)
-        hip.check(hip.lib().cadre_demo_rows(hip.ptr(latent), latent.stride(0), n_frames, hip.ptr(window), hip.ptr(meas), T, S,
-                                            hip.ptr(steer._obs), steer._ldo, hip.stream()), "cadre_demo_rows")
+        if frame_table:
+            # one row per FRAME: cadre_demo_rows over n_frames "windows" of one frame each, the identity for ids; the
+            # record's own window indices become the storages' `_win` (row T, which no minibatch reads: -1)
+            from .frames import frame_pair
+            win = torch.cat([window.view(T, S), torch.full((1, S), -1, dtype=torch.int32, device=dev)])
+            steer, throttle = frame_pair(T, agent.lstm_input, S, agent.lstm_input, gamma, dev, win=win, frame_capacity=n_frames)
+            steer.n_frames = throttle.n_frames = n_frames
+            ident = torch.arange(n_frames, dtype=torch.int32, device=dev)
+            hip.check(hip.lib().cadre_demo_rows(hip.ptr(latent), latent.stride(0), n_frames, hip.ptr(ident), hip.ptr(meas),
+                                                n_frames, 1, hip.ptr(steer._frames), steer._ldo, hip.stream()), "cadre_demo_rows")
+        else:
+            steer, throttle = cls._storages(T, agent.lstm_input, S, agent.lstm_input, gamma, dev)
+            hip.check(hip.lib().cadre_demo_rows(hip.ptr(latent), latent.stride(0), n_frames, hip.ptr(window), hip.ptr(meas), T, S,
+                                                hip.ptr(steer._obs), steer._ldo, hip.stream()), "cadre_demo_rows")
         cmd = np.concatenate([np.asarray(ep["command"], dtype=np.int64).reshape(-1) for ep in eps])
         act = np.concatenate([np.asarray(ep["action"], dtype=np.int64).reshape(-1, 2) for ep in eps])
         rew = np.concatenate([np.asarray(ep["reward"], dtype=np.float32).reshape(-1, 2) for ep in eps])
@@ -187,8 +207,14 @@ class DemoSet(object):
         idx = torch.from_numpy(rows).to(dev)
         T = int(rows.size)
         s0 = self.steer
-        steer, throttle = self._storages(T, s0.z_dims, s0.seq_length, s0.hid_size, self.gamma, dev)
-        steer._obs[:T].copy_(s0._obs.index_select(0, idx))
+        if self.frame_table:                              # the windows of the rows; the frames are shared, not copied
+            from .frames import frame_pair
+            win = torch.cat([s0._win.index_select(0, idx), torch.full((1, s0.seq_length), -1, dtype=torch.int32, device=dev)])
+            steer, throttle = frame_pair(T, s0.z_dims, s0.seq_length, s0.hid_size, self.gamma, dev, frames=s0._frames, win=win,
+                                         n_frames=s0.n_frames)
+        else:
+            steer, throttle = self._storages(T, s0.z_dims, s0.seq_length, s0.hid_size, self.gamma, dev)
+            steer._obs[:T].copy_(s0._obs.index_select(0, idx))
         for src, dst in ((self.steer, steer), (self.throttle, throttle)):
             for k in ("command", "action", "rewards", "masks", "returns"):
                 getattr(dst, k)[:T].copy_(getattr(src, k).index_select(0, idx))
@@ -307,14 +333,15 @@ def evaluate(agent, demo, minibatch, _device=False):
 # ----------------------------------------------------------------------------- train_cfg["pretrain"]
 def pretrain_config(train_cfg_value):
     """train_cfg["pretrain"]: absent / None -> None; else a dict {"episodes": DIR or a list of record paths, "epochs",
-    "minibatch", "lr", "label_smoothing", "balance", "validation_fraction", "max_grad_norm", "return_scale", "seed"} ->
-    the dict with defaults filled in (max_grad_norm None: train_cfg's)."""
+    "minibatch", "lr", "label_smoothing", "balance", "validation_fraction", "max_grad_norm", "return_scale", "seed",
+    "frame_table" (False; True: the set keeps frame rows and window indices, DemoSet.from_episodes(frame_table=True))} -> the dict with
+    defaults filled in (max_grad_norm None: train_cfg's)."""
     cfg = train_cfg_value
     if cfg is None:
         return None
     if not isinstance(cfg, dict):
         raise ValueError("train_cfg.pretrain: expected None or a dict (got %r)" % (cfg,))
-    unknown = sorted(set(cfg) - set(PRETRAIN_KEYS))
+    unknown = sorted(set(cfg) - set(PRETRAIN_KEYS + FRAME_KEYS))
     if unknown or "episodes" not in cfg:
         raise ValueError("train_cfg.pretrain: needs episodes; known keys %r (unknown: %r)" % (PRETRAIN_KEYS, unknown))
     out = dict(episodes=cfg["episodes"], epochs=int(cfg.get("epochs", 1)), minibatch=int(cfg.get("minibatch", 64)),
@@ -322,6 +349,8 @@ def pretrain_config(train_cfg_value):
                balance=cfg.get("balance", "command"), validation_fraction=cfg.get("validation_fraction"),
                max_grad_norm=cfg.get("max_grad_norm"), return_scale=float(cfg.get("return_scale", 1.0)),
                seed=int(cfg.get("seed", 0)))
+    if "frame_table" in cfg:
+        out["frame_table"] = _frame_table_value("pretrain", cfg["frame_table"])
     if out["epochs"] < 0 or out["minibatch"] < 1 or not out["lr"] > 0.0 or not 0.0 <= out["label_smoothing"] < 1.0:
         raise ValueError("train_cfg.pretrain: need epochs >= 0, minibatch >= 1, lr > 0, 0 <= label_smoothing < 1 (got %r)" % (cfg,))
     if out["balance"] not in (None, "command"):
@@ -344,7 +373,8 @@ def pretrain_from_config(agent, cfg, gamma, max_grad_norm, shared_grad_buffers=N
     records = None
     if rank == 0:
         # (a set train_cfg["demo_mix"] built from the same records and parameters is shared: frames are encoded once)
-        demo = demo_set_for(agent, cfg["episodes"], gamma, cfg["balance"], cfg["return_scale"])
+        demo = demo_set_for(agent, cfg["episodes"], gamma, cfg["balance"], cfg["return_scale"],
+                            frame_table=cfg.get("frame_table", False))
         val = None
         if cfg["validation_fraction"] is not None and len(demo.episodes) >= 2:
             demo, val = demo.split(cfg["validation_fraction"], cfg["seed"])
@@ -363,22 +393,23 @@ def _episode_paths(src):
     return replay.list_episodes(src) if isinstance(src, (str, os.PathLike)) else list(src)
 
 
-def _demo_key(src, gamma, balance, return_scale):
+def _demo_key(src, gamma, balance, return_scale, frame_table=False):
     paths = _episode_paths(src)
     if not all(isinstance(p, (str, os.PathLike)) for p in paths):
         return None                                      # loaded record dicts: nothing to key a shared set on
-    return (tuple(os.fspath(p) for p in paths), float(gamma), balance, float(return_scale))
+    return (tuple(os.fspath(p) for p in paths), float(gamma), balance, float(return_scale), bool(frame_table))
 
 
-def demo_set_for(agent, src, gamma, balance, return_scale, keep=False):
+def demo_set_for(agent, src, gamma, balance, return_scale, keep=False, frame_table=False):
     """The DemoSet of record directory / path list `src` with these parameters.  keep: the set stays with the agent, so a
     later call that names the same records and parameters (train_cfg.pretrain beside train_cfg.demo_mix) gets the same
     object instead of encoding every frame again."""
-    key = _demo_key(src, gamma, balance, return_scale)
+    key = _demo_key(src, gamma, balance, return_scale, frame_table)
     kept = agent.__dict__.setdefault("_demo_sets", {})
     if key is not None and key in kept:
         return kept[key]
-    demo = DemoSet.from_episodes(agent, _episode_paths(src), gamma, balance=balance, return_scale=return_scale)
+    demo = DemoSet.from_episodes(agent, _episode_paths(src), gamma, balance=balance, return_scale=return_scale,
+                                 frame_table=frame_table)
     if keep and key is not None:
         kept[key] = demo
     return demo
@@ -425,15 +456,16 @@ class DemoMixer(object):
 def demo_mix_config(train_cfg_value):
     """train_cfg["demo_mix"]: absent / None -> None; else a dict {"episodes": DIR or a list of record paths (required),
     "coeff": a number, ("linear", start, end) or a callable of episode / max_episode (ppo_agent.train.schedule_value; 1.0),
-    "value_coeff" (0.0), "blocks" (1), "label_smoothing" (0.0), "balance" ("command"), "return_scale" (1.0), "seed" (0)} ->
-    the dict with defaults filled in.  value_coeff defaults to 0 because the Monte-Carlo returns of a demonstrator and the
+    "value_coeff" (0.0), "blocks" (1), "label_smoothing" (0.0), "balance" ("command"), "return_scale" (1.0), "seed" (0),
+    "frame_table" (False; as in train_cfg["pretrain"])} -> the dict with defaults filled in.  value_coeff defaults to 0
+    because the Monte-Carlo returns of a demonstrator and the
     GAE returns of the rollouts (under reward scaling) live on different scales: whoever sets it also sets return_scale."""
     cfg = train_cfg_value
     if cfg is None:
         return None
     if not isinstance(cfg, dict):
         raise ValueError("train_cfg.demo_mix: expected None or a dict (got %r)" % (cfg,))
-    unknown = sorted(set(cfg) - set(DEMO_MIX_KEYS))
+    unknown = sorted(set(cfg) - set(DEMO_MIX_KEYS + FRAME_KEYS))
     if unknown or "episodes" not in cfg:
         raise ValueError("train_cfg.demo_mix: needs episodes; known keys %r (unknown: %r)" % (DEMO_MIX_KEYS, unknown))
     coeff = cfg.get("coeff", 1.0)
@@ -455,11 +487,20 @@ def demo_mix_config(train_cfg_value):
     out = dict(episodes=cfg["episodes"], coeff=coeff, value_coeff=float(cfg.get("value_coeff", 0.0)), blocks=int(blocks),
                label_smoothing=float(cfg.get("label_smoothing", 0.0)), balance=cfg.get("balance", "command"),
                return_scale=float(cfg.get("return_scale", 1.0)), seed=int(seed))
+    if "frame_table" in cfg:
+        out["frame_table"] = _frame_table_value("demo_mix", cfg["frame_table"])
     if not 0.0 <= out["label_smoothing"] < 1.0:
         raise ValueError("train_cfg.demo_mix: need 0 <= label_smoothing < 1 (got %r)" % (cfg["label_smoothing"],))
     if out["balance"] not in (None, "command"):
         raise ValueError("train_cfg.demo_mix: balance must be \"command\" or None (got %r)" % (out["balance"],))
     return out
+
+
+def _frame_table_value(where, v):
+    if not isinstance(v, bool):
+        raise ValueError("train_cfg.%s: frame_table must be a bool (got %r): True keeps the demonstration set as frame rows "
+                         "and window indices" % (where, v))
+    return v
 
 
 def _is_number(v):
@@ -469,6 +510,7 @@ def _is_number(v):
 def demo_mixer_from_config(agent, cfg, gamma, rank=0):
     """train_cfg["demo_mix"] (already through demo_mix_config) -> a DemoMixer over the DemoSet of its records.  The set is
     kept with the agent (demo_set_for(keep=True)) so that train_cfg.pretrain on the same records shares it."""
-    demo = demo_set_for(agent, cfg["episodes"], gamma, cfg["balance"], cfg["return_scale"], keep=True)
+    demo = demo_set_for(agent, cfg["episodes"], gamma, cfg["balance"], cfg["return_scale"], keep=True,
+                        frame_table=cfg.get("frame_table", False))
     return DemoMixer(demo, blocks=cfg["blocks"], seed=cfg["seed"], rank=rank, coeff=cfg["coeff"],
                      value_coeff=cfg["value_coeff"], label_smoothing=cfg["label_smoothing"])

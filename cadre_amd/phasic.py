@@ -21,6 +21,8 @@ import torch
 from . import hip
 
 AUX_KEYS = ("interval", "epochs", "minibatch", "beta_clone", "value_coeff", "seed")
+# accepted beside them; in the parsed dict only when given (absent: the dict, and the buffer, are what they always were)
+AUX_FRAME_KEYS = ("frames_per_row",)
 
 
 def slot_rows(slot, rows_per_slot):
@@ -59,10 +61,15 @@ class AuxBuffer(object):
     (`steer`, `throttle`) with num_steps = R that share one `_obs` (both heads see the same windows, as DemoSet._storages),
     beside `table` float32 [2][R][64], the distributions cadre_aux_record writes.  Per row: the window, the LSTM state it
     started from, the command, and per head `returns` — the value targets exactly as the critic saw them in the PPO update,
-    including any reward scaling.  Memory: about 17 KB per row (8 frames x 532 floats of window, two LSTM states) plus 512 B
-    of table."""
+    including any reward scaling.  Memory: about 17 KB per row (8 frames x `_ldo` floats of window, two LSTM states) plus
+    512 B of table.
+    `frames_per_row` (None: the buffer above): a finite number in [1 / S, S].  The two storages are then FrameStorages
+    (cadre_amd.frames) that share a frame table of ceil(R * frames_per_row) rows and the window ids: `append` packs each
+    section's rows into it (cadre_frames_scan / cadre_frames_copy — a window that slid, or that a reset filled with one
+    frame, adds ONE frame: sliding rollouts need 1 frame per row, and up to S - 1 more per storage for a first window of S
+    different frames) and refuses a section whose frames do not fit.  Every step of the phase reads the same bits either way."""
 
-    def __init__(self, agent, slots, rows_per_slot, _device=None):
+    def __init__(self, agent, slots, rows_per_slot, frames_per_row=None, _device=None):
         for name, v in (("slots", slots), ("rows_per_slot", rows_per_slot)):
             if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or v < 1:
                 raise ValueError("AuxBuffer: %s must be an integer >= 1 (got %r)" % (name, v))
@@ -70,8 +77,16 @@ class AuxBuffer(object):
         self.R = self.slots * self.rows_per_slot
         self.filled = 0                # slots appended since the last clear()
         dev = agent.arena.device if _device is None else _device
-        from .imitation import DemoSet
-        self.steer, self.throttle = DemoSet._storages(self.R, agent.lstm_input, agent.learner.S, agent.lstm_input, 0.0, dev)
+        self.frames_per_row = frames_per_row
+        self.frames_used = 0           # frame-table form: the bump pointer (frames in use since the last clear())
+        if frames_per_row is None:
+            from .imitation import DemoSet
+            self.steer, self.throttle = DemoSet._storages(self.R, agent.lstm_input, agent.learner.S, agent.lstm_input, 0.0, dev)
+        else:
+            from .frames import capacity_for, frame_pair
+            cap = capacity_for(self.R, frames_per_row, agent.learner.S)
+            self.steer, self.throttle = frame_pair(self.R, agent.lstm_input, agent.learner.S, agent.lstm_input, 0.0, dev,
+                                                   frame_capacity=cap)
         self.table = torch.zeros(2, self.R, 64, device=dev)
 
     @property
@@ -80,10 +95,16 @@ class AuxBuffer(object):
 
     def clear(self):
         self.filled = 0
+        self.frames_used = 0
+        if self.frames_per_row is not None:
+            self.steer.n_frames = self.throttle.n_frames = 0
 
     def append(self, rollouts):
         """rollouts = [(steer_storage, throttle_storage), ...] of one learner section, after it ran (their `returns` hold
-        the section's value targets): device-to-device copies into the next slot.  Not a hot path."""
+        the section's value targets): device-to-device copies into the next slot.  Not a hot path.
+        Frame-table form: the windows are packed instead of copied (frames.scan_frames / copy_frames: the scan, ONE small
+        read-back of the storages' frame counts, the copy at the bump pointer).  A section that needs more frames than are left raises
+        ValueError naming both numbers before anything of the buffer is written."""
         if self.full:
             raise ValueError("AuxBuffer.append: all %d slots are filled (run the phase, then clear())" % self.slots)
         n = sum(int(s.num_steps) for s, _t in rollouts)
@@ -91,10 +112,14 @@ class AuxBuffer(object):
             raise ValueError("AuxBuffer.append: %d rows for a slot of %d" % (n, self.rows_per_slot))
         lo, _hi = slot_rows(self.filled, self.rows_per_slot)
         for s, t in rollouts:
-            T = int(s.num_steps)
-            if t.num_steps != T or (s._ldo, s.seq_length, s._ldh) != (self.steer._ldo, self.steer.seq_length, self.steer._ldh):
+            if t.num_steps != s.num_steps or (s._ldo, s.seq_length, s._ldh) != (self.steer._ldo, self.steer.seq_length, self.steer._ldh):
                 raise ValueError("AuxBuffer.append: a storage pair whose geometry differs from the buffer's")
-            self.steer._obs[lo:lo + T].copy_(s._obs[:T])
+        if self.frames_per_row is not None:
+            self._append_frames([s for s, _t in rollouts], lo)
+        for s, t in rollouts:
+            T = int(s.num_steps)
+            if self.frames_per_row is None:
+                self.steer._obs[lo:lo + T].copy_(s._obs[:T])
             for src, dst in ((s, self.steer), (t, self.throttle)):
                 dst._hn[lo:lo + T].copy_(src._hn[:T])
                 dst._cn[lo:lo + T].copy_(src._cn[:T])
@@ -102,6 +127,38 @@ class AuxBuffer(object):
                 dst.returns[lo:lo + T].copy_(src.returns[:T])
             lo += T
         self.filled += 1
+
+    def _append_frames(self, storages, lo):
+        """The windows of one section into the frame table from row `lo`: storages of one length in one scan, else one by
+        one.  All scans run, and all counts are known, before the first copy."""
+        from . import frames as fr
+        one_T = all(int(s.num_steps) == int(storages[0].num_steps) for s in storages)
+        groups = [storages] if one_T else [[s] for s in storages]
+        scans, need = [], 0
+        for g in groups:
+            s0 = g[0]
+            if any(getattr(s, "_obs", None) is None for s in g):
+                raise ValueError("AuxBuffer.append: the sections' storages are materialised RolloutStorages")
+            scan = fr.scan_frames([s._obs for s in g], int(s0.num_steps), s0.seq_length, s0._ldo, s0.z_dims)
+            counts = scan[3].cpu().tolist()                   # (the one small read-back per scan)
+            scans.append((g, scan, counts))
+            need += sum(counts)
+        cap = self.steer._frames.shape[0]
+        if need > cap - self.frames_used:
+            raise ValueError("AuxBuffer.append: this section needs %d frames, %d of the buffer's %d are available "
+                             "(frames_per_row=%r: raise it)" % (need, cap - self.frames_used, cap, self.frames_per_row))
+        frame = self.frames_used
+        for g, scan, counts in scans:
+            s0, T = g[0], int(g[0].num_steps)
+            base, row0 = [], []
+            for c in counts:
+                base.append(frame)
+                row0.append(lo)
+                frame += c
+                lo += T
+            fr.copy_frames(scan, T, s0.seq_length, s0._ldo, s0.z_dims, base, self.steer._frames, self.steer._win, row0)
+        self.frames_used = frame
+        self.steer.n_frames = self.throttle.n_frames = frame
 
     def entry(self, idx):
         """The one-entry `entry` argument of CadreAgent.aux_record_from_storages / aux_from_storages for rows `idx` (a CPU
@@ -178,13 +235,15 @@ def _is_int(v):
 def aux_config(train_cfg_value):
     """train_cfg["aux_phase"]: absent / None -> None (nothing runs, nothing is allocated, nothing is drawn); else a dict
     {"interval": rollouts per phase (required, an integer >= 1), "epochs" (2), "minibatch" (None = the PPO minibatch size),
-    "beta_clone" (1.0), "value_coeff" (1.0), "seed" (0)} -> the dict with defaults filled in."""
+    "beta_clone" (1.0), "value_coeff" (1.0), "seed" (0)} -> the dict with defaults filled in.  "frames_per_row" (optional;
+    AuxBuffer(frames_per_row=): a finite number in [1 / S, S], S the window length — checked here against the widest window
+    the kernels take, 16, and against the agent's S when the buffer is built) stays in the dict only when given."""
     cfg = train_cfg_value
     if cfg is None:
         return None
     if not isinstance(cfg, dict):
         raise ValueError("train_cfg.aux_phase: expected None or a dict (got %r)" % (cfg,))
-    unknown = sorted(set(cfg) - set(AUX_KEYS))
+    unknown = sorted(set(cfg) - set(AUX_KEYS + AUX_FRAME_KEYS))
     if unknown or "interval" not in cfg:
         raise ValueError("train_cfg.aux_phase: needs interval; known keys %r (unknown: %r)" % (AUX_KEYS, unknown))
     interval, epochs, mb, seed = cfg["interval"], cfg.get("epochs", 2), cfg.get("minibatch"), cfg.get("seed", 0)
@@ -199,8 +258,18 @@ def aux_config(train_cfg_value):
     for name in ("beta_clone", "value_coeff"):
         if name in cfg and not _is_number(cfg[name]):
             raise ValueError("train_cfg.aux_phase: %s=%r is not a finite number" % (name, cfg[name]))
-    return dict(interval=int(interval), epochs=int(epochs), minibatch=None if mb is None else int(mb),
-                beta_clone=float(cfg.get("beta_clone", 1.0)), value_coeff=float(cfg.get("value_coeff", 1.0)), seed=int(seed))
+    out = dict(interval=int(interval), epochs=int(epochs), minibatch=None if mb is None else int(mb),
+               beta_clone=float(cfg.get("beta_clone", 1.0)), value_coeff=float(cfg.get("value_coeff", 1.0)), seed=int(seed))
+    if "frames_per_row" in cfg:
+        fpr = cfg["frames_per_row"]
+        if fpr is not None:
+            from .frames import MAX_S, frames_per_row_ok
+            if not frames_per_row_ok(fpr):
+                raise ValueError("train_cfg.aux_phase: frames_per_row must be None or a finite number in [1/S, S] for a window "
+                                 "of S <= %d frames (got %r)" % (MAX_S, fpr))
+            fpr = float(fpr)
+        out["frames_per_row"] = fpr
+    return out
 
 
 def check_intervals(interval, checkpoint_interval, first_episode=0):
@@ -229,7 +298,8 @@ class AuxRunner(object):
         """Returns the phase's records when it ran after this episode, else None."""
         cfg = self.cfg
         if self.buffer is None:
-            self.buffer = AuxBuffer(self.agent, cfg["interval"], sum(int(s.num_steps) for s, _t in rollouts))
+            self.buffer = AuxBuffer(self.agent, cfg["interval"], sum(int(s.num_steps) for s, _t in rollouts),
+                                    frames_per_row=cfg.get("frames_per_row"))
         self.buffer.append(rollouts)
         if (episode + 1) % cfg["interval"]:
             return None

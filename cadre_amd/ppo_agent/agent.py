@@ -582,25 +582,32 @@ class CadreAgent(object):
             aux_rows = w["reuse_rows"]
         s0 = batches[0][0]
         geo = (s0._ldo, s0.seq_length, s0._ldh)
+        # a frame-table storage (cadre_amd.frames.FrameStorage) among the step's: the gathers' `_ft` twins, which take the
+        # window ids of each source (none: a materialised one).  With no such storage the launches are what they always were
+        ft = any(getattr(st_, "_win", None) is not None for b in batches for st_ in (b[0], b[3]))
+        self._gather_entry = None                      # the gather entry point of the step (what the tests look at)
         if any((st_._ldo, st_.seq_length, st_._ldh) != geo for b in batches for st_ in (b[0], b[3])):
             # storages of different geometry (feature pitch / window length): one gather launch per storage with its
             # own strides (cadre_gather_minibatch) — the one-launch table below assumes a single geometry
             if self.learner.loss_mode == "ppo+suggest":
                 raise ValueError("the 'ppo+suggest' loss needs storages of one geometry: the kinds of the minibatch are placed "
                                  "by one launch beside the one-launch gather")
+            self._gather_entry = "cadre_gather_minibatch_ft" if ft else "cadre_gather_minibatch"
             for i, (ss, si, sa, ts, ti, ta) in enumerate(batches):
                 for hd, (stor, idx, adv) in enumerate(((ss, si, sa), (ts, ti, ta))):
                     idx_d = idx.reshape(-1).to(self.device)
                     if aux:
                         aux_rows[hd].copy_(idx_d)
-                    hip.check(L.cadre_gather_minibatch(
-                        hip.ptr(stor._obs), stor._ldo, stor.seq_length, hip.ptr(stor._hn), hip.ptr(stor._cn), stor._ldh,
-                        hip.ptr(stor.action), hip.ptr(stor.value_preds), hip.ptr(stor.returns),
-                        hip.ptr(stor.action_log_probs), hip.ptr(stor.command), hip.ptr(adv), hip.ptr(idx_d), Bw, a.D, a.D,
-                        B, i * Bw, hip.ptr(w[Xk][hd]), a.DP, hip.ptr(w[hk][hd]), hip.ptr(w[ck][hd]), a.DP,
-                        hip.ptr(w["actions" + u][hd]), hip.ptr(w["commands" + u][hd]), hip.ptr(w["old_values" + u][hd]),
-                        hip.ptr(w["returns" + u][hd]), hip.ptr(w["old_logp" + u][hd]), hip.ptr(w["adv" + u][hd]), st),
-                        "cadre_gather_minibatch")
+                    rest = (stor._ldo, stor.seq_length, hip.ptr(stor._hn), hip.ptr(stor._cn), stor._ldh,
+                            hip.ptr(stor.action), hip.ptr(stor.value_preds), hip.ptr(stor.returns),
+                            hip.ptr(stor.action_log_probs), hip.ptr(stor.command), hip.ptr(adv), hip.ptr(idx_d), Bw, a.D, a.D,
+                            B, i * Bw, hip.ptr(w[Xk][hd]), a.DP, hip.ptr(w[hk][hd]), hip.ptr(w[ck][hd]), a.DP,
+                            hip.ptr(w["actions" + u][hd]), hip.ptr(w["commands" + u][hd]), hip.ptr(w["old_values" + u][hd]),
+                            hip.ptr(w["returns" + u][hd]), hip.ptr(w["old_logp" + u][hd]), hip.ptr(w["adv" + u][hd]), st)
+                    if ft:
+                        hip.check(L.cadre_gather_minibatch_ft(*(self._ft_source(stor) + rest)), "cadre_gather_minibatch_ft")
+                    else:
+                        hip.check(L.cadre_gather_minibatch(hip.ptr(stor._obs), *rest), "cadre_gather_minibatch")
             return self._finish_update(w, B, nW, srt, sync, mlp_grads_ready, evaluate=evaluate, stats_row=stats_row,
                                        demo_stats_row=demo_stats_row, record=record)
         # ONE gather launch for all workers and both heads: a device table of the storages' pointers (built once per set
@@ -608,7 +615,9 @@ class CadreAgent(object):
         pairs = [(stor, adv) for (ss, si, sa, ts, ti, ta) in batches for (stor, adv) in ((ss, sa), (ts, ta))]
         ptrs = [[hip.ptr(stor._obs), hip.ptr(stor._hn), hip.ptr(stor._cn), hip.ptr(stor.action), hip.ptr(stor.value_preds),
                  hip.ptr(stor.returns), hip.ptr(stor.action_log_probs), hip.ptr(stor.command), hip.ptr(adv)] for stor, adv in pairs]
-        key = tuple(p for row in ptrs for p in row)
+        if ft:      # records of eleven words: the frame table in the first, then the window ids (0: materialised) and the frame count
+            ptrs = [[src[0]] + row[1:] + [src[1] or 0, src[2]] for row, src in zip(ptrs, (self._ft_source(stor) for stor, _ in pairs))]
+        key = (("ft",) if ft else ()) + tuple(p for row in ptrs for p in row)
         cache = self.__dict__.setdefault("_gather_tables", {})
         table = cache.get(key)
         if table is None:
@@ -651,22 +660,30 @@ class CadreAgent(object):
         if srt and (os.environ.get("CADRE_GATHER_SORTED", "1") != "0" if gs is None else gs):
             # rows sorted by command: gather, stable counting sort and placement in ONE launch (round 6; CADRE_GATHER_SORTED=0:
             # gather into staging rows, then cadre_sort_rows_by_command + cadre_permute_minibatch)
-            hip.check(L.cadre_gather_sorted_multi(
+            name = self._gather_entry = "cadre_gather_sorted_multi_ft" if ft else "cadre_gather_sorted_multi"
+            hip.check(getattr(L, name)(
                 hip.ptr(table), 2 * nW, s0._ldo, s0.seq_length, s0._ldh, hip.ptr(stage[1]), Bw, a.D, a.D, B, a.C,
                 hip.ptr(w["X"]), w["X"].stride(0), a.DP, hip.ptr(w["h0"]), hip.ptr(w["c0"]), w["h0"].stride(0), a.DP,
                 hip.ptr(w["actions"]), hip.ptr(w["commands"]), hip.ptr(w["old_values"]),
-                hip.ptr(w["returns"]), hip.ptr(w["old_logp"]), hip.ptr(w["adv"]), hip.ptr(w["pos"]), hip.ptr(w["seg"]), st),
-                "cadre_gather_sorted_multi")
+                hip.ptr(w["returns"]), hip.ptr(w["old_logp"]), hip.ptr(w["adv"]), hip.ptr(w["pos"]), hip.ptr(w["seg"]), st), name)
             return self._finish_update(w, B, nW, srt, sync, mlp_grads_ready, evaluate=evaluate, placed=True, stats_row=stats_row,
                                        demo_stats_row=demo_stats_row, record=record)
-        hip.check(L.cadre_gather_minibatch_multi(
+        name = self._gather_entry = "cadre_gather_minibatch_multi_ft" if ft else "cadre_gather_minibatch_multi"
+        hip.check(getattr(L, name)(
             hip.ptr(table), 2 * nW, s0._ldo, s0.seq_length, s0._ldh, hip.ptr(stage[1]), Bw, a.D, a.D, B,
             hip.ptr(w[Xk]), w[Xk].stride(0), a.DP, hip.ptr(w[hk]), hip.ptr(w[ck]), w[hk].stride(0), a.DP,
             hip.ptr(w["actions" + u]), hip.ptr(w["commands" + u]), hip.ptr(w["old_values" + u]),
-            hip.ptr(w["returns" + u]), hip.ptr(w["old_logp" + u]), hip.ptr(w["adv" + u]), st),
-            "cadre_gather_minibatch_multi")
+            hip.ptr(w["returns" + u]), hip.ptr(w["old_logp" + u]), hip.ptr(w["adv" + u]), st), name)
         return self._finish_update(w, B, nW, srt, sync, mlp_grads_ready, evaluate=evaluate, stats_row=stats_row,
                                        demo_stats_row=demo_stats_row, record=record)
+
+    @staticmethod
+    def _ft_source(stor):
+        """(rows pointer, window ids pointer or None, frame count) of a gather source for the `_ft` entry points."""
+        win = getattr(stor, "_win", None)
+        if win is None:
+            return (hip.ptr(stor._obs), None, 0)
+        return (hip.ptr(stor._frames), hip.ptr(win), int(stor.n_frames))
 
     def _finish_update(self, w, B, nW, srt, sync, mlp_grads_ready=None, placed=False, stats_row=None, evaluate=False,
                        demo_stats_row=None, record=None):

@@ -42,10 +42,9 @@ class RolloutStorage(object):
         T = self.num_steps
         z = lambda *s, dtype=torch.float32: torch.zeros(*s, dtype=dtype, device=device)
         self.device = device
-        self._obs = z(T + 1, self.seq_length, self._ldo)
+        self._alloc_obs(device)
         self._hn = z(T + 1, self._ldh)
         self._cn = z(T + 1, self._ldh)
-        self.obs = self._obs[:, :, :self.z_dims]
         self.hn = self._hn[:, :self.hid_size]
         self.cn = self._cn[:, :self.hid_size]
         self.command = z(T + 1, 1, dtype=torch.int)
@@ -58,6 +57,11 @@ class RolloutStorage(object):
         self.time_limits = z(T + 1, 1)       # 1 where the row's episode was cut by a step limit (insert(time_limit=True))
         self.advantages = z(T, 1)            # filled by compute_returns (train.py:82-88)
         self._next = z(1)
+
+    def _alloc_obs(self, device):
+        """The window rows (cadre_amd.frames.FrameStorage keeps frames and window ids in their place)."""
+        self._obs = torch.zeros(self.num_steps + 1, self.seq_length, self._ldo, dtype=torch.float32, device=device)
+        self.obs = self._obs[:, :, :self.z_dims]
 
     def to(self, device):
         device = torch.device(device)
@@ -137,6 +141,9 @@ class RolloutStorage(object):
         flat = [s for pair in storages for s in pair]
         if len(flat) != 2 * N:
             raise ValueError("insert_batch: storages must be (steer, throttle) pairs")
+        if any(getattr(s, "_win", None) is not None for s in flat):
+            raise ValueError("insert_batch: a frame-table storage is not filled row by row (insert gets no frame identity); "
+                             "DemoSet.from_episodes(frame_table=True) and AuxBuffer(frames_per_row=) build one")
         s0 = flat[0]
         geo = (s0.num_steps, s0.seq_length, s0._ldo, s0._ldh, s0.z_dims, s0.hid_size, s0.device)
         if any((s.num_steps, s.seq_length, s._ldo, s._ldh, s.z_dims, s.hid_size, s.device) != geo for s in flat):

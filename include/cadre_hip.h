@@ -1004,6 +1004,55 @@ int cadre_return_scale_merge(const double* stats, int32_t world, double epsilon,
 #define CADRE_CAPTURE_BAD_RANGE 0xFFFFFFFFFFFFFFFFull
 int cadre_state_capture(const void* range_table, int32_t n_ranges, void* staging, uint64_t* digests, void* stream);
 
+/* ---------------------------------------------------------------- frame-table storages (csrc/frame_table.hip)
+ * A storage may keep every distinct frame row once, frames f32 [F][ldo], and its windows as frame ids, win int32 [T+1][S],
+ * in place of the materialised rows obs [T+1][S][ldo].  The four gathers above have a twin each that takes the ids:
+ *     win == NULL   a materialised source: window row (t, s) is read at obs + (t * S + s) * ldo, exactly as the twin reads it
+ *     win != NULL   obs is the frame table and window row (t, s) is read at obs + win[t * S + s] * ldo
+ * Everything else is the statement of the twin: placement and sort rank, pos / seg, h0 / c0 / scalars, the zero pad up to
+ * ldx — the outputs are bit-identical for equal content.  A frame id outside [0, n_frames) reads nothing and gives NaN in
+ * columns 0 .. D-1 of its row (the pad stays zero), as cadre_demo_rows treats it.  Rows move 16 bytes per lane when ldo and
+ * ldx are multiples of 4 floats and the source base and the destination (of the head) are 16-byte aligned; else element by
+ * element.
+ * The multi forms: src_table holds n_src records of ELEVEN 8-byte words — the nine pointers of the records above, then
+ * `const int32_t* win` and `int64_t n_frames` (the count rides in the record: one table, one cache key; not read where win
+ * is NULL).  Materialised and frame-table sources may stand in one table. */
+int cadre_gather_obs_ft(const float* obs, const int32_t* win, int64_t n_frames, int64_t ldo, int32_t S, const int64_t* idx,
+                        int32_t B, float* x, int64_t ldx, int32_t D, void* stream);
+int cadre_gather_minibatch_ft(const float* obs, const int32_t* win, int64_t n_frames, int64_t ldo, int32_t S, const float* hn,
+                              const float* cn, int64_t ldh, const int64_t* action, const float* value_preds,
+                              const float* returns, const float* logp, const int32_t* command, const float* adv,
+                              const int64_t* idx, int32_t B, int32_t D, int32_t Hd, int32_t Bt, int32_t b0, float* X,
+                              int64_t ldx, float* h0, float* c0, int64_t ldho, int64_t* actions_o, int32_t* commands_o,
+                              float* old_values_o, float* returns_o, float* old_logp_o, float* adv_o, void* stream);
+int cadre_gather_minibatch_multi_ft(const void* src_table, int32_t n_src, int64_t ldo, int32_t S, int64_t ldh,
+                                    const int64_t* idx, int32_t Bw, int32_t D, int32_t Hd, int32_t Bt, float* X,
+                                    int64_t x_head_stride, int64_t ldx, float* h0, float* c0, int64_t h_head_stride,
+                                    int64_t ldho, int64_t* actions_o, int32_t* commands_o, float* old_values_o,
+                                    float* returns_o, float* old_logp_o, float* adv_o, void* stream);
+int cadre_gather_sorted_multi_ft(const void* src_table, int32_t n_src, int64_t ldo, int32_t S, int64_t ldh,
+                                 const int64_t* idx, int32_t Bw, int32_t D, int32_t Hd, int32_t Bt, int32_t C, float* X,
+                                 int64_t x_head_stride, int64_t ldx, float* h0, float* c0, int64_t h_head_stride,
+                                 int64_t ldho, int64_t* actions_o, int32_t* commands_o, float* old_values_o,
+                                 float* returns_o, float* old_logp_o, float* adv_o, int32_t* pos, int32_t* seg, void* stream);
+/* Packing materialised storages into frames (buffers filled from live rollouts, whose rows carry no frame identity).
+ * cadre_frames_scan: src_table = n device pointers to obs [P][S][ldo] (P rows per storage, 1 <= S <= 16).  Per storage z and
+ * window row (t, s), rows compared as 32-bit patterns over columns 0 .. D-1 only (the pad is ignored, -0.0 differs from
+ * +0.0, identical NaN bits are equal):
+ *     1. t > 0, s < S-1 and row (t, s) equals row (t-1, s+1): flags = 1, it takes that row's id (the window slid)
+ *     2. else s > 0 and it equals row (t, s-1): flags = 2, it takes that row's id (a reset filled the window with one frame)
+ *     3. else flags = 0, a new frame: id = the number of new rows of the storage before it in (t, s) order
+ * flags, win_local int32 [n][P][S]; count int32 [n] = the new rows of each storage.  Two launches: the compares (one wave per
+ * window row), then the ids (one wave per storage, serial in t).
+ * cadre_frames_copy: every new row goes to frames[base[z] + id] (ld floats: columns 0 .. D-1 as they are, zeros up to ld; a
+ * row at or past F_cap is not written) and every window row's global id to win_dst[(row0[z] + t) * S + s] = base[z] + id.
+ * base, row0: device int32 [n], filled by the host after it read `count`. */
+int cadre_frames_scan(const void* src_table, int32_t n, int32_t P, int32_t S, int64_t ldo, int32_t D, int32_t* flags,
+                      int32_t* win_local, int32_t* count, void* stream);
+int cadre_frames_copy(const void* src_table, int32_t n, int32_t P, int32_t S, int64_t ldo, int32_t D, const int32_t* flags,
+                      const int32_t* win_local, const int32_t* base, float* frames, int64_t ld, int64_t F_cap,
+                      int32_t* win_dst, const int32_t* row0, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
