@@ -195,6 +195,11 @@ SYMBOLS = {
                                      vp, vp, vp, vp, vp, vp, vp, vp, vp],
     "cadre_frames_scan": [vp, i32, i32, i32, i64, i32, vp, vp, vp, vp],
     "cadre_frames_copy": [vp, i32, i32, i32, i64, i32, vp, vp, vp, vp, i64, i64, vp, vp, vp],
+    "cadre_deconv3x3_s2_supported": [i32, i32, i32, i32, i32, i32, i32, i32],
+    "cadre_deconv3x3_s2": [vp, i64, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, i32, f32, vp],
+    "cadre_deconv3x3_s2_out": [vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, vp],
+    "cadre_argmax_rows": [vp, i64, i32, i32, vp, vp],
+    "cadre_bc_head": [vp, i64, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, f32, vp],
 }
 # entry points of the A/B build only (include/cadre_hip_ab.h; CADRE_BUILD_AB=1 python -m cadre_amd.build, then
 # CADRE_HIP_LIB=.../libcadre_hip_ab.so): bound when the loaded library has them
@@ -526,3 +531,38 @@ def conv3x3_ring(x, w_ring, scale, shift, resid, out, F, H, W, Cin, N, act):
     res = 0 if resid is None else (2 if resid.dtype == torch.bfloat16 else 1)
     key = ("ring", bf, code % 1000, res, out.dtype == torch.bfloat16, code // 1000 % 100, code // 100000 % 10, code // 1000000)
     PROFILE.append((key, 2.0 * M * N * 9 * Cin, e0, e1, (M, N, 9 * Cin, 1, 1, 0), nbytes))
+
+
+def deconv3x3_s2(x, x_zstride, w, scale, shift, out, Z, F, H, W, Cin, Cout, oph, opw, act=0, slope=0.01):
+    """cadre_deconv3x3_s2 (ConvTranspose2d 3x3 / s2 / p1 as four parity-class implicit GEMMs, csrc/deconv.hip) with the profiling
+    hook of gemm(): key ("deconv", Cin, Cout); FLOPs = the EXECUTED ones, 9 taps x Cin x Cout per input position (a tap the
+    map's last row / column does not have is multiplied as zeros)."""
+    fn = lib().cadre_deconv3x3_s2
+    args = (ptr(x), x_zstride, ptr(w), ptr(scale), ptr(shift), ptr(out), Z, F, H, W, Cin, Cout, oph, opw, act, slope, stream())
+    if PROFILE is None or torch.cuda.is_current_stream_capturing():
+        check(fn(*args), "cadre_deconv3x3_s2")
+        return
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record()
+    check(fn(*args), "cadre_deconv3x3_s2")
+    e1.record()
+    Ho, Wo = 2 * H - 1 + oph, 2 * W - 1 + opw
+    nbytes = (F * H * W * Cin * (Z if x_zstride else 1) + Z * 9 * Cin * Cout + Z * F * Ho * Wo * Cout) * 4
+    PROFILE.append((("deconv", Cin, Cout), 2.0 * Z * F * H * W * 9 * Cin * Cout, e0, e1, (F * H * W, Cout, 9 * Cin, Z, 1, 0), nbytes))
+
+
+def deconv3x3_s2_out(x, w, bias, logits, cls, sig, F, H, W, Cout, oph=1, opw=1):
+    """cadre_deconv3x3_s2_out (last decoder level, 32 -> Cout <= 8 on the vector ALU); logits / cls / sig: a tensor, or None when
+    that output is not wanted.  Profiling key ("deconv_out", Cout)."""
+    fn = lib().cadre_deconv3x3_s2_out
+    args = (ptr(x), ptr(w), ptr(bias), ptr(logits), ptr(cls), ptr(sig), F, H, W, Cout, oph, opw, stream())
+    if PROFILE is None or torch.cuda.is_current_stream_capturing():
+        check(fn(*args), "cadre_deconv3x3_s2_out")
+        return
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record()
+    check(fn(*args), "cadre_deconv3x3_s2_out")
+    e1.record()
+    Ho, Wo = 2 * H - 1 + oph, 2 * W - 1 + opw
+    nbytes = F * H * W * 32 * 4 + F * Ho * Wo * ((Cout * 4 if logits is not None else 0) + (1 if cls is not None else 0) + (4 if sig is not None else 0))
+    PROFILE.append((("deconv_out", Cout), 2.0 * F * H * W * 9 * 32 * Cout, e0, e1, (F * H * W, Cout, 9 * 32, 1, 1, 0), nbytes))

@@ -100,6 +100,34 @@ class CadreAgent(object):
         # act_batch(): at most `max_envs` environments per call (sizes the device ring of their latent windows)
         self.max_envs = int(_cfg(model_cfg, "max_envs", 32))
         self._vec = None
+        self._decoder = None        # DANetDecoderHIP, built by the first decode / bc_controls / light_state call
+
+    # ------------------------------------------------------------------ decoder branches (danet.py:164-361)
+    def decoder(self):
+        """The encoder checkpoint's decoder branches (cadre_amd/decoder.py), built on first use from the state create_model loaded."""
+        if self._decoder is None:
+            from ..decoder import DANetDecoderHIP
+            state = getattr(self.vae_model, "source_state", None)
+            if state is None:
+                raise hip.CadreHipError("this agent's encoder keeps no checkpoint state to build the decoder from")
+            self._decoder = DANetDecoderHIP(state, self.device)
+        return self._decoder
+
+    def decode(self, tick_data_or_latents, speed=None, want=("seg", "route", "light", "bc"), seg_logits=False):
+        """DANetDecoderHIP.decode of an observation's window (a tick_data dict: its frames go through get_latent_feature) or of
+        latent rows already on the device (storage rows, a FrameStorage table)."""
+        x = tick_data_or_latents
+        lat = self.get_latent_feature(x) if isinstance(x, dict) else x
+        return self.decoder().decode(lat, speed=speed, want=want, seg_logits=seg_logits)
+
+    def bc_controls(self, tick_data, speed=None):
+        """danet.py:265-291 get_bc_actions -> (steer [S], throttle [S]): the controls the perception module was trained to predict."""
+        bc = self.decode(tick_data, speed=speed, want=("bc",)).bc
+        return bc[:, 0], bc[:, 1]
+
+    def light_state(self, tick_data):
+        """danet.py:334-361 get_light_state -> the 0 .. 3 traffic-light class of the window's first frame (a 0-d device tensor)."""
+        return self.decode(tick_data, want=("light",)).light_state[0]
 
     # ------------------------------------------------------------------ observation -> feature
     def pre_process(self, tick_data, first=0):

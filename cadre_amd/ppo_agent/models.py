@@ -317,9 +317,11 @@ def create_model(model_cfg, load_vae=False):
     if load_vae:
         vae_device = _device(_cfg(model_cfg, "vae_device"))
         H, W = vae_params.obs_hw
-        vae_model = DANetEncoderHIP(load_encoder_state(model_cfg, vae_params), H, W, vae_device,
+        enc_state = load_encoder_state(model_cfg, vae_params)
+        vae_model = DANetEncoderHIP(enc_state, H, W, vae_device,
                                     max_frames=_cfg(model_cfg, "encoder_max_frames", 64),
                                     dtype=_cfg(model_cfg, "encoder_dtype", "f32"))
+        vae_model.source_state = enc_state      # a reference, no copy: CadreAgent.decode builds the decoder branches from it on first use
     device = _device(_cfg(model_cfg, "device_num"))
     if not _cfg(model_cfg, "use_lstm", True):
         raise hip.CadreHipError("use_lstm=False is not on the accelerated path (reference default is True)")

@@ -99,6 +99,67 @@ def encoder_state(feat_h, feat_w, seed=0):
     return {k: make_tensor(k, s, kd, seed) for k, s, kd in encoder_spec(feat_h, feat_w)}
 
 
+DECODER_DIMS = (512, 256, 128, 64, 32)      # visual_branch.py:69 hidden_dims, reversed: channels of the 5x8 ... 72x128 maps
+
+
+def decoder_spec():
+    """[(key, shape, kind)] of the decoder branches of the deployed configuration (auto_danet.py, output mode 12), in the
+    reference's state_dict order: visual_branch.reverse_feature / reverse_image / reverse_route / reverse_lightState
+    (visual_branch.py:86-163), in_bc_speed_fc (danet.py:98-104) and bc_branch.bc_model (bc_branch.py:56-61).  78 keys, 8 of
+    them BatchNorm `num_batches_tracked` counters (kind "count": int64 zeros, dropped by the loader).  ConvTranspose2d
+    weights are [Cin][Cout][3][3]."""
+    spec = []
+
+    def lin(name, out_f, in_f):
+        spec.append((name + ".weight", (out_f, in_f), "lin"))
+        spec.append((name + ".bias", (out_f,), "bias"))
+
+    def reverse_module(name, out_c):
+        d = DECODER_DIMS
+        for i in range(4):
+            spec.append(("%s.%d.weight" % (name, 3 * i), (d[i], d[i + 1], 3, 3), "deconv"))
+            spec.append(("%s.%d.bias" % (name, 3 * i), (d[i + 1],), "bias"))
+            bn = "%s.%d" % (name, 3 * i + 1)
+            spec.append((bn + ".weight", (d[i + 1],), "bn_w"))
+            spec.append((bn + ".bias", (d[i + 1],), "bias"))
+            spec.append((bn + ".running_mean", (d[i + 1],), "bias"))
+            spec.append((bn + ".running_var", (d[i + 1],), "bn_w"))
+            spec.append((bn + ".num_batches_tracked", (), "count"))
+        spec.append((name + ".12.weight", (d[4], out_c, 3, 3), "deconv"))
+        spec.append((name + ".12.bias", (out_c,), "bias"))
+
+    lin("visual_branch.reverse_feature.0", 512, 256)
+    lin("visual_branch.reverse_feature.2", 512 * 5 * 8, 512)
+    reverse_module("visual_branch.reverse_image", 8)
+    reverse_module("visual_branch.reverse_route", 1)
+    lin("visual_branch.reverse_lightState.1", 256, 512 * 5 * 8)
+    lin("visual_branch.reverse_lightState.3", 64, 256)
+    lin("visual_branch.reverse_lightState.5", 4, 64)
+    lin("in_bc_speed_fc.1", 64, 1)
+    lin("in_bc_speed_fc.3", 256, 64)
+    lin("bc_branch.bc_model.1", 128, 256)
+    lin("bc_branch.bc_model.3", 2, 128)
+    return spec
+
+
+def decoder_state(seed=0):
+    """dict name -> ndarray for decoder_spec() (float32; the counters int64), seeded by name like encoder_state."""
+    out = {}
+    for k, s, kd in decoder_spec():
+        if kd == "count":
+            out[k] = np.zeros(s, np.int64)
+        elif kd == "deconv":
+            # an output pixel of a stride-2 transposed 3x3 sums 9/4 taps of Cin channels on average; He gain 2 for the leaky ReLU
+            # keeps the activations' spread level (1.5 at every level of the reverse modules); the last layer (".12", no BatchNorm behind
+            # it) a sixteenth of that, for logits of spread 0.6: the route sigmoid stays unsaturated, and its slope times the fp32
+            # reference's own logit error stays inside the 1e-6 bar the golden generator holds float64 restatements to
+            gain = 0.125 if k.endswith(".12.weight") else 2.0
+            out[k] = (_rs(k, seed).standard_normal(s) * np.sqrt(gain / (s[0] * 2.25))).astype(np.float32)
+        else:
+            out[k] = make_tensor(k, s, kd, seed)
+    return out
+
+
 def feat_hw(H, W):
     """layer-4 map size of the ResNet-18 trunk for an HxW input (resnet.py:111-115,152-166)."""
     def down(n, k, s, p):

@@ -1053,6 +1053,35 @@ int cadre_frames_copy(const void* src_table, int32_t n, int32_t P, int32_t S, in
                       const int32_t* win_local, const int32_t* base, float* frames, int64_t ld, int64_t F_cap,
                       int32_t* win_dst, const int32_t* row0, void* stream);
 
+/* ---- decoder (csrc/deconv.hip): the reverse modules of the reference's visual branch (visual_branch.py:141-163), fp32.
+ * cadre_deconv3x3_s2: out = act(ConvTranspose2d(Cin, Cout, 3, stride 2, padding 1, output_padding (oph, opw))(x) * scale + shift)
+ * for Z independent modules in one launch.  Dense NHWC: x [Z][F][H][W][Cin] with module stride x_zstride floats (0: every
+ * module reads the same input), out [Z][F][2H-1+oph][2W-1+opw][Cout], scale / shift [Z][Cout] (bias and eval-mode BatchNorm
+ * folded by the host), act 0 none / 1 ReLU / 2 leaky ReLU(slope).  w [Z][9 * Cin * Cout]: per module the four output-parity
+ * classes c = 2 py + px one after the other, class c as [Cout][tap][Cin] with tap = dy (1 + px) + dx over dy <= py,
+ * dx <= px, holding the reference weight [Cin][Cout][ky][kx] at ky = 1 (py = 0), 2 (py = 1, dy = 0), 0 (py = 1, dy = 1),
+ * kx alike (cadre_amd/decoder.py pack_deconv).  out[2m+py][2n+px] reads x[m+dy][n+dx]; every output is written once.
+ * _supported: Cin % 32 == 0, Cout % 32 == 0, oph / opw in {0, 1}, every tensor below 2 GiB (host logic, no launch).
+ * cadre_deconv3x3_s2_out: the last level, Cin = 32 -> Cout <= 8, bias only.  x [F][H][W][32]; w [3][3][32][CO] with CO = Cout
+ * rounded up to a power of two and zeros past Cout (w[ky][kx][ci][co] = reference weight [ci][co][ky][kx]).  Outputs, each
+ * NULL when not wanted: logits fp32 [F][Ho][Wo][Cout], cls u8 [F][Ho][Wo] = the first maximum over channels, sig fp32
+ * [F][Ho][Wo] = sigmoid of channel 0 (Cout == 1 only).
+ * cadre_argmax_rows: out[r] = index of the first maximum of x[r][0 .. n-1] (row pitch ld floats).
+ * cadre_bc_head: out [F][2] = (steer, throttle) = bc_model(att_bc), att_bc = lat[f][256 .. 511] (+ in_bc_speed_fc(speed[f]) when speed
+ * is not NULL); lat rows of ld >= 512 floats.  Reference weights as stored: sw1 [64][1], sb1 [64], sw2 [256][64], sb2 [256]
+ * (in_bc_speed_fc.1 / .3), bw1 [128][256], bb1 [128], bw2 [2][128], bb2 [2] (bc_branch.bc_model.1 / .3); leaky ReLU(slope)
+ * between.  One workgroup per row; each layer's output is fp32, its sum runs in double. */
+int cadre_deconv3x3_s2_supported(int32_t Z, int32_t F, int32_t H, int32_t W, int32_t Cin, int32_t Cout, int32_t oph, int32_t opw);
+int cadre_deconv3x3_s2(const float* x, int64_t x_zstride, const float* w, const float* scale, const float* shift, float* out,
+                       int32_t Z, int32_t F, int32_t H, int32_t W, int32_t Cin, int32_t Cout, int32_t oph, int32_t opw,
+                       int32_t act, float slope, void* stream);
+int cadre_deconv3x3_s2_out(const float* x, const float* w, const float* bias, float* logits, uint8_t* cls, float* sig,
+                           int32_t F, int32_t H, int32_t W, int32_t Cout, int32_t oph, int32_t opw, void* stream);
+int cadre_argmax_rows(const float* x, int64_t ld, int32_t rows, int32_t n, int32_t* out, void* stream);
+int cadre_bc_head(const float* lat, int64_t ld, const float* speed, const float* sw1, const float* sb1, const float* sw2,
+                  const float* sb2, const float* bw1, const float* bb1, const float* bw2, const float* bb2, float* out, int32_t F,
+                  float slope, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
