@@ -1680,63 +1680,72 @@ __device__ __forceinline__ void ppo_loss_body(const float* logits, int64_t ldl, 
   }
 }
 
+// One kernel for every mode of the loss, with the full argument list: an instantiation reads only what its flags name (HP: the
+// block instead of the four by-value scalars; STATS: `so`; ORD: `ord`).
+template <bool STATS, bool HP, bool ORD>
 __global__ __launch_bounds__(256) void ppo_loss_kernel(const float* logits, int64_t ldl, int64_t l_ns,
                                                        const float* values, int64_t ldv, int64_t v_ns,
                                                        const int64_t* actions, const int32_t* commands,
                                                        const float* old_values, const float* returns,
                                                        const float* old_logp, const float* adv, int B, int C,
-                                                       int n_steer, int n_throttle, float clip, float value_coeff,
+                                                       int n_steer, int n_throttle, double* hp, float clip, float value_coeff,
                                                        float clip_coeff, float ent_coeff, float inv_b,
                                                        float* losses, float* dlogits, float* dvalues, float* scratch,
-                                                       const int32_t* poison) {
-  const ppo_stats_t none{nullptr, 0, nullptr, 0.f, nullptr};
-  ppo_loss_body<false, false>(logits, ldl, l_ns, values, ldv, v_ns, actions, commands, old_values, returns, old_logp, adv, B, C,
-                              n_steer, n_throttle, clip, value_coeff, clip_coeff, ent_coeff, inv_b, losses, dlogits, dvalues,
-                              scratch, poison, none, nullptr);
-}
-
-__global__ __launch_bounds__(256) void ppo_loss_stats_kernel(const float* logits, int64_t ldl, int64_t l_ns,
-                                                             const float* values, int64_t ldv, int64_t v_ns,
-                                                             const int64_t* actions, const int32_t* commands,
-                                                             const float* old_values, const float* returns,
-                                                             const float* old_logp, const float* adv, int B, int C,
-                                                             int n_steer, int n_throttle, float clip, float value_coeff,
-                                                             float clip_coeff, float ent_coeff, float inv_b,
-                                                             float* losses, float* dlogits, float* dvalues, float* scratch,
-                                                             const int32_t* poison, ppo_stats_t so) {
-  ppo_loss_body<true, false>(logits, ldl, l_ns, values, ldv, v_ns, actions, commands, old_values, returns, old_logp, adv, B, C,
-                             n_steer, n_throttle, clip, value_coeff, clip_coeff, ent_coeff, inv_b, losses, dlogits, dvalues,
-                             scratch, poison, so, nullptr);
-}
-
-// (the same bodies with the four scalars read from the hyper-parameter block)
-__global__ __launch_bounds__(256) void ppo_loss_hp_kernel(const float* logits, int64_t ldl, int64_t l_ns,
-                                                          const float* values, int64_t ldv, int64_t v_ns,
-                                                          const int64_t* actions, const int32_t* commands,
-                                                          const float* old_values, const float* returns,
-                                                          const float* old_logp, const float* adv, int B, int C,
-                                                          int n_steer, int n_throttle, double* hp, float inv_b,
-                                                          float* losses, float* dlogits, float* dvalues, float* scratch,
-                                                          const int32_t* poison) {
-  const ppo_stats_t none{nullptr, 0, nullptr, 0.f, nullptr};
-  ppo_loss_body<false, true>(logits, ldl, l_ns, values, ldv, v_ns, actions, commands, old_values, returns, old_logp, adv, B, C,
-                             n_steer, n_throttle, 0.f, 0.f, 0.f, 0.f, inv_b, losses, dlogits, dvalues, scratch, poison, none, hp);
-}
-
-__global__ __launch_bounds__(256) void ppo_loss_stats_hp_kernel(const float* logits, int64_t ldl, int64_t l_ns,
-                                                                const float* values, int64_t ldv, int64_t v_ns,
-                                                                const int64_t* actions, const int32_t* commands,
-                                                                const float* old_values, const float* returns,
-                                                                const float* old_logp, const float* adv, int B, int C,
-                                                                int n_steer, int n_throttle, double* hp, float inv_b,
-                                                                float* losses, float* dlogits, float* dvalues, float* scratch,
-                                                                const int32_t* poison, ppo_stats_t so) {
-  ppo_loss_body<true, true>(logits, ldl, l_ns, values, ldv, v_ns, actions, commands, old_values, returns, old_logp, adv, B, C,
-                            n_steer, n_throttle, 0.f, 0.f, 0.f, 0.f, inv_b, losses, dlogits, dvalues, scratch, poison, so, hp);
+                                                       const int32_t* poison, ppo_stats_t so, const int32_t* ord) {
+  ppo_loss_body<STATS, HP, ORD>(logits, ldl, l_ns, values, ldv, v_ns, actions, commands, old_values, returns, old_logp, adv, B,
+                                C, n_steer, n_throttle, clip, value_coeff, clip_coeff, ent_coeff, inv_b, losses, dlogits,
+                                dvalues, scratch, poison, so, hp, ord);
 }
 
 __global__ void zero_f32_kernel(float* p, int n) {
   if ((int)threadIdx.x < n) p[threadIdx.x] = 0.f;
+}
+
+// (an entry point's error, for the host functions that stand behind several entry points)
+static int cadre_fail_in(const char* who, const char* what) {
+  snprintf(g_cadre_err, sizeof(g_cadre_err), "%s: %s", who, what);
+  return -1;
+}
+
+// Hyper-parameter block: clip / value_coeff / clip_coeff / ent_coeff are (float)hp[CADRE_HP_*] at run time, so a captured
+// launch follows the block's values.  hp: device double[CADRE_HP_FIELDS], 8-byte aligned.
+#define BAD_HP(hp) (!(hp) || ((uintptr_t)(hp) & 7))
+
+// The host side of the five loss entry points: the checks once, then the instantiation that the optional arguments name
+// (stats_row, hp, ord: NULL = that mode off).  need_*: the entry point has no form without that argument.  An entry point
+// without an `ord` argument passes NULL and so launches ORD = false; cadre_ppo_loss_ord refuses NULL and launches ORD = true,
+// also for a marker table.
+static int ppo_loss_launch(const char* who, const float* logits, int64_t ldl, int64_t l_ns, const float* values, int64_t ldv,
+                           int64_t v_ns, const int64_t* actions, const int32_t* commands, const float* old_values,
+                           const float* returns, const float* old_logp, const float* adv, int32_t B, int32_t C,
+                           int32_t n_out_steer, int32_t n_out_throttle, double* hp, float clip, float value_coeff,
+                           float clip_coeff, float ent_coeff, float inv_b, float* losses, float* dlogits, float* dvalues,
+                           float* scratch, const int32_t* poison, float* stats_row, int32_t F, float* stats_scratch,
+                           float target_kl, int32_t* stop, const int32_t* ord, void* stream, bool need_stats, bool need_hp,
+                           bool need_ord) {
+  if (!logits || !values || !actions || !commands || !old_values || !returns || !old_logp || !adv || !losses || !dlogits ||
+      !dvalues || !scratch || B < 1 || C < 1 || n_out_steer < 1 || n_out_steer > MAX_NOUT || n_out_throttle < 1 ||
+      n_out_throttle > MAX_NOUT || ldl < n_out_steer || ldl < n_out_throttle || ldl > 64)
+    return cadre_fail_in(who, "bad argument");
+  if (need_ord && !ord)
+    return cadre_fail_in(who, "null rank table (device int32 [2][64]; ord[h][0] = -1 marks a categorical head)");
+  if ((need_stats && !stats_row) ||
+      (stats_row && (F < CADRE_PPO_STATS_FIELDS || !stats_scratch || !(target_kl >= 0.f) || (target_kl > 0.f && !stop))))
+    return cadre_fail_in(who, "bad stats argument (F >= CADRE_PPO_STATS_FIELDS, target_kl >= 0, a stop flag with target_kl > 0)");
+  if ((need_hp && !hp) || ((uintptr_t)hp & 7))
+    return cadre_fail_in(who, "bad hyper-parameter block (device double[CADRE_HP_FIELDS], 8-byte aligned)");
+  const ppo_stats_t so{stats_row, F, stats_scratch, target_kl, stop};
+#define PPO_LOSS_MODES(O_) \
+  ppo_loss_kernel<false, false, O_>, ppo_loss_kernel<true, false, O_>, ppo_loss_kernel<false, true, O_>, ppo_loss_kernel<true, true, O_>
+  static const decltype(&ppo_loss_kernel<false, false, false>) kernels[8] = {PPO_LOSS_MODES(false), PPO_LOSS_MODES(true)};
+#undef PPO_LOSS_MODES
+  // scratch[0] (arrival counter) must be zero on entry: zero-initialised by the caller once, reset by the kernel's last
+  // arriver after every launch
+  hipLaunchKernelGGL(kernels[(stats_row ? 1 : 0) | (hp ? 2 : 0) | (ord ? 4 : 0)], dim3((B + 15) / 16, 2), dim3(256), 0,
+                     ST(stream), logits, ldl, l_ns, values, ldv, v_ns, actions, commands, old_values, returns, old_logp, adv, B, C,
+                     n_out_steer, n_out_throttle, hp, clip, value_coeff, clip_coeff, ent_coeff, inv_b, losses, dlogits, dvalues,
+                     scratch, poison, so, ord);
+  return (int)hipGetLastError();
 }
 
 extern "C" int cadre_ppo_loss(const float* logits, int64_t ldl, int64_t l_ns, const float* values, int64_t ldv,
@@ -1745,17 +1754,9 @@ extern "C" int cadre_ppo_loss(const float* logits, int64_t ldl, int64_t l_ns, co
                               int32_t n_out_throttle, float clip, float value_coeff, float clip_coeff,
                               float ent_coeff, float inv_b, float* losses, float* dlogits, float* dvalues,
                               float* scratch, const int32_t* poison, void* stream) {
-  FAIL_IF(!logits || !values || !actions || !commands || !old_values || !returns || !old_logp || !adv || !losses ||
-              !dlogits || !dvalues || !scratch || B < 1 || C < 1 || n_out_steer < 1 || n_out_steer > MAX_NOUT || n_out_throttle < 1 ||
-              n_out_throttle > MAX_NOUT || ldl < n_out_steer || ldl < n_out_throttle || ldl > 64,
-          "cadre_ppo_loss: bad argument");
-  // scratch[0] (arrival counter) must be zero on entry: zero-initialised by the caller once, reset by the kernel's last
-  // arriver after every launch
-  hipLaunchKernelGGL(ppo_loss_kernel, dim3((B + 15) / 16, 2), dim3(256), 0, ST(stream), logits, ldl, l_ns, values, ldv, v_ns,
-                     actions, commands,
-                     old_values, returns, old_logp, adv, B, C, n_out_steer, n_out_throttle, clip, value_coeff,
-                     clip_coeff, ent_coeff, inv_b, losses, dlogits, dvalues, scratch, poison);
-  return (int)hipGetLastError();
+  return ppo_loss_launch("cadre_ppo_loss", logits, ldl, l_ns, values, ldv, v_ns, actions, commands, old_values, returns, old_logp,
+                         adv, B, C, n_out_steer, n_out_throttle, nullptr, clip, value_coeff, clip_coeff, ent_coeff, inv_b, losses,
+                         dlogits, dvalues, scratch, poison, nullptr, 0, nullptr, 0.f, nullptr, nullptr, stream, false, false, false);
 }
 
 extern "C" int cadre_ppo_loss_stats(const float* logits, int64_t ldl, int64_t l_ns, const float* values, int64_t ldv,
@@ -1765,37 +1766,20 @@ extern "C" int cadre_ppo_loss_stats(const float* logits, int64_t ldl, int64_t l_
                                     float clip_coeff, float ent_coeff, float inv_b, float* losses, float* dlogits,
                                     float* dvalues, float* scratch, const int32_t* poison, float* stats_row, int32_t F,
                                     float* stats_scratch, float target_kl, int32_t* stop, void* stream) {
-  FAIL_IF(!logits || !values || !actions || !commands || !old_values || !returns || !old_logp || !adv || !losses ||
-              !dlogits || !dvalues || !scratch || B < 1 || C < 1 || n_out_steer < 1 || n_out_steer > MAX_NOUT || n_out_throttle < 1 ||
-              n_out_throttle > MAX_NOUT || ldl < n_out_steer || ldl < n_out_throttle || ldl > 64,
-          "cadre_ppo_loss_stats: bad argument");
-  FAIL_IF(!stats_row || F < CADRE_PPO_STATS_FIELDS || !stats_scratch || !(target_kl >= 0.f) || (target_kl > 0.f && !stop),
-          "cadre_ppo_loss_stats: bad stats argument (F >= CADRE_PPO_STATS_FIELDS, target_kl >= 0, a stop flag with target_kl > 0)");
-  const ppo_stats_t so{stats_row, F, stats_scratch, target_kl, stop};
-  hipLaunchKernelGGL(ppo_loss_stats_kernel, dim3((B + 15) / 16, 2), dim3(256), 0, ST(stream), logits, ldl, l_ns, values, ldv,
-                     v_ns, actions, commands, old_values, returns, old_logp, adv, B, C, n_out_steer, n_out_throttle, clip,
-                     value_coeff, clip_coeff, ent_coeff, inv_b, losses, dlogits, dvalues, scratch, poison, so);
-  return (int)hipGetLastError();
+  return ppo_loss_launch("cadre_ppo_loss_stats", logits, ldl, l_ns, values, ldv, v_ns, actions, commands, old_values, returns,
+                         old_logp, adv, B, C, n_out_steer, n_out_throttle, nullptr, clip, value_coeff, clip_coeff, ent_coeff, inv_b,
+                         losses, dlogits, dvalues, scratch, poison, stats_row, F, stats_scratch, target_kl, stop, nullptr, stream,
+                         true, false, false);
 }
-
-// Hyper-parameter block variants: clip / value_coeff / clip_coeff / ent_coeff are (float)hp[CADRE_HP_*] at run time, so a
-// captured launch follows the block's values.  hp: device double[CADRE_HP_FIELDS], 8-byte aligned.
-#define BAD_HP(hp) (!(hp) || ((uintptr_t)(hp) & 7))
 
 extern "C" int cadre_ppo_loss_hp(const float* logits, int64_t ldl, int64_t l_ns, const float* values, int64_t ldv,
                                  int64_t v_ns, const int64_t* actions, const int32_t* commands, const float* old_values,
                                  const float* returns, const float* old_logp, const float* adv, int32_t B, int32_t C,
                                  int32_t n_out_steer, int32_t n_out_throttle, double* hp, float inv_b, float* losses,
                                  float* dlogits, float* dvalues, float* scratch, const int32_t* poison, void* stream) {
-  FAIL_IF(!logits || !values || !actions || !commands || !old_values || !returns || !old_logp || !adv || !losses ||
-              !dlogits || !dvalues || !scratch || B < 1 || C < 1 || n_out_steer < 1 || n_out_steer > MAX_NOUT || n_out_throttle < 1 ||
-              n_out_throttle > MAX_NOUT || ldl < n_out_steer || ldl < n_out_throttle || ldl > 64,
-          "cadre_ppo_loss_hp: bad argument");
-  FAIL_IF(BAD_HP(hp), "cadre_ppo_loss_hp: bad hyper-parameter block (device double[CADRE_HP_FIELDS], 8-byte aligned)");
-  hipLaunchKernelGGL(ppo_loss_hp_kernel, dim3((B + 15) / 16, 2), dim3(256), 0, ST(stream), logits, ldl, l_ns, values, ldv, v_ns,
-                     actions, commands, old_values, returns, old_logp, adv, B, C, n_out_steer, n_out_throttle, hp, inv_b,
-                     losses, dlogits, dvalues, scratch, poison);
-  return (int)hipGetLastError();
+  return ppo_loss_launch("cadre_ppo_loss_hp", logits, ldl, l_ns, values, ldv, v_ns, actions, commands, old_values, returns,
+                         old_logp, adv, B, C, n_out_steer, n_out_throttle, hp, 0.f, 0.f, 0.f, 0.f, inv_b, losses, dlogits, dvalues,
+                         scratch, poison, nullptr, 0, nullptr, 0.f, nullptr, nullptr, stream, false, true, false);
 }
 
 extern "C" int cadre_ppo_loss_stats_hp(const float* logits, int64_t ldl, int64_t l_ns, const float* values, int64_t ldv,
@@ -1804,36 +1788,12 @@ extern "C" int cadre_ppo_loss_stats_hp(const float* logits, int64_t ldl, int64_t
                                        int32_t n_out_steer, int32_t n_out_throttle, double* hp, float inv_b, float* losses,
                                        float* dlogits, float* dvalues, float* scratch, const int32_t* poison, float* stats_row,
                                        int32_t F, float* stats_scratch, float target_kl, int32_t* stop, void* stream) {
-  FAIL_IF(!logits || !values || !actions || !commands || !old_values || !returns || !old_logp || !adv || !losses ||
-              !dlogits || !dvalues || !scratch || B < 1 || C < 1 || n_out_steer < 1 || n_out_steer > MAX_NOUT || n_out_throttle < 1 ||
-              n_out_throttle > MAX_NOUT || ldl < n_out_steer || ldl < n_out_throttle || ldl > 64,
-          "cadre_ppo_loss_stats_hp: bad argument");
-  FAIL_IF(!stats_row || F < CADRE_PPO_STATS_FIELDS || !stats_scratch || !(target_kl >= 0.f) || (target_kl > 0.f && !stop),
-          "cadre_ppo_loss_stats_hp: bad stats argument (F >= CADRE_PPO_STATS_FIELDS, target_kl >= 0, a stop flag with target_kl > 0)");
-  FAIL_IF(BAD_HP(hp), "cadre_ppo_loss_stats_hp: bad hyper-parameter block (device double[CADRE_HP_FIELDS], 8-byte aligned)");
-  const ppo_stats_t so{stats_row, F, stats_scratch, target_kl, stop};
-  hipLaunchKernelGGL(ppo_loss_stats_hp_kernel, dim3((B + 15) / 16, 2), dim3(256), 0, ST(stream), logits, ldl, l_ns, values, ldv,
-                     v_ns, actions, commands, old_values, returns, old_logp, adv, B, C, n_out_steer, n_out_throttle, hp, inv_b,
-                     losses, dlogits, dvalues, scratch, poison, so);
-  return (int)hipGetLastError();
+  return ppo_loss_launch("cadre_ppo_loss_stats_hp", logits, ldl, l_ns, values, ldv, v_ns, actions, commands, old_values, returns,
+                         old_logp, adv, B, C, n_out_steer, n_out_throttle, hp, 0.f, 0.f, 0.f, 0.f, inv_b, losses, dlogits, dvalues,
+                         scratch, poison, stats_row, F, stats_scratch, target_kl, stop, nullptr, stream, true, true, false);
 }
 
-// ---------------------------------------------------------------------------- ordinal heads: the four modes in one entry
-template <bool STATS, bool HP>
-__global__ __launch_bounds__(256) void ppo_loss_ord_kernel(const float* logits, int64_t ldl, int64_t l_ns,
-                                                           const float* values, int64_t ldv, int64_t v_ns,
-                                                           const int64_t* actions, const int32_t* commands,
-                                                           const float* old_values, const float* returns,
-                                                           const float* old_logp, const float* adv, int B, int C,
-                                                           int n_steer, int n_throttle, double* hp, float clip,
-                                                           float value_coeff, float clip_coeff, float ent_coeff, float inv_b,
-                                                           float* losses, float* dlogits, float* dvalues, float* scratch,
-                                                           const int32_t* poison, ppo_stats_t so, const int32_t* ord) {
-  ppo_loss_body<STATS, HP, true>(logits, ldl, l_ns, values, ldv, v_ns, actions, commands, old_values, returns, old_logp, adv, B,
-                                 C, n_steer, n_throttle, clip, value_coeff, clip_coeff, ent_coeff, inv_b, losses, dlogits,
-                                 dvalues, scratch, poison, so, hp, ord);
-}
-
+// ordinal heads: the four modes in one entry (hp NULL = by-value scalars, stats row NULL = no diagnostics)
 extern "C" int cadre_ppo_loss_ord(const float* logits, int64_t ldl, int64_t l_ns, const float* values, int64_t ldv,
                                   int64_t v_ns, const int64_t* actions, const int32_t* commands, const float* old_values,
                                   const float* returns, const float* old_logp, const float* adv, int32_t B, int32_t C,
@@ -1841,26 +1801,10 @@ extern "C" int cadre_ppo_loss_ord(const float* logits, int64_t ldl, int64_t l_ns
                                   float clip_coeff, float ent_coeff, float inv_b, float* losses, float* dlogits,
                                   float* dvalues, float* scratch, const int32_t* poison, float* stats_row, int32_t F,
                                   float* stats_scratch, float target_kl, int32_t* stop, const int32_t* ord, void* stream) {
-  FAIL_IF(!logits || !values || !actions || !commands || !old_values || !returns || !old_logp || !adv || !losses ||
-              !dlogits || !dvalues || !scratch || B < 1 || C < 1 || n_out_steer < 1 || n_out_steer > MAX_NOUT || n_out_throttle < 1 ||
-              n_out_throttle > MAX_NOUT || ldl < n_out_steer || ldl < n_out_throttle || ldl > 64,
-          "cadre_ppo_loss_ord: bad argument");
-  FAIL_IF(!ord, "cadre_ppo_loss_ord: null rank table (device int32 [2][64]; ord[h][0] = -1 marks a categorical head)");
-  FAIL_IF(stats_row && (F < CADRE_PPO_STATS_FIELDS || !stats_scratch || !(target_kl >= 0.f) || (target_kl > 0.f && !stop)),
-          "cadre_ppo_loss_ord: bad stats argument (F >= CADRE_PPO_STATS_FIELDS, target_kl >= 0, a stop flag with target_kl > 0)");
-  FAIL_IF(hp && ((uintptr_t)hp & 7), "cadre_ppo_loss_ord: bad hyper-parameter block (device double[CADRE_HP_FIELDS], 8-byte aligned)");
-  const ppo_stats_t so{stats_row, F, stats_scratch, target_kl, stop};
-  const dim3 grid((B + 15) / 16, 2), block(256);
-#define CADRE_ORD_LAUNCH(S_, H_)                                                                                              \
-  hipLaunchKernelGGL((ppo_loss_ord_kernel<S_, H_>), grid, block, 0, ST(stream), logits, ldl, l_ns, values, ldv, v_ns, actions,  \
-                     commands, old_values, returns, old_logp, adv, B, C, n_out_steer, n_out_throttle, hp, clip, value_coeff,  \
-                     clip_coeff, ent_coeff, inv_b, losses, dlogits, dvalues, scratch, poison, so, ord)
-  if (stats_row && hp) CADRE_ORD_LAUNCH(true, true);
-  else if (stats_row) CADRE_ORD_LAUNCH(true, false);
-  else if (hp) CADRE_ORD_LAUNCH(false, true);
-  else CADRE_ORD_LAUNCH(false, false);
-#undef CADRE_ORD_LAUNCH
-  return (int)hipGetLastError();
+  return ppo_loss_launch("cadre_ppo_loss_ord", logits, ldl, l_ns, values, ldv, v_ns, actions, commands, old_values, returns,
+                         old_logp, adv, B, C, n_out_steer, n_out_throttle, hp, clip, value_coeff, clip_coeff, ent_coeff, inv_b,
+                         losses, dlogits, dvalues, scratch, poison, stats_row, F, stats_scratch, target_kl, stop, ord, stream,
+                         false, false, true);
 }
 
 // ============================================================================ sampling: argmax(p / q)
@@ -2072,39 +2016,14 @@ __global__ void adam_kernel(float* p, const float* g, float* m, float* v, const 
 
 // Graph-capturable variant: the step count lives in device memory so a captured launch sequence
 // replays with fresh bias corrections.  scal = norms2 + n_models: {step_size, bc2_sqrt} as doubles.
-__global__ void adam_prep_kernel(double* norms2, int n_models, int32_t* step_dev, double lr, double beta1, double beta2) {
-  const int i = threadIdx.x;
-  if (i < n_models) norms2[i] = 0.0;
-  if (i == 0) {
-    const int step = ++(*step_dev);
-    const double bc1 = 1.0 - pow(beta1, (double)step);
-    const double bc2 = 1.0 - pow(beta2, (double)step);
-    norms2[n_models] = lr / bc1;
-    norms2[n_models + 1] = sqrt(bc2);
-  }
-}
-
-// (gated: the norms are still cleared for the norm pass, which runs either way; the step count and the bias corrections stay)
-__global__ void adam_prep_kernel_gated(double* norms2, int n_models, int32_t* step_dev, double lr, double beta1, double beta2,
-                                       const int32_t* stop) {
-  const int i = threadIdx.x;
-  if (i < n_models) norms2[i] = 0.0;
-  if (i == 0 && *stop == 0) {
-    const int step = ++(*step_dev);
-    const double bc1 = 1.0 - pow(beta1, (double)step);
-    const double bc2 = 1.0 - pow(beta2, (double)step);
-    norms2[n_models] = lr / bc1;
-    norms2[n_models + 1] = sqrt(bc2);
-  }
-}
-
-// (hyper-parameter block: lr is hp[CADRE_HP_LR] at run time — the only place lr enters the step; stop may be NULL)
-__global__ void adam_prep_kernel_hp(double* norms2, int n_models, int32_t* step_dev, const double* hp, double beta1, double beta2,
-                                    const int32_t* stop) {
+// hp (may be NULL): lr is hp[CADRE_HP_LR] at run time — the only place lr enters the step.  stop (may be NULL): the gate; while
+// *stop is set the norms are still cleared for the norm pass, which runs either way; the step count and the bias corrections stay.
+__global__ void adam_prep_kernel(double* norms2, int n_models, int32_t* step_dev, double lr, const double* hp, double beta1,
+                                 double beta2, const int32_t* stop) {
   const int i = threadIdx.x;
   if (i < n_models) norms2[i] = 0.0;
   if (i == 0 && (!stop || *stop == 0)) {
-    const double lr = hp[CADRE_HP_LR];
+    if (hp) lr = hp[CADRE_HP_LR];
     const int step = ++(*step_dev);
     const double bc1 = 1.0 - pow(beta1, (double)step);
     const double bc2 = 1.0 - pow(beta2, (double)step);
@@ -2152,27 +2071,15 @@ __device__ __forceinline__ void adam_dev_kernel_body(float* p, const float* g, f
   }
 }
 
+// HP: max_norm is (float)hp[CADRE_HP_MAX_GRAD_NORM] at run time and the by-value argument is ignored.  GATED: nothing is written
+// while *stop is set — the KL gate of cadre_ppo_loss_stats fired this round.  (The same for the two kernels below.)
+template <bool HP, bool GATED>
 __global__ void adam_dev_kernel(float* p, const float* g, float* m, float* v, const int64_t* seg_off,
-                                const double* norms2, int n_models, float max_norm, float w1, float beta2, float w2,
-                                float eps, int64_t rlo, int64_t rhi) {
-  adam_dev_kernel_body(p, g, m, v, seg_off, norms2, n_models, max_norm, w1, beta2, w2, eps, rlo, rhi);
-}
-
-// (gated twin: nothing is written while *stop is set — the KL gate of cadre_ppo_loss_stats fired this round)
-__global__ void adam_dev_kernel_gated(float* p, const float* g, float* m, float* v, const int64_t* seg_off,
-                                const double* norms2, int n_models, float max_norm, float w1, float beta2, float w2,
-                                float eps, int64_t rlo, int64_t rhi, const int32_t* stop) {
-  if (*stop) return;
-  adam_dev_kernel_body(p, g, m, v, seg_off, norms2, n_models, max_norm, w1, beta2, w2, eps, rlo, rhi);
-}
-
-// (hyper-parameter block twin: max_norm is (float)hp[CADRE_HP_MAX_GRAD_NORM]; GATED: nothing is written while *stop is set)
-template <bool GATED>
-__global__ void adam_dev_kernel_hp(float* p, const float* g, float* m, float* v, const int64_t* seg_off,
-                                   const double* norms2, int n_models, const double* hp, float w1, float beta2, float w2,
-                                   float eps, int64_t rlo, int64_t rhi, const int32_t* stop) {
+                                const double* norms2, int n_models, float max_norm, const double* hp, float w1, float beta2,
+                                float w2, float eps, int64_t rlo, int64_t rhi, const int32_t* stop) {
   if constexpr (GATED) { if (*stop) return; }
-  adam_dev_kernel_body(p, g, m, v, seg_off, norms2, n_models, (float)hp[CADRE_HP_MAX_GRAD_NORM], w1, beta2, w2, eps, rlo, rhi);
+  if constexpr (HP) max_norm = (float)hp[CADRE_HP_MAX_GRAD_NORM];
+  adam_dev_kernel_body(p, g, m, v, seg_off, norms2, n_models, max_norm, w1, beta2, w2, eps, rlo, rhi);
 }
 
 // ---- Adam with the recurrent weights' fragment-order copies written in the same pass (round 4).  The update's LSTM kernels
@@ -2180,7 +2087,7 @@ __global__ void adam_dev_kernel_hp(float* p, const float* g, float* m, float* v,
 // [lane][4], backward the transpose); packing them was its own launch after every optimiser step — 37 MB read twice and 76 MB
 // written, 30 us.  Here the thread that steps a 4 x 4 block of a W_hh matrix (rows n .. n+3, columns k .. k+3) also stores
 // its four rows into the forward copy and its four columns into the backward copy: 16-byte stores, nothing read twice.
-// adam_dev_kernel<true> steps everything else (it skips the W_hh region of the first n_lstm models).
+// adam_dev_skip_kernel steps everything else (it skips the W_hh region of the first n_lstm models).
 struct whh_pack_t {
   int32_t n_lstm;       // models 0 .. n_lstm-1 are LSTM blocks of lstm_str floats
   int64_t lstm_str;     // (= seg_off[1] - seg_off[0])
@@ -2283,26 +2190,13 @@ __device__ __forceinline__ void adam_whh_pack_kernel_body(float* p, const float*
   }
 }
 
+template <bool HP, bool GATED>
 __global__ __launch_bounds__(256) void adam_whh_pack_kernel(float* p, const float* g, float* m, float* v, const double* norms2,
-                                                            int n_models, float max_norm, float w1, float beta2, float w2, float eps,
-                                                            whh_pack_t k) {
-  adam_whh_pack_kernel_body(p, g, m, v, norms2, n_models, max_norm, w1, beta2, w2, eps, k);
-}
-
-// (gated twin: nothing is written while *stop is set — the KL gate of cadre_ppo_loss_stats fired this round)
-__global__ __launch_bounds__(256) void adam_whh_pack_kernel_gated(float* p, const float* g, float* m, float* v, const double* norms2,
-                                                            int n_models, float max_norm, float w1, float beta2, float w2, float eps,
-                                                            whh_pack_t k, const int32_t* stop) {
-  if (*stop) return;
-  adam_whh_pack_kernel_body(p, g, m, v, norms2, n_models, max_norm, w1, beta2, w2, eps, k);
-}
-
-template <bool GATED>
-__global__ __launch_bounds__(256) void adam_whh_pack_kernel_hp(float* p, const float* g, float* m, float* v, const double* norms2,
-                                                               int n_models, const double* hp, float w1, float beta2, float w2,
-                                                               float eps, whh_pack_t k, const int32_t* stop) {
+                                                            int n_models, float max_norm, const double* hp, float w1, float beta2,
+                                                            float w2, float eps, whh_pack_t k, const int32_t* stop) {
   if constexpr (GATED) { if (*stop) return; }
-  adam_whh_pack_kernel_body(p, g, m, v, norms2, n_models, (float)hp[CADRE_HP_MAX_GRAD_NORM], w1, beta2, w2, eps, k);
+  if constexpr (HP) max_norm = (float)hp[CADRE_HP_MAX_GRAD_NORM];
+  adam_whh_pack_kernel_body(p, g, m, v, norms2, n_models, max_norm, w1, beta2, w2, eps, k);
 }
 
 // adam_dev_kernel on everything but the W_hh regions of the LSTM models (those: adam_whh_pack_kernel)
@@ -2338,27 +2232,91 @@ __device__ __forceinline__ void adam_dev_skip_kernel_body(float* p, const float*
   }
 }
 
+template <bool HP, bool GATED>
 __global__ void adam_dev_skip_kernel(float* p, const float* g, float* m, float* v, const int64_t* seg_off, const double* norms2,
-                                     int n_models, float max_norm, float w1, float beta2, float w2, float eps, int n_lstm,
-                                     int64_t o_whh, int64_t whh_len) {
-  adam_dev_skip_kernel_body(p, g, m, v, seg_off, norms2, n_models, max_norm, w1, beta2, w2, eps, n_lstm, o_whh, whh_len);
-}
-
-// (gated twin: nothing is written while *stop is set — the KL gate of cadre_ppo_loss_stats fired this round)
-__global__ void adam_dev_skip_kernel_gated(float* p, const float* g, float* m, float* v, const int64_t* seg_off, const double* norms2,
-                                     int n_models, float max_norm, float w1, float beta2, float w2, float eps, int n_lstm,
-                                     int64_t o_whh, int64_t whh_len, const int32_t* stop) {
-  if (*stop) return;
-  adam_dev_skip_kernel_body(p, g, m, v, seg_off, norms2, n_models, max_norm, w1, beta2, w2, eps, n_lstm, o_whh, whh_len);
-}
-
-template <bool GATED>
-__global__ void adam_dev_skip_kernel_hp(float* p, const float* g, float* m, float* v, const int64_t* seg_off, const double* norms2,
-                                        int n_models, const double* hp, float w1, float beta2, float w2, float eps, int n_lstm,
-                                        int64_t o_whh, int64_t whh_len, const int32_t* stop) {
+                                     int n_models, float max_norm, const double* hp, float w1, float beta2, float w2, float eps,
+                                     int n_lstm, int64_t o_whh, int64_t whh_len, const int32_t* stop) {
   if constexpr (GATED) { if (*stop) return; }
-  adam_dev_skip_kernel_body(p, g, m, v, seg_off, norms2, n_models, (float)hp[CADRE_HP_MAX_GRAD_NORM], w1, beta2, w2, eps, n_lstm,
-                            o_whh, whh_len);
+  if constexpr (HP) max_norm = (float)hp[CADRE_HP_MAX_GRAD_NORM];
+  adam_dev_skip_kernel_body(p, g, m, v, seg_off, norms2, n_models, max_norm, w1, beta2, w2, eps, n_lstm, o_whh, whh_len);
+}
+
+// The host side of the eight graph entry points cadre_clip_adam_[pack_]graph[_hp][_gated]: prep -> per-model square norms ->
+// Adam (pack: on everything but the W_hh regions, then the W_hh kernel that also writes the two copies).
+//   hp (the `_hp` forms, need_hp): lr = hp[CADRE_HP_LR] (read by the prep kernel) and max_norm = hp[CADRE_HP_MAX_GRAD_NORM] (read
+//     by the Adam kernels) at run time; the by-value pair is ignored.  Same kernels' bodies on the same values as the by-value
+//     entry points: bit-identical results for equal values.
+//   stop (the `_gated` forms, need_stop; the KL gate of cadre_ppo_loss_stats): while *stop is set, no parameter, moment, weight
+//     copy or step count is written; the norm pass still runs (cadre_grad_norms reports it).  Clear flag: the same kernels' code
+//     on the same arguments as the ungated entry points, bit for bit.
+#define ADAM_MODES(K_) {K_<false, false>, K_<true, false>, K_<false, true>, K_<true, true>}      // [HP | 2 * GATED]
+static int clip_adam_graph_launch(const char* who, float* params, const float* grads, float* exp_avg, float* exp_avg_sq,
+                                  const int64_t* seg_off, int32_t n_models, double* norms2, double max_norm, double lr,
+                                  const double* hp, bool need_hp, double beta1, double beta2, double eps, int32_t* step_dev,
+                                  const whh_pack_t* pack, const int32_t* stop, bool need_stop, void* stream) {
+  if (!params || !grads || !exp_avg || !exp_avg_sq || !seg_off || !norms2 || !step_dev || (need_stop && !stop) || n_models < 1 ||
+      n_models > 254 || (need_hp && BAD_HP(hp)) || (pack && (!pack->fwd || !pack->bwd || pack->n_lstm < 1 || pack->n_lstm > n_models)))
+    return cadre_fail_in(who, need_hp ? "bad argument (hp: device double[CADRE_HP_FIELDS], 8-byte aligned)" : "bad argument");
+  if (pack) {
+    const int32_t H4 = pack->H4, ldw = pack->ldw, D = pack->D;
+    if (ldw != 544 || D < 1 || D > ldw || H4 != 4 * D || (H4 & 3) || (pack->o_whh & 3) || (pack->lstm_str & 3) ||
+        (pack->p_str & 3) || pack->o_whh + (int64_t)H4 * ldw > pack->lstm_str ||
+        pack->p_str < (int64_t)((D + 15) / 16) * 4 * 34 * 256 ||
+        (((uintptr_t)params | (uintptr_t)pack->fwd | (uintptr_t)pack->bwd) & 15))
+      return cadre_fail_in(who, "built for W_hh [4 D][544] inside an LSTM block, 16-byte aligned (see cadre_pack_lstm_weights)");
+  }
+  static const decltype(&adam_dev_kernel<false, false>) dev_k[4] = ADAM_MODES(adam_dev_kernel);
+  static const decltype(&adam_dev_skip_kernel<false, false>) skip_k[4] = ADAM_MODES(adam_dev_skip_kernel);
+  static const decltype(&adam_whh_pack_kernel<false, false>) pack_k[4] = ADAM_MODES(adam_whh_pack_kernel);
+  const int mode = (hp ? 1 : 0) | (stop ? 2 : 0);
+  hipLaunchKernelGGL(adam_prep_kernel, dim3(1), dim3(256), 0, ST(stream), norms2, n_models, step_dev, lr, hp, beta1, beta2, stop);
+  const int64_t all = (int64_t)1 << 62;
+  hipLaunchKernelGGL(sqnorm_kernel, dim3(64, n_models), dim3(256), 0, ST(stream), grads, seg_off, norms2, (int64_t)0, all);
+  const float mn = (float)max_norm, w1 = (float)(1.0 - beta1), b2 = (float)beta2, w2 = (float)(1.0 - beta2);
+  if (!pack) {
+    hipLaunchKernelGGL(dev_k[mode], dim3(256, n_models), dim3(256), 0, ST(stream), params, grads, exp_avg, exp_avg_sq, seg_off,
+                       norms2, n_models, mn, hp, w1, b2, w2, (float)eps, (int64_t)0, all, stop);
+    return (int)hipGetLastError();
+  }
+  hipLaunchKernelGGL(skip_k[mode], dim3(256, n_models), dim3(256), 0, ST(stream), params, grads, exp_avg, exp_avg_sq, seg_off,
+                     norms2, n_models, mn, hp, w1, b2, w2, (float)eps, pack->n_lstm, pack->o_whh, (int64_t)pack->H4 * pack->ldw,
+                     stop);
+  const int blocks = (((pack->H4 + 15) / 16) * (pack->ldw / 16) + 7) / 8;   // per pass: two 16 x 16 tiles per wave, four waves per workgroup
+  hipLaunchKernelGGL(pack_k[mode], dim3(blocks, pack->n_lstm), dim3(256), 0, ST(stream), params, grads, exp_avg, exp_avg_sq,
+                     norms2, n_models, mn, hp, w1, b2, w2, (float)eps, *pack, stop);
+  return (int)hipGetLastError();
+}
+#undef ADAM_MODES
+
+extern "C" int cadre_clip_adam_graph(float* params, const float* grads, float* exp_avg, float* exp_avg_sq,
+                                     const int64_t* seg_off, int32_t n_models, double* norms2, double max_norm,
+                                     double lr, double beta1, double beta2, double eps, int32_t* step_dev,
+                                     void* stream) {
+  return clip_adam_graph_launch("cadre_clip_adam_graph", params, grads, exp_avg, exp_avg_sq, seg_off, n_models, norms2, max_norm,
+                                lr, nullptr, false, beta1, beta2, eps, step_dev, nullptr, nullptr, false, stream);
+}
+
+extern "C" int cadre_clip_adam_graph_gated(float* params, const float* grads, float* exp_avg, float* exp_avg_sq,
+                                           const int64_t* seg_off, int32_t n_models, double* norms2, double max_norm,
+                                           double lr, double beta1, double beta2, double eps, int32_t* step_dev,
+                                           const int32_t* stop, void* stream) {
+  return clip_adam_graph_launch("cadre_clip_adam_graph_gated", params, grads, exp_avg, exp_avg_sq, seg_off, n_models, norms2,
+                                max_norm, lr, nullptr, false, beta1, beta2, eps, step_dev, nullptr, stop, true, stream);
+}
+
+extern "C" int cadre_clip_adam_graph_hp(float* params, const float* grads, float* exp_avg, float* exp_avg_sq,
+                                        const int64_t* seg_off, int32_t n_models, double* norms2, const double* hp,
+                                        double beta1, double beta2, double eps, int32_t* step_dev, void* stream) {
+  return clip_adam_graph_launch("cadre_clip_adam_graph_hp", params, grads, exp_avg, exp_avg_sq, seg_off, n_models, norms2, 0.0,
+                                0.0, hp, true, beta1, beta2, eps, step_dev, nullptr, nullptr, false, stream);
+}
+
+extern "C" int cadre_clip_adam_graph_hp_gated(float* params, const float* grads, float* exp_avg, float* exp_avg_sq,
+                                              const int64_t* seg_off, int32_t n_models, double* norms2, const double* hp,
+                                              double beta1, double beta2, double eps, int32_t* step_dev, const int32_t* stop,
+                                              void* stream) {
+  return clip_adam_graph_launch("cadre_clip_adam_graph_hp_gated", params, grads, exp_avg, exp_avg_sq, seg_off, n_models, norms2,
+                                0.0, 0.0, hp, true, beta1, beta2, eps, step_dev, nullptr, stop, true, stream);
 }
 
 extern "C" int cadre_clip_adam_pack_graph(float* params, const float* grads, float* exp_avg, float* exp_avg_sq,
@@ -2366,61 +2324,9 @@ extern "C" int cadre_clip_adam_pack_graph(float* params, const float* grads, flo
                                           double beta1, double beta2, double eps, int32_t* step_dev, int32_t n_lstm,
                                           int64_t lstm_str, int64_t o_whh, int32_t H4, int32_t ldw, int32_t D, float* fwd,
                                           float* bwd, int64_t p_str, void* stream) {
-  FAIL_IF(!params || !grads || !exp_avg || !exp_avg_sq || !seg_off || !norms2 || !step_dev || !fwd || !bwd || n_models < 1 ||
-              n_models > 254 || n_lstm < 1 || n_lstm > n_models,
-          "cadre_clip_adam_pack_graph: bad argument");
-  FAIL_IF(ldw != 544 || D < 1 || D > ldw || H4 != 4 * D || (H4 & 3) || (o_whh & 3) || (lstm_str & 3) || (p_str & 3) ||
-              o_whh + (int64_t)H4 * ldw > lstm_str || p_str < (int64_t)((D + 15) / 16) * 4 * 34 * 256 ||
-              (((uintptr_t)params | (uintptr_t)fwd | (uintptr_t)bwd) & 15),
-          "cadre_clip_adam_pack_graph: built for W_hh [4 D][544] inside an LSTM block, 16-byte aligned (see cadre_pack_lstm_weights)");
-  hipLaunchKernelGGL(adam_prep_kernel, dim3(1), dim3(256), 0, ST(stream), norms2, n_models, step_dev, lr, beta1, beta2);
-  const int64_t all = (int64_t)1 << 62;
-  hipLaunchKernelGGL(sqnorm_kernel, dim3(64, n_models), dim3(256), 0, ST(stream), grads, seg_off, norms2, (int64_t)0, all);
-  const float w1 = (float)(1.0 - beta1), b2 = (float)beta2, w2 = (float)(1.0 - beta2);
-  hipLaunchKernelGGL(adam_dev_skip_kernel, dim3(256, n_models), dim3(256), 0, ST(stream), params, grads, exp_avg, exp_avg_sq, seg_off,
-                     norms2, n_models, (float)max_norm, w1, b2, w2, (float)eps, n_lstm, o_whh, (int64_t)H4 * ldw);
-  whh_pack_t k{n_lstm, lstm_str, o_whh, H4, ldw, D, fwd, bwd, p_str};
-  const int blocks = (((H4 + 15) / 16) * (ldw / 16) + 7) / 8;                                 // per pass: two 16 x 16 tiles per wave, four waves per workgroup
-  hipLaunchKernelGGL(adam_whh_pack_kernel, dim3(blocks, n_lstm), dim3(256), 0, ST(stream), params, grads, exp_avg, exp_avg_sq,
-                     norms2, n_models, (float)max_norm, w1, b2, w2, (float)eps, k);
-  return (int)hipGetLastError();
-}
-
-extern "C" int cadre_clip_adam_graph(float* params, const float* grads, float* exp_avg, float* exp_avg_sq,
-                                     const int64_t* seg_off, int32_t n_models, double* norms2, double max_norm,
-                                     double lr, double beta1, double beta2, double eps, int32_t* step_dev,
-                                     void* stream) {
-  FAIL_IF(!params || !grads || !exp_avg || !exp_avg_sq || !seg_off || !norms2 || !step_dev || n_models < 1 ||
-              n_models > 254,
-          "cadre_clip_adam_graph: bad argument");
-  hipLaunchKernelGGL(adam_prep_kernel, dim3(1), dim3(256), 0, ST(stream), norms2, n_models, step_dev, lr, beta1, beta2);
-  dim3 grid(64, n_models), grid2(256, n_models);
-  const int64_t all = (int64_t)1 << 62;
-  hipLaunchKernelGGL(sqnorm_kernel, grid, dim3(256), 0, ST(stream), grads, seg_off, norms2, (int64_t)0, all);
-  hipLaunchKernelGGL(adam_dev_kernel, grid2, dim3(256), 0, ST(stream), params, grads, exp_avg, exp_avg_sq, seg_off,
-                     norms2, n_models, (float)max_norm, (float)(1.0 - beta1), (float)beta2, (float)(1.0 - beta2),
-                     (float)eps, (int64_t)0, all);
-  return (int)hipGetLastError();
-}
-
-// Gated twins of the two graph entry points (the KL gate of cadre_ppo_loss_stats): while *stop is set, no parameter, moment,
-// weight copy or step count is written; the norm pass still runs (cadre_grad_norms reports it).  Clear flag: the same
-// kernels' code on the same arguments as the ungated entry points, bit for bit.
-extern "C" int cadre_clip_adam_graph_gated(float* params, const float* grads, float* exp_avg, float* exp_avg_sq,
-                                           const int64_t* seg_off, int32_t n_models, double* norms2, double max_norm,
-                                           double lr, double beta1, double beta2, double eps, int32_t* step_dev,
-                                           const int32_t* stop, void* stream) {
-  FAIL_IF(!params || !grads || !exp_avg || !exp_avg_sq || !seg_off || !norms2 || !step_dev || !stop || n_models < 1 ||
-              n_models > 254,
-          "cadre_clip_adam_graph_gated: bad argument");
-  hipLaunchKernelGGL(adam_prep_kernel_gated, dim3(1), dim3(256), 0, ST(stream), norms2, n_models, step_dev, lr, beta1, beta2, stop);
-  dim3 grid(64, n_models), grid2(256, n_models);
-  const int64_t all = (int64_t)1 << 62;
-  hipLaunchKernelGGL(sqnorm_kernel, grid, dim3(256), 0, ST(stream), grads, seg_off, norms2, (int64_t)0, all);
-  hipLaunchKernelGGL(adam_dev_kernel_gated, grid2, dim3(256), 0, ST(stream), params, grads, exp_avg, exp_avg_sq, seg_off,
-                     norms2, n_models, (float)max_norm, (float)(1.0 - beta1), (float)beta2, (float)(1.0 - beta2),
-                     (float)eps, (int64_t)0, all, stop);
-  return (int)hipGetLastError();
+  const whh_pack_t k{n_lstm, lstm_str, o_whh, H4, ldw, D, fwd, bwd, p_str};
+  return clip_adam_graph_launch("cadre_clip_adam_pack_graph", params, grads, exp_avg, exp_avg_sq, seg_off, n_models, norms2,
+                                max_norm, lr, nullptr, false, beta1, beta2, eps, step_dev, &k, nullptr, false, stream);
 }
 
 extern "C" int cadre_clip_adam_pack_graph_gated(float* params, const float* grads, float* exp_avg, float* exp_avg_sq,
@@ -2429,94 +2335,9 @@ extern "C" int cadre_clip_adam_pack_graph_gated(float* params, const float* grad
                                                 int32_t n_lstm, int64_t lstm_str, int64_t o_whh, int32_t H4, int32_t ldw,
                                                 int32_t D, float* fwd, float* bwd, int64_t p_str, const int32_t* stop,
                                                 void* stream) {
-  FAIL_IF(!params || !grads || !exp_avg || !exp_avg_sq || !seg_off || !norms2 || !step_dev || !fwd || !bwd || !stop ||
-              n_models < 1 || n_models > 254 || n_lstm < 1 || n_lstm > n_models,
-          "cadre_clip_adam_pack_graph_gated: bad argument");
-  FAIL_IF(ldw != 544 || D < 1 || D > ldw || H4 != 4 * D || (H4 & 3) || (o_whh & 3) || (lstm_str & 3) || (p_str & 3) ||
-              o_whh + (int64_t)H4 * ldw > lstm_str || p_str < (int64_t)((D + 15) / 16) * 4 * 34 * 256 ||
-              (((uintptr_t)params | (uintptr_t)fwd | (uintptr_t)bwd) & 15),
-          "cadre_clip_adam_pack_graph_gated: built for W_hh [4 D][544] inside an LSTM block, 16-byte aligned (see cadre_pack_lstm_weights)");
-  hipLaunchKernelGGL(adam_prep_kernel_gated, dim3(1), dim3(256), 0, ST(stream), norms2, n_models, step_dev, lr, beta1, beta2, stop);
-  const int64_t all = (int64_t)1 << 62;
-  hipLaunchKernelGGL(sqnorm_kernel, dim3(64, n_models), dim3(256), 0, ST(stream), grads, seg_off, norms2, (int64_t)0, all);
-  const float w1 = (float)(1.0 - beta1), b2 = (float)beta2, w2 = (float)(1.0 - beta2);
-  hipLaunchKernelGGL(adam_dev_skip_kernel_gated, dim3(256, n_models), dim3(256), 0, ST(stream), params, grads, exp_avg, exp_avg_sq,
-                     seg_off, norms2, n_models, (float)max_norm, w1, b2, w2, (float)eps, n_lstm, o_whh, (int64_t)H4 * ldw, stop);
-  whh_pack_t k{n_lstm, lstm_str, o_whh, H4, ldw, D, fwd, bwd, p_str};
-  const int blocks = (((H4 + 15) / 16) * (ldw / 16) + 7) / 8;
-  hipLaunchKernelGGL(adam_whh_pack_kernel_gated, dim3(blocks, n_lstm), dim3(256), 0, ST(stream), params, grads, exp_avg, exp_avg_sq,
-                     norms2, n_models, (float)max_norm, w1, b2, w2, (float)eps, k, stop);
-  return (int)hipGetLastError();
-}
-
-// Hyper-parameter block forms of the four graph entry points: lr = hp[CADRE_HP_LR] (read by the prep kernel) and
-// max_norm = hp[CADRE_HP_MAX_GRAD_NORM] (read by the Adam kernels) at run time.  Same kernels' bodies on the same values as
-// the by-value entry points: bit-identical results for equal values.
-template <bool GATED>
-static int clip_adam_graph_hp(const char* who, float* params, const float* grads, float* exp_avg, float* exp_avg_sq,
-                              const int64_t* seg_off, int32_t n_models, double* norms2, const double* hp, double beta1,
-                              double beta2, double eps, int32_t* step_dev, const int32_t* stop, void* stream) {
-  if (!params || !grads || !exp_avg || !exp_avg_sq || !seg_off || !norms2 || !step_dev || (GATED && !stop) || n_models < 1 ||
-      n_models > 254 || BAD_HP(hp)) {
-    snprintf(g_cadre_err, sizeof(g_cadre_err), "%s: bad argument (hp: device double[CADRE_HP_FIELDS], 8-byte aligned)", who);
-    return -1;
-  }
-  hipLaunchKernelGGL(adam_prep_kernel_hp, dim3(1), dim3(256), 0, ST(stream), norms2, n_models, step_dev, hp, beta1, beta2,
-                     GATED ? stop : nullptr);
-  dim3 grid(64, n_models), grid2(256, n_models);
-  const int64_t all = (int64_t)1 << 62;
-  hipLaunchKernelGGL(sqnorm_kernel, grid, dim3(256), 0, ST(stream), grads, seg_off, norms2, (int64_t)0, all);
-  hipLaunchKernelGGL(adam_dev_kernel_hp<GATED>, grid2, dim3(256), 0, ST(stream), params, grads, exp_avg, exp_avg_sq, seg_off,
-                     norms2, n_models, hp, (float)(1.0 - beta1), (float)beta2, (float)(1.0 - beta2), (float)eps, (int64_t)0, all,
-                     stop);
-  return (int)hipGetLastError();
-}
-
-template <bool GATED>
-static int clip_adam_pack_graph_hp(const char* who, float* params, const float* grads, float* exp_avg, float* exp_avg_sq,
-                                   const int64_t* seg_off, int32_t n_models, double* norms2, const double* hp, double beta1,
-                                   double beta2, double eps, int32_t* step_dev, int32_t n_lstm, int64_t lstm_str, int64_t o_whh,
-                                   int32_t H4, int32_t ldw, int32_t D, float* fwd, float* bwd, int64_t p_str, const int32_t* stop,
-                                   void* stream) {
-  if (!params || !grads || !exp_avg || !exp_avg_sq || !seg_off || !norms2 || !step_dev || !fwd || !bwd || (GATED && !stop) ||
-      n_models < 1 || n_models > 254 || n_lstm < 1 || n_lstm > n_models || BAD_HP(hp)) {
-    snprintf(g_cadre_err, sizeof(g_cadre_err), "%s: bad argument (hp: device double[CADRE_HP_FIELDS], 8-byte aligned)", who);
-    return -1;
-  }
-  if (ldw != 544 || D < 1 || D > ldw || H4 != 4 * D || (H4 & 3) || (o_whh & 3) || (lstm_str & 3) || (p_str & 3) ||
-      o_whh + (int64_t)H4 * ldw > lstm_str || p_str < (int64_t)((D + 15) / 16) * 4 * 34 * 256 ||
-      (((uintptr_t)params | (uintptr_t)fwd | (uintptr_t)bwd) & 15)) {
-    snprintf(g_cadre_err, sizeof(g_cadre_err),
-             "%s: built for W_hh [4 D][544] inside an LSTM block, 16-byte aligned (see cadre_pack_lstm_weights)", who);
-    return -1;
-  }
-  hipLaunchKernelGGL(adam_prep_kernel_hp, dim3(1), dim3(256), 0, ST(stream), norms2, n_models, step_dev, hp, beta1, beta2,
-                     GATED ? stop : nullptr);
-  const int64_t all = (int64_t)1 << 62;
-  hipLaunchKernelGGL(sqnorm_kernel, dim3(64, n_models), dim3(256), 0, ST(stream), grads, seg_off, norms2, (int64_t)0, all);
-  const float w1 = (float)(1.0 - beta1), b2 = (float)beta2, w2 = (float)(1.0 - beta2);
-  hipLaunchKernelGGL(adam_dev_skip_kernel_hp<GATED>, dim3(256, n_models), dim3(256), 0, ST(stream), params, grads, exp_avg,
-                     exp_avg_sq, seg_off, norms2, n_models, hp, w1, b2, w2, (float)eps, n_lstm, o_whh, (int64_t)H4 * ldw, stop);
-  whh_pack_t k{n_lstm, lstm_str, o_whh, H4, ldw, D, fwd, bwd, p_str};
-  const int blocks = (((H4 + 15) / 16) * (ldw / 16) + 7) / 8;
-  hipLaunchKernelGGL(adam_whh_pack_kernel_hp<GATED>, dim3(blocks, n_lstm), dim3(256), 0, ST(stream), params, grads, exp_avg,
-                     exp_avg_sq, norms2, n_models, hp, w1, b2, w2, (float)eps, k, stop);
-  return (int)hipGetLastError();
-}
-
-extern "C" int cadre_clip_adam_graph_hp(float* params, const float* grads, float* exp_avg, float* exp_avg_sq,
-                                        const int64_t* seg_off, int32_t n_models, double* norms2, const double* hp,
-                                        double beta1, double beta2, double eps, int32_t* step_dev, void* stream) {
-  return clip_adam_graph_hp<false>("cadre_clip_adam_graph_hp", params, grads, exp_avg, exp_avg_sq, seg_off, n_models, norms2, hp,
-                                   beta1, beta2, eps, step_dev, nullptr, stream);
-}
-
-extern "C" int cadre_clip_adam_graph_hp_gated(float* params, const float* grads, float* exp_avg, float* exp_avg_sq,
-                                              const int64_t* seg_off, int32_t n_models, double* norms2, const double* hp,
-                                              double beta1, double beta2, double eps, int32_t* step_dev, const int32_t* stop,
-                                              void* stream) {
-  return clip_adam_graph_hp<true>("cadre_clip_adam_graph_hp_gated", params, grads, exp_avg, exp_avg_sq, seg_off, n_models, norms2,
-                                  hp, beta1, beta2, eps, step_dev, stop, stream);
+  const whh_pack_t k{n_lstm, lstm_str, o_whh, H4, ldw, D, fwd, bwd, p_str};
+  return clip_adam_graph_launch("cadre_clip_adam_pack_graph_gated", params, grads, exp_avg, exp_avg_sq, seg_off, n_models, norms2,
+                                max_norm, lr, nullptr, false, beta1, beta2, eps, step_dev, &k, stop, true, stream);
 }
 
 extern "C" int cadre_clip_adam_pack_graph_hp(float* params, const float* grads, float* exp_avg, float* exp_avg_sq,
@@ -2524,9 +2345,9 @@ extern "C" int cadre_clip_adam_pack_graph_hp(float* params, const float* grads, 
                                              double beta1, double beta2, double eps, int32_t* step_dev, int32_t n_lstm,
                                              int64_t lstm_str, int64_t o_whh, int32_t H4, int32_t ldw, int32_t D, float* fwd,
                                              float* bwd, int64_t p_str, void* stream) {
-  return clip_adam_pack_graph_hp<false>("cadre_clip_adam_pack_graph_hp", params, grads, exp_avg, exp_avg_sq, seg_off, n_models,
-                                        norms2, hp, beta1, beta2, eps, step_dev, n_lstm, lstm_str, o_whh, H4, ldw, D, fwd, bwd,
-                                        p_str, nullptr, stream);
+  const whh_pack_t k{n_lstm, lstm_str, o_whh, H4, ldw, D, fwd, bwd, p_str};
+  return clip_adam_graph_launch("cadre_clip_adam_pack_graph_hp", params, grads, exp_avg, exp_avg_sq, seg_off, n_models, norms2,
+                                0.0, 0.0, hp, true, beta1, beta2, eps, step_dev, &k, nullptr, false, stream);
 }
 
 extern "C" int cadre_clip_adam_pack_graph_hp_gated(float* params, const float* grads, float* exp_avg, float* exp_avg_sq,
@@ -2534,15 +2355,19 @@ extern "C" int cadre_clip_adam_pack_graph_hp_gated(float* params, const float* g
                                                    double beta1, double beta2, double eps, int32_t* step_dev, int32_t n_lstm,
                                                    int64_t lstm_str, int64_t o_whh, int32_t H4, int32_t ldw, int32_t D,
                                                    float* fwd, float* bwd, int64_t p_str, const int32_t* stop, void* stream) {
-  return clip_adam_pack_graph_hp<true>("cadre_clip_adam_pack_graph_hp_gated", params, grads, exp_avg, exp_avg_sq, seg_off,
-                                       n_models, norms2, hp, beta1, beta2, eps, step_dev, n_lstm, lstm_str, o_whh, H4, ldw, D, fwd,
-                                       bwd, p_str, stop, stream);
+  const whh_pack_t k{n_lstm, lstm_str, o_whh, H4, ldw, D, fwd, bwd, p_str};
+  return clip_adam_graph_launch("cadre_clip_adam_pack_graph_hp_gated", params, grads, exp_avg, exp_avg_sq, seg_off, n_models,
+                                norms2, 0.0, 0.0, hp, true, beta1, beta2, eps, step_dev, &k, stop, true, stream);
 }
 
 // Per-model gradient norms of the step into its stats row: model m = kind * Z + head * C + c (kind 0 LSTM, 1 MLP towers;
 // Z = 2 C) goes to row[head * F + CADRE_PPO_STATS_FIELDS + kind * C + c].  sqrt(norms2[m]): the pre-clip total norm.
-__global__ void grad_norms_kernel(const double* norms2, int C, float* row, int F) {
+// hp (cadre_grad_norms_hp; NULL otherwise): the launch also reports the learning rate the step used: row[CADRE_PPO_STATS_LR] of
+// head 0 = (float)hp[LR] (the launch follows the optimiser step and precedes the next loss launch, so the block still holds the
+// step's value).
+__global__ void grad_norms_kernel(const double* norms2, int C, float* row, int F, const double* hp) {
   const int m = threadIdx.x, Z = 2 * C;
+  if (hp && m == 255) row[CADRE_PPO_STATS_LR] = (float)hp[CADRE_HP_LR];
   if (m >= 2 * Z) return;
   const int kind = m / Z, g = m - kind * Z, head = g / C, c = g - head * C;
   row[head * F + CADRE_PPO_STATS_FIELDS + kind * C + c] = (float)sqrt(norms2[m]);
@@ -2550,24 +2375,14 @@ __global__ void grad_norms_kernel(const double* norms2, int C, float* row, int F
 
 extern "C" int cadre_grad_norms(const double* norms2, int32_t C, float* stats_row, int32_t F, void* stream) {
   FAIL_IF(!norms2 || !stats_row || C < 1 || C > 63 || F < CADRE_PPO_STATS_FIELDS + 2 * C, "cadre_grad_norms: bad argument");
-  hipLaunchKernelGGL(grad_norms_kernel, dim3(1), dim3(256), 0, ST(stream), norms2, C, stats_row, F);
+  hipLaunchKernelGGL(grad_norms_kernel, dim3(1), dim3(256), 0, ST(stream), norms2, C, stats_row, F, (const double*)nullptr);
   return (int)hipGetLastError();
-}
-
-// cadre_grad_norms that also reports the learning rate the step used: row[CADRE_PPO_STATS_LR] of head 0 = (float)hp[LR]
-// (the launch follows the optimiser step and precedes the next loss launch, so the block still holds the step's value).
-__global__ void grad_norms_hp_kernel(const double* norms2, int C, float* row, int F, const double* hp) {
-  const int m = threadIdx.x, Z = 2 * C;
-  if (m == 255) row[CADRE_PPO_STATS_LR] = (float)hp[CADRE_HP_LR];
-  if (m >= 2 * Z) return;
-  const int kind = m / Z, g = m - kind * Z, head = g / C, c = g - head * C;
-  row[head * F + CADRE_PPO_STATS_FIELDS + kind * C + c] = (float)sqrt(norms2[m]);
 }
 
 extern "C" int cadre_grad_norms_hp(const double* norms2, int32_t C, float* stats_row, int32_t F, const double* hp, void* stream) {
   FAIL_IF(!norms2 || !stats_row || C < 1 || C > 63 || F < CADRE_PPO_STATS_FIELDS + 2 * C || BAD_HP(hp),
           "cadre_grad_norms_hp: bad argument");
-  hipLaunchKernelGGL(grad_norms_hp_kernel, dim3(1), dim3(256), 0, ST(stream), norms2, C, stats_row, F, hp);
+  hipLaunchKernelGGL(grad_norms_kernel, dim3(1), dim3(256), 0, ST(stream), norms2, C, stats_row, F, hp);
   return (int)hipGetLastError();
 }
 
@@ -2618,13 +2433,16 @@ extern "C" int cadre_explained_variance(const void* src_table, int32_t n_src, do
 // [rlo, rhi)): cadre_clip_adam_norms leaves this rank's partial per-model square norms in norms2[0..n_models) — the
 // caller sums them over the ranks (all-reduce of n_models doubles) — then cadre_clip_adam_apply runs clip + Adam on
 // the shard only.  exp_avg / exp_avg_sq point at the SHARD's state: element i of the arena is exp_avg[i - rlo].
+// The `_hp` pair reads lr (norms) and max_norm (apply) from the hyper-parameter block, as the graph forms do.
+static bool bad_shard(int64_t rlo, int64_t rhi) { return rlo < 0 || rhi <= rlo || (rlo & 3) || (rhi & 3); }
+
 extern "C" int cadre_clip_adam_norms(const float* grads, const int64_t* seg_off, int32_t n_models, double* norms2,
                                      double lr, double beta1, double beta2, int32_t* step_dev, int64_t rlo,
                                      int64_t rhi, void* stream) {
-  FAIL_IF(!grads || !seg_off || !norms2 || !step_dev || n_models < 1 || n_models > 254 || rlo < 0 || rhi <= rlo ||
-              (rlo & 3) || (rhi & 3),
+  FAIL_IF(!grads || !seg_off || !norms2 || !step_dev || n_models < 1 || n_models > 254 || bad_shard(rlo, rhi),
           "cadre_clip_adam_norms: bad argument (shard bounds must be multiples of 4 elements)");
-  hipLaunchKernelGGL(adam_prep_kernel, dim3(1), dim3(256), 0, ST(stream), norms2, n_models, step_dev, lr, beta1, beta2);
+  hipLaunchKernelGGL(adam_prep_kernel, dim3(1), dim3(256), 0, ST(stream), norms2, n_models, step_dev, lr, (const double*)nullptr,
+                     beta1, beta2, (const int32_t*)nullptr);
   hipLaunchKernelGGL(sqnorm_kernel, dim3(64, n_models), dim3(256), 0, ST(stream), grads, seg_off, norms2, rlo, rhi);
   return (int)hipGetLastError();
 }
@@ -2633,21 +2451,20 @@ extern "C" int cadre_clip_adam_apply(float* params, const float* grads, float* e
                                      const int64_t* seg_off, int32_t n_models, const double* norms2, double max_norm,
                                      double beta1, double beta2, double eps, int64_t rlo, int64_t rhi, void* stream) {
   FAIL_IF(!params || !grads || !exp_avg || !exp_avg_sq || !seg_off || !norms2 || n_models < 1 || n_models > 254 ||
-              rlo < 0 || rhi <= rlo || (rlo & 3) || (rhi & 3),
+              bad_shard(rlo, rhi),
           "cadre_clip_adam_apply: bad argument (shard bounds must be multiples of 4 elements)");
-  hipLaunchKernelGGL(adam_dev_kernel, dim3(256, n_models), dim3(256), 0, ST(stream), params, grads, exp_avg - rlo,
-                     exp_avg_sq - rlo, seg_off, norms2, n_models, (float)max_norm, (float)(1.0 - beta1), (float)beta2,
-                     (float)(1.0 - beta2), (float)eps, rlo, rhi);
+  hipLaunchKernelGGL((adam_dev_kernel<false, false>), dim3(256, n_models), dim3(256), 0, ST(stream), params, grads, exp_avg - rlo,
+                     exp_avg_sq - rlo, seg_off, norms2, n_models, (float)max_norm, (const double*)nullptr, (float)(1.0 - beta1),
+                     (float)beta2, (float)(1.0 - beta2), (float)eps, rlo, rhi, (const int32_t*)nullptr);
   return (int)hipGetLastError();
 }
 
 extern "C" int cadre_clip_adam_norms_hp(const float* grads, const int64_t* seg_off, int32_t n_models, double* norms2,
                                         const double* hp, double beta1, double beta2, int32_t* step_dev, int64_t rlo,
                                         int64_t rhi, void* stream) {
-  FAIL_IF(!grads || !seg_off || !norms2 || !step_dev || n_models < 1 || n_models > 254 || rlo < 0 || rhi <= rlo ||
-              (rlo & 3) || (rhi & 3) || BAD_HP(hp),
+  FAIL_IF(!grads || !seg_off || !norms2 || !step_dev || n_models < 1 || n_models > 254 || bad_shard(rlo, rhi) || BAD_HP(hp),
           "cadre_clip_adam_norms_hp: bad argument (shard bounds must be multiples of 4 elements; hp 8-byte aligned)");
-  hipLaunchKernelGGL(adam_prep_kernel_hp, dim3(1), dim3(256), 0, ST(stream), norms2, n_models, step_dev, hp, beta1, beta2,
+  hipLaunchKernelGGL(adam_prep_kernel, dim3(1), dim3(256), 0, ST(stream), norms2, n_models, step_dev, 0.0, hp, beta1, beta2,
                      (const int32_t*)nullptr);
   hipLaunchKernelGGL(sqnorm_kernel, dim3(64, n_models), dim3(256), 0, ST(stream), grads, seg_off, norms2, rlo, rhi);
   return (int)hipGetLastError();
@@ -2657,11 +2474,11 @@ extern "C" int cadre_clip_adam_apply_hp(float* params, const float* grads, float
                                         const int64_t* seg_off, int32_t n_models, const double* norms2, const double* hp,
                                         double beta1, double beta2, double eps, int64_t rlo, int64_t rhi, void* stream) {
   FAIL_IF(!params || !grads || !exp_avg || !exp_avg_sq || !seg_off || !norms2 || n_models < 1 || n_models > 254 ||
-              rlo < 0 || rhi <= rlo || (rlo & 3) || (rhi & 3) || BAD_HP(hp),
+              bad_shard(rlo, rhi) || BAD_HP(hp),
           "cadre_clip_adam_apply_hp: bad argument (shard bounds must be multiples of 4 elements; hp 8-byte aligned)");
-  hipLaunchKernelGGL(adam_dev_kernel_hp<false>, dim3(256, n_models), dim3(256), 0, ST(stream), params, grads, exp_avg - rlo,
-                     exp_avg_sq - rlo, seg_off, norms2, n_models, hp, (float)(1.0 - beta1), (float)beta2, (float)(1.0 - beta2),
-                     (float)eps, rlo, rhi, (const int32_t*)nullptr);
+  hipLaunchKernelGGL((adam_dev_kernel<true, false>), dim3(256, n_models), dim3(256), 0, ST(stream), params, grads, exp_avg - rlo,
+                     exp_avg_sq - rlo, seg_off, norms2, n_models, 0.f, hp, (float)(1.0 - beta1), (float)beta2,
+                     (float)(1.0 - beta2), (float)eps, rlo, rhi, (const int32_t*)nullptr);
   return (int)hipGetLastError();
 }
 

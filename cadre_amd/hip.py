@@ -328,6 +328,20 @@ def state_capture(table, n_ranges, staging, digests):
 PROFILE = None
 
 
+def _launch(name, fn, args, record):
+    """check(fn(*args), name).  When PROFILE is a list and the stream is not capturing, the call is bracketed by two events and
+    (key, flops, start, end, shape, bytes) is appended; record() -> (key, flops, shape, bytes), evaluated after the launch."""
+    if PROFILE is None or torch.cuda.is_current_stream_capturing():
+        check(fn(*args), name)
+        return
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record()
+    check(fn(*args), name)
+    e1.record()
+    key, flops, shape, nbytes = record()
+    PROFILE.append((key, flops, e0, e1, shape, nbytes))
+
+
 def gemm(A, B, Cout, M, N, K, lda, ldb, ldc, a_mode=0, b_mode=0, scale=None, shift=None, resid=None, ldr=0,
          act=0, slope=0.01, batch=1, a_z=(1, 0, 0), b_z=(1, 0, 0), c_z=(1, 0, 0), s_z=(1, 0, 0), r_z=(1, 0, 0),
          conv=None, split_k=1, tile=0, bf16=False, flags=0, seg=None):
@@ -349,25 +363,21 @@ def gemm(A, B, Cout, M, N, K, lda, ldb, ldc, a_mode=0, b_mode=0, scale=None, shi
         d.row_seg = ptr(seg[1])
     fn = lib().cadre_gemm_bf16 if bf16 else lib().cadre_gemm_f32
     name = "cadre_gemm_bf16" if bf16 else "cadre_gemm_f32"
-    if PROFILE is None or torch.cuda.is_current_stream_capturing():
-        check(fn(C.byref(d), stream()), name)
-        return
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    check(fn(C.byref(d), stream()), name)
-    e1.record()
-    nb = max(1, batch)
-    k_alg = conv[5] * conv[6] * conv[2] if conv is not None else K      # algorithmic K (the stems pad 196 -> 224 / 256)
-    esz = 2 if bf16 else 4
-    a_bytes = (M // (conv[3] * conv[4])) * conv[0] * conv[1] * conv[2] * esz if conv is not None else M * K * esz * nb
-    c_esz = 2 if (flags & 2) else 4
-    r_esz = 2 if (flags & 4) else 4
-    nbytes = a_bytes + N * k_alg * esz * nb + M * N * c_esz * nb * max(1, split_k) + (M * N * r_esz * nb if resid is not None else 0)
-    if bf16:
-        key = ("bf16", lib().cadre_gemm_bf16_pick_tile(C.byref(d)), a_mode)
-    else:
-        key = (lib().cadre_gemm_pick_tile(C.byref(d)), a_mode, b_mode)
-    PROFILE.append((key, 2.0 * M * N * k_alg * nb, e0, e1, (M, N, K, nb, split_k, seg[0] if seg is not None else 0), nbytes))
+
+    def record():
+        nb = max(1, batch)
+        k_alg = conv[5] * conv[6] * conv[2] if conv is not None else K      # algorithmic K (the stems pad 196 -> 224 / 256)
+        esz = 2 if bf16 else 4
+        a_bytes = (M // (conv[3] * conv[4])) * conv[0] * conv[1] * conv[2] * esz if conv is not None else M * K * esz * nb
+        c_esz = 2 if (flags & 2) else 4
+        r_esz = 2 if (flags & 4) else 4
+        nbytes = a_bytes + N * k_alg * esz * nb + M * N * c_esz * nb * max(1, split_k) + (M * N * r_esz * nb if resid is not None else 0)
+        if bf16:
+            key = ("bf16", lib().cadre_gemm_bf16_pick_tile(C.byref(d)), a_mode)
+        else:
+            key = (lib().cadre_gemm_pick_tile(C.byref(d)), a_mode, b_mode)
+        return key, 2.0 * M * N * k_alg * nb, (M, N, K, nb, split_k, seg[0] if seg is not None else 0), nbytes
+    _launch(name, fn, (C.byref(d), stream()), record)
 
 
 def conv3x3_c64_bf16(x, w, scale, shift, resid, out, F, H, W, relu):
@@ -376,16 +386,12 @@ def conv3x3_c64_bf16(x, w, scale, shift, resid, out, F, H, W, relu):
         raise CadreHipError("cadre_conv3x3_c64_bf16 exists only in the A/B build (CADRE_BUILD_AB=1 python -m cadre_amd.build)")
     fn = lib().cadre_conv3x3_c64_bf16
     args = (ptr(x), ptr(w), ptr(scale), ptr(shift), ptr(resid), ptr(out), F, H, W, relu, stream())
-    if PROFILE is None or torch.cuda.is_current_stream_capturing():
-        check(fn(*args), "cadre_conv3x3_c64_bf16")
-        return
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    check(fn(*args), "cadre_conv3x3_c64_bf16")
-    e1.record()
-    M = F * H * W
-    nbytes = M * 64 * 2 * (3 if resid is not None else 2) + 64 * 576 * 2
-    PROFILE.append((("bf16", 64, 2), 2.0 * M * 64 * 576, e0, e1, (M, 64, 576, 1, 1, 0), nbytes))
+
+    def record():
+        M = F * H * W
+        nbytes = M * 64 * 2 * (3 if resid is not None else 2) + 64 * 576 * 2
+        return ("bf16", 64, 2), 2.0 * M * 64 * 576, (M, 64, 576, 1, 1, 0), nbytes
+    _launch("cadre_conv3x3_c64_bf16", fn, args, record)
 
 
 def winograd_c64(x, u, scale, shift, resid, out, F, H, W, act):
@@ -393,16 +399,12 @@ def winograd_c64(x, u, scale, shift, resid, out, F, H, W, act):
     key ("wino_c64", residual); FLOPs = the EXECUTED ones (16 planes x tiles x 64 x 64)."""
     fn = lib().cadre_winograd_c64
     args = (ptr(x), ptr(u), ptr(scale), ptr(shift), ptr(resid), ptr(out), F, H, W, act, stream())
-    if PROFILE is None or torch.cuda.is_current_stream_capturing():
-        check(fn(*args), "cadre_winograd_c64")
-        return
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    check(fn(*args), "cadre_winograd_c64")
-    e1.record()
-    T = F * ((H + 1) // 2) * ((W + 1) // 2)
-    nbytes = F * H * W * 64 * 4 * (3 if resid is not None else 2) + 16 * 64 * 64 * 4
-    PROFILE.append((("wino_c64", resid is not None), 2.0 * 16 * T * 64 * 64, e0, e1, (T, 64, 64 * 16, 1, 1, 0), nbytes))
+
+    def record():
+        T = F * ((H + 1) // 2) * ((W + 1) // 2)
+        nbytes = F * H * W * 64 * 4 * (3 if resid is not None else 2) + 16 * 64 * 64 * 4
+        return ("wino_c64", resid is not None), 2.0 * 16 * T * 64 * 64, (T, 64, 64 * 16, 1, 1, 0), nbytes
+    _launch("cadre_winograd_c64", fn, args, record)
 
 
 def winograd_fused(x, V, u_frag, scale, shift, resid, out, F, H, W, Cin, N, act, m):
@@ -413,16 +415,12 @@ def winograd_fused(x, V, u_frag, scale, shift, resid, out, F, H, W, Cin, N, act,
     check(L.cadre_winograd_in_frag(ptr(x), ptr(V), F, H, W, Cin, m, stream()), "cadre_winograd_in_frag")
     fn = L.cadre_winograd_gemm_out
     args = (ptr(V), ptr(u_frag), ptr(scale), ptr(shift), ptr(resid), ptr(out), F, H, W, Cin, N, act, m, stream())
-    if PROFILE is None or torch.cuda.is_current_stream_capturing():
-        check(fn(*args), "cadre_winograd_gemm_out")
-        return
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    check(fn(*args), "cadre_winograd_gemm_out")
-    e1.record()
-    P, T = (m + 2) ** 2, F * -(-H // m) * -(-W // m)
-    nbytes = (P * T * Cin + P * N * Cin + F * H * W * N * (2 if resid is not None else 1)) * 4
-    PROFILE.append((("wgo", m, int(L.cadre_winograd_fused_ntb(T, N))), 2.0 * P * T * Cin * N, e0, e1, (T, N, Cin * P, 1, 1, 0), nbytes))
+
+    def record():
+        P, T = (m + 2) ** 2, F * -(-H // m) * -(-W // m)
+        nbytes = (P * T * Cin + P * N * Cin + F * H * W * N * (2 if resid is not None else 1)) * 4
+        return ("wgo", m, int(L.cadre_winograd_fused_ntb(T, N))), 2.0 * P * T * Cin * N, (T, N, Cin * P, 1, 1, 0), nbytes
+    _launch("cadre_winograd_gemm_out", fn, args, record)
 
 
 def conv3x3_s2(x, w_s2, scale, shift, out, F, H, W, Cin, N, act):
@@ -430,17 +428,13 @@ def conv3x3_s2(x, w_s2, scale, shift, out, F, H, W, Cin, N, act):
     conv3x3_s2_kernel<npw>, npw = window pieces per wave (9 for output rows of <= 31 pixels, else 10)."""
     fn = lib().cadre_conv3x3_s2
     args = (ptr(x), ptr(w_s2), ptr(scale), ptr(shift), ptr(out), F, H, W, Cin, N, act, stream())
-    if PROFILE is None or torch.cuda.is_current_stream_capturing():
-        check(fn(*args), "cadre_conv3x3_s2")
-        return
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    check(fn(*args), "cadre_conv3x3_s2")
-    e1.record()
-    M = F * (H // 2) * (W // 2)
-    nbytes = F * H * W * Cin * 2 + N * 9 * Cin * 2 + M * N * 2
-    npw = 9 if (256 + W // 2 + 1 + 7) // 8 <= 36 else 10
-    PROFILE.append((("s2", npw), 2.0 * M * N * 9 * Cin, e0, e1, (M, N, 9 * Cin, 1, 1, 0), nbytes))
+
+    def record():
+        M = F * (H // 2) * (W // 2)
+        nbytes = F * H * W * Cin * 2 + N * 9 * Cin * 2 + M * N * 2
+        npw = 9 if (256 + W // 2 + 1 + 7) // 8 <= 36 else 10
+        return ("s2", npw), 2.0 * M * N * 9 * Cin, (M, N, 9 * Cin, 1, 1, 0), nbytes
+    _launch("cadre_conv3x3_s2", fn, args, record)
 
 
 def conv3x3_s1x(x, x2, w_s1x, shift, out, F, H, W, C1, Cd, N, act):
@@ -449,19 +443,15 @@ def conv3x3_s1x(x, x2, w_s1x, shift, out, F, H, W, C1, Cd, N, act):
     weight stages (2; CADRE_S1X_STAGES=3 selects the symmetric-issue form)."""
     fn = lib().cadre_conv3x3_s1x
     args = (ptr(x), ptr(x2), ptr(w_s1x), ptr(shift), ptr(out), F, H, W, C1, Cd, N, act, stream())
-    if PROFILE is None or torch.cuda.is_current_stream_capturing():
-        check(fn(*args), "cadre_conv3x3_s1x")
-        return
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    check(fn(*args), "cadre_conv3x3_s1x")
-    e1.record()
-    M = F * H * W
-    nbytes = (M * C1 + M * Cd + N * (9 * C1 + Cd) + M * N) * 2          # (the shortcut reads one pixel in four of x2)
-    pa = ((256 + 2 * W + 2 + 7) // 8 * 8) // 8
-    nps = 9 if pa <= 36 else (10 if pa <= 40 else 11)
-    nstg = int(lib().cadre_conv3x3_s1x_stages(W, N))       # (what the library launches: a request for 3 stages falls back to 2 where they do not fit)
-    PROFILE.append((("s1x", nps, nstg), 2.0 * M * N * (9 * C1 + Cd), e0, e1, (M, N, 9 * C1 + Cd, 1, 1, 0), nbytes))
+
+    def record():
+        M = F * H * W
+        nbytes = (M * C1 + M * Cd + N * (9 * C1 + Cd) + M * N) * 2          # (the shortcut reads one pixel in four of x2)
+        pa = ((256 + 2 * W + 2 + 7) // 8 * 8) // 8
+        nps = 9 if pa <= 36 else (10 if pa <= 40 else 11)
+        nstg = int(lib().cadre_conv3x3_s1x_stages(W, N))       # (what the library launches: a request for 3 stages falls back to 2 where they do not fit)
+        return ("s1x", nps, nstg), 2.0 * M * N * (9 * C1 + Cd), (M, N, 9 * C1 + Cd, 1, 1, 0), nbytes
+    _launch("cadre_conv3x3_s1x", fn, args, record)
 
 
 def gemm_bf16_w128(A, B_frag, slabs, M, N, K, lda, ldc, split_k):
@@ -469,15 +459,11 @@ def gemm_bf16_w128(A, B_frag, slabs, M, N, K, lda, ldc, split_k):
     key ("gw128",): gemm_bf16_w128_kernel."""
     fn = lib().cadre_gemm_bf16_w128
     args = (ptr(A), ptr(B_frag), ptr(slabs), M, N, K, lda, ldc, split_k, stream())
-    if PROFILE is None or torch.cuda.is_current_stream_capturing():
-        check(fn(*args), "cadre_gemm_bf16_w128")
-        return
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    check(fn(*args), "cadre_gemm_bf16_w128")
-    e1.record()
-    nbytes = (M * K + N * K) * 2 + M * N * 4 * split_k
-    PROFILE.append((("gw128",), 2.0 * M * N * K, e0, e1, (M, N, K, 1, split_k, 0), nbytes))
+
+    def record():
+        nbytes = (M * K + N * K) * 2 + M * N * 4 * split_k
+        return ("gw128",), 2.0 * M * N * K, (M, N, K, 1, split_k, 0), nbytes
+    _launch("cadre_gemm_bf16_w128", fn, args, record)
 
 
 def w128_shape(W, N):
@@ -496,17 +482,13 @@ def conv3x3_w128(x, w_frag, shift, resid, out, F, H, W, Cin, N, act):
         raise CadreHipError("cadre_conv3x3_w128 exists only in the A/B build (CADRE_BUILD_AB=1 python -m cadre_amd.build)")
     fn = lib().cadre_conv3x3_w128
     args = (ptr(x), ptr(w_frag), None, ptr(shift), ptr(resid), ptr(out), F, H, W, Cin, N, act, stream())
-    if PROFILE is None or torch.cuda.is_current_stream_capturing():
-        check(fn(*args), "cadre_conv3x3_w128")
-        return
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    check(fn(*args), "cadre_conv3x3_w128")
-    e1.record()
-    M = F * H * W
-    nbytes = (M * Cin + N * 9 * Cin + M * N * (2 if resid is not None else 1)) * 2
-    mw, npw = w128_shape(W, N)
-    PROFILE.append((("w128", mw, npw, resid is not None), 2.0 * M * N * 9 * Cin, e0, e1, (M, N, 9 * Cin, 1, 1, 0), nbytes))
+
+    def record():
+        M = F * H * W
+        nbytes = (M * Cin + N * 9 * Cin + M * N * (2 if resid is not None else 1)) * 2
+        mw, npw = w128_shape(W, N)
+        return ("w128", mw, npw, resid is not None), 2.0 * M * N * 9 * Cin, (M, N, 9 * Cin, 1, 1, 0), nbytes
+    _launch("cadre_conv3x3_w128", fn, args, record)
 
 
 def conv3x3_ring(x, w_ring, scale, shift, resid, out, F, H, W, Cin, N, act):
@@ -518,19 +500,15 @@ def conv3x3_ring(x, w_ring, scale, shift, resid, out, F, H, W, Cin, N, act):
     flags = (1 if bf else 0) | (2 if out.dtype == torch.bfloat16 else 0) | (4 if (resid is not None and resid.dtype == torch.bfloat16) else 0)
     fn = lib().cadre_conv3x3_ring
     args = (ptr(x), ptr(w_ring), ptr(scale), ptr(shift), ptr(resid), ptr(out), F, H, W, Cin, N, act, flags, stream())
-    if PROFILE is None or torch.cuda.is_current_stream_capturing():
-        check(fn(*args), "cadre_conv3x3_ring")
-        return
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    check(fn(*args), "cadre_conv3x3_ring")
-    e1.record()
-    M, esz = F * H * W, (2 if bf else 4)
-    nbytes = M * Cin * esz + N * 9 * Cin * esz + M * N * out.element_size() + (M * N * resid.element_size() if resid is not None else 0)
-    code = lib().cadre_conv3x3_ring_ntile(F, H, W, Cin, N, 1 if bf else 0)      # ntile + 1000 * WVM + 100000 * ping-pong + 1000000 * G
-    res = 0 if resid is None else (2 if resid.dtype == torch.bfloat16 else 1)
-    key = ("ring", bf, code % 1000, res, out.dtype == torch.bfloat16, code // 1000 % 100, code // 100000 % 10, code // 1000000)
-    PROFILE.append((key, 2.0 * M * N * 9 * Cin, e0, e1, (M, N, 9 * Cin, 1, 1, 0), nbytes))
+
+    def record():
+        M, esz = F * H * W, (2 if bf else 4)
+        nbytes = M * Cin * esz + N * 9 * Cin * esz + M * N * out.element_size() + (M * N * resid.element_size() if resid is not None else 0)
+        code = lib().cadre_conv3x3_ring_ntile(F, H, W, Cin, N, 1 if bf else 0)      # ntile + 1000 * WVM + 100000 * ping-pong + 1000000 * G
+        res = 0 if resid is None else (2 if resid.dtype == torch.bfloat16 else 1)
+        key = ("ring", bf, code % 1000, res, out.dtype == torch.bfloat16, code // 1000 % 100, code // 100000 % 10, code // 1000000)
+        return key, 2.0 * M * N * 9 * Cin, (M, N, 9 * Cin, 1, 1, 0), nbytes
+    _launch("cadre_conv3x3_ring", fn, args, record)
 
 
 def deconv3x3_s2(x, x_zstride, w, scale, shift, out, Z, F, H, W, Cin, Cout, oph, opw, act=0, slope=0.01):
@@ -539,16 +517,12 @@ def deconv3x3_s2(x, x_zstride, w, scale, shift, out, Z, F, H, W, Cin, Cout, oph,
     map's last row / column does not have is multiplied as zeros)."""
     fn = lib().cadre_deconv3x3_s2
     args = (ptr(x), x_zstride, ptr(w), ptr(scale), ptr(shift), ptr(out), Z, F, H, W, Cin, Cout, oph, opw, act, slope, stream())
-    if PROFILE is None or torch.cuda.is_current_stream_capturing():
-        check(fn(*args), "cadre_deconv3x3_s2")
-        return
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    check(fn(*args), "cadre_deconv3x3_s2")
-    e1.record()
-    Ho, Wo = 2 * H - 1 + oph, 2 * W - 1 + opw
-    nbytes = (F * H * W * Cin * (Z if x_zstride else 1) + Z * 9 * Cin * Cout + Z * F * Ho * Wo * Cout) * 4
-    PROFILE.append((("deconv", Cin, Cout), 2.0 * Z * F * H * W * 9 * Cin * Cout, e0, e1, (F * H * W, Cout, 9 * Cin, Z, 1, 0), nbytes))
+
+    def record():
+        Ho, Wo = 2 * H - 1 + oph, 2 * W - 1 + opw
+        nbytes = (F * H * W * Cin * (Z if x_zstride else 1) + Z * 9 * Cin * Cout + Z * F * Ho * Wo * Cout) * 4
+        return ("deconv", Cin, Cout), 2.0 * Z * F * H * W * 9 * Cin * Cout, (F * H * W, Cout, 9 * Cin, Z, 1, 0), nbytes
+    _launch("cadre_deconv3x3_s2", fn, args, record)
 
 
 def deconv3x3_s2_out(x, w, bias, logits, cls, sig, F, H, W, Cout, oph=1, opw=1):
@@ -556,13 +530,9 @@ def deconv3x3_s2_out(x, w, bias, logits, cls, sig, F, H, W, Cout, oph=1, opw=1):
     that output is not wanted.  Profiling key ("deconv_out", Cout)."""
     fn = lib().cadre_deconv3x3_s2_out
     args = (ptr(x), ptr(w), ptr(bias), ptr(logits), ptr(cls), ptr(sig), F, H, W, Cout, oph, opw, stream())
-    if PROFILE is None or torch.cuda.is_current_stream_capturing():
-        check(fn(*args), "cadre_deconv3x3_s2_out")
-        return
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    check(fn(*args), "cadre_deconv3x3_s2_out")
-    e1.record()
-    Ho, Wo = 2 * H - 1 + oph, 2 * W - 1 + opw
-    nbytes = F * H * W * 32 * 4 + F * Ho * Wo * ((Cout * 4 if logits is not None else 0) + (1 if cls is not None else 0) + (4 if sig is not None else 0))
-    PROFILE.append((("deconv_out", Cout), 2.0 * F * H * W * 9 * 32 * Cout, e0, e1, (F * H * W, Cout, 9 * 32, 1, 1, 0), nbytes))
+
+    def record():
+        Ho, Wo = 2 * H - 1 + oph, 2 * W - 1 + opw
+        nbytes = F * H * W * 32 * 4 + F * Ho * Wo * ((Cout * 4 if logits is not None else 0) + (1 if cls is not None else 0) + (4 if sig is not None else 0))
+        return ("deconv_out", Cout), 2.0 * F * H * W * 9 * 32 * Cout, (F * H * W, Cout, 9 * 32, 1, 1, 0), nbytes
+    _launch("cadre_deconv3x3_s2_out", fn, args, record)

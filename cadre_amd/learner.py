@@ -940,6 +940,30 @@ class PPOLearnerHIP:
                 gc.enable()
         return g
 
+    def _ppo_launch(self, w, B, inv_b, ord_t):
+        """The PPO-loss launch of the plain, stats, device-hyper and ordinal modes: entry point and arguments from the flags.
+        cadre_ppo_loss[_stats][_hp] take the block OR the four scalars, and the stats arguments only as `_stats`;
+        cadre_ppo_loss_ord takes all of them (hp NULL = by-value scalars, stats row NULL = no diagnostics) and the rank table."""
+        a, S = self.a, self.S
+        Z, NP, O3, dO3 = a.Z, a.NP, w["O3"], w["dO3"]
+        hp, stats, ordinal = self._hp_on, self._loss_stats(), ord_t is not None
+        name = "cadre_ppo_loss_ord" if ordinal else "cadre_ppo_loss%s%s" % ("_stats" if stats else "", "_hp" if hp else "")
+        srow, sscr = self._stats_ws(w, B) if stats else (None, None)
+        args = (hip.ptr(O3), NP, 2 * B * NP, hip.ptr(O3[1]), NP, 2 * B * NP,
+                hip.ptr(w["actions"]), hip.ptr(w["commands"]), hip.ptr(w["old_values"]),
+                hip.ptr(w["returns"]), hip.ptr(w["old_logp"]), hip.ptr(w["adv"]), B, a.C, a.n_out[0], a.n_out[1])
+        if hp or ordinal:
+            args += (hip.ptr(self._hp) if hp else None,)
+        if ordinal or not hp:
+            args += (self.clip, self.vc, self.cc, self.ec)
+        args += (inv_b, hip.ptr(w["losses"]), hip.ptr(dO3), hip.ptr(dO3[1]), hip.ptr(w["loss_scratch"]), hip.ptr(w["sync"][Z * S:]))
+        if stats or ordinal:
+            args += (hip.ptr(srow), srow.shape[1] if stats else 0, hip.ptr(sscr), self._loss_tkl(),
+                     hip.ptr(self._stop) if (stats and self.target_kl is not None) else None)
+        if ordinal:
+            args += (hip.ptr(ord_t),)
+        hip.check(getattr(hip.lib(), name)(*args, hip.stream()), name)
+
     def _update_body(self, B, inv_b, sorted_rows=False, part="all"):
         """part: "all", or the three cuts of the same launch sequence: "front" (forward, loss, MLP-tower backward, dh_S),
         "mid" (backward through time + the weight gradients of the steer nets, arena nets 0 .. Z/2 - 1), "back" (the weight
@@ -968,54 +992,8 @@ class PPOLearnerHIP:
             self._aux_launch(w, B, inv_b, sorted_rows)  # critic + KL clone against the recorded table: the rest is indifferent
         elif front and self.loss_mode == "ppo+suggest":
             self._sug_launch(w, B, inv_b)               # PPO + the event priors on marked rows: the rest is indifferent
-        elif front and ord_t is not None:
-            # one entry point for the four modes: hp NULL = by-value scalars, stats row NULL = no diagnostics
-            stats = self._loss_stats()
-            srow, sscr = self._stats_ws(w, B) if stats else (None, None)
-            tkl = self._loss_tkl()
-            hip.check(L.cadre_ppo_loss_ord(hip.ptr(O3), NP, 2 * B * NP, hip.ptr(O3[1]), NP, 2 * B * NP,
-                                           hip.ptr(w["actions"]), hip.ptr(w["commands"]), hip.ptr(w["old_values"]),
-                                           hip.ptr(w["returns"]), hip.ptr(w["old_logp"]), hip.ptr(w["adv"]), B, C,
-                                           a.n_out[0], a.n_out[1], hip.ptr(self._hp) if self._hp_on else None,
-                                           self.clip, self.vc, self.cc, self.ec, inv_b,
-                                           hip.ptr(w["losses"]), hip.ptr(dO3), hip.ptr(dO3[1]), hip.ptr(w["loss_scratch"]),
-                                           hip.ptr(w["sync"][Z * S:]), hip.ptr(srow), srow.shape[1] if stats else 0,
-                                           hip.ptr(sscr), tkl,
-                                           hip.ptr(self._stop) if (stats and self.target_kl is not None) else None,
-                                           hip.ptr(ord_t), st), "cadre_ppo_loss_ord")
-        elif front and self._hp_on:
-            loss_args = (hip.ptr(O3), NP, 2 * B * NP, hip.ptr(O3[1]), NP, 2 * B * NP,
-                         hip.ptr(w["actions"]), hip.ptr(w["commands"]), hip.ptr(w["old_values"]),
-                         hip.ptr(w["returns"]), hip.ptr(w["old_logp"]), hip.ptr(w["adv"]), B, C,
-                         a.n_out[0], a.n_out[1], hip.ptr(self._hp), inv_b,
-                         hip.ptr(w["losses"]), hip.ptr(dO3), hip.ptr(dO3[1]), hip.ptr(w["loss_scratch"]),
-                         hip.ptr(w["sync"][Z * S:]))
-            if self._loss_stats():
-                srow, sscr = self._stats_ws(w, B)
-                tkl = self._loss_tkl()
-                hip.check(L.cadre_ppo_loss_stats_hp(*loss_args, hip.ptr(srow), srow.shape[1], hip.ptr(sscr), tkl,
-                                                    hip.ptr(self._stop) if self.target_kl is not None else None, st),
-                          "cadre_ppo_loss_stats_hp")
-            else:
-                hip.check(L.cadre_ppo_loss_hp(*loss_args, st), "cadre_ppo_loss_hp")
-        elif front and self._loss_stats():
-            srow, sscr = self._stats_ws(w, B)
-            tkl = self._loss_tkl()
-            hip.check(L.cadre_ppo_loss_stats(hip.ptr(O3), NP, 2 * B * NP, hip.ptr(O3[1]), NP, 2 * B * NP,
-                                             hip.ptr(w["actions"]), hip.ptr(w["commands"]), hip.ptr(w["old_values"]),
-                                             hip.ptr(w["returns"]), hip.ptr(w["old_logp"]), hip.ptr(w["adv"]), B, C,
-                                             a.n_out[0], a.n_out[1], self.clip, self.vc, self.cc, self.ec, inv_b,
-                                             hip.ptr(w["losses"]), hip.ptr(dO3), hip.ptr(dO3[1]), hip.ptr(w["loss_scratch"]),
-                                             hip.ptr(w["sync"][Z * S:]), hip.ptr(srow), srow.shape[1], hip.ptr(sscr), tkl,
-                                             hip.ptr(self._stop) if self.target_kl is not None else None, st),
-                      "cadre_ppo_loss_stats")
         elif front:
-            hip.check(L.cadre_ppo_loss(hip.ptr(O3), NP, 2 * B * NP, hip.ptr(O3[1]), NP, 2 * B * NP,
-                                       hip.ptr(w["actions"]), hip.ptr(w["commands"]), hip.ptr(w["old_values"]),
-                                       hip.ptr(w["returns"]), hip.ptr(w["old_logp"]), hip.ptr(w["adv"]), B, C,
-                                       a.n_out[0], a.n_out[1], self.clip, self.vc, self.cc, self.ec, inv_b,
-                                       hip.ptr(w["losses"]), hip.ptr(dO3), hip.ptr(dO3[1]), hip.ptr(w["loss_scratch"]),
-                                       hip.ptr(w["sync"][Z * S:]), st), "cadre_ppo_loss")
+            self._ppo_launch(w, B, inv_b, ord_t)
         # ---------------- backward: MLP towers (16 = 2Z batched)
         Gr = a.grads
         pP, gP = a.params[a.P0:], Gr[a.P0:]
@@ -1090,49 +1068,26 @@ class PPOLearnerHIP:
         fused = self.fused_pack
         gated = self.target_kl is not None
         hp = self._hp_on
+        b1, b2, eps = float(betas[0]), float(betas[1]), float(eps)
         if hp:      # lr and max_grad_norm live in the block: a new value is a copy, not a new graph
             self._sync_hyper(lr, max_grad_norm)
-            key = ("adam", "hp", float(betas[0]), float(betas[1]), float(eps), fused) + (("gated",) if gated else ())
+            key = ("adam", "hp", b1, b2, eps, fused) + (("gated",) if gated else ())
         else:
-            key = ("adam", float(lr), float(max_grad_norm), float(betas[0]), float(betas[1]), float(eps), fused) + (("gated",) if gated else ())
+            key = ("adam", float(lr), float(max_grad_norm), b1, b2, eps, fused) + (("gated",) if gated else ())
         if fused:
             self._alloc_wp()
 
-        def body_hp():
+        def body():
+            # cadre_clip_adam_[pack_]graph[_hp][_gated]: the block stands where max_norm and lr stand by value
             L = hip.lib()
+            scal = (hip.ptr(self._hp),) if hp else (float(max_grad_norm), float(lr))
             head = (hip.ptr(a.params), hip.ptr(a.grads), hip.ptr(a.exp_avg), hip.ptr(a.exp_avg_sq), hip.ptr(a.seg_off),
-                    2 * a.Z, hip.ptr(a.norms2), hip.ptr(self._hp), key[2], key[3], key[4], hip.ptr(a.step_dev))
+                    2 * a.Z, hip.ptr(a.norms2)) + scal + (b1, b2, eps, hip.ptr(a.step_dev))
             pack = (a.Z, a.size_L, a.o_whh, a.H4, a.DP, a.D, hip.ptr(self._wp[0]), hip.ptr(self._wp[1]),
                     self._wp.stride(1)) if fused else ()
             tail = ((hip.ptr(self._stop),) if gated else ()) + (hip.stream(),)
-            name = "cadre_clip_adam_%sgraph_hp%s" % ("pack_" if fused else "", "_gated" if gated else "")
+            name = "cadre_clip_adam_%sgraph%s%s" % ("pack_" if fused else "", "_hp" if hp else "", "_gated" if gated else "")
             hip.check(getattr(L, name)(*(head + pack + tail)), name)
-
-        def body():
-            if hp:
-                body_hp()
-            elif gated and fused:
-                hip.check(hip.lib().cadre_clip_adam_pack_graph_gated(
-                    hip.ptr(a.params), hip.ptr(a.grads), hip.ptr(a.exp_avg), hip.ptr(a.exp_avg_sq), hip.ptr(a.seg_off),
-                    2 * a.Z, hip.ptr(a.norms2), key[2], key[1], key[3], key[4], key[5], hip.ptr(a.step_dev),
-                    a.Z, a.size_L, a.o_whh, a.H4, a.DP, a.D, hip.ptr(self._wp[0]), hip.ptr(self._wp[1]), self._wp.stride(1),
-                    hip.ptr(self._stop), hip.stream()), "cadre_clip_adam_pack_graph_gated")
-            elif gated:
-                hip.check(hip.lib().cadre_clip_adam_graph_gated(
-                    hip.ptr(a.params), hip.ptr(a.grads), hip.ptr(a.exp_avg), hip.ptr(a.exp_avg_sq), hip.ptr(a.seg_off),
-                    2 * a.Z, hip.ptr(a.norms2), key[2], key[1], key[3], key[4], key[5], hip.ptr(a.step_dev),
-                    hip.ptr(self._stop), hip.stream()), "cadre_clip_adam_graph_gated")
-            elif fused:
-                hip.check(hip.lib().cadre_clip_adam_pack_graph(
-                    hip.ptr(a.params), hip.ptr(a.grads), hip.ptr(a.exp_avg), hip.ptr(a.exp_avg_sq), hip.ptr(a.seg_off),
-                    2 * a.Z, hip.ptr(a.norms2), key[2], key[1], key[3], key[4], key[5], hip.ptr(a.step_dev),
-                    a.Z, a.size_L, a.o_whh, a.H4, a.DP, a.D, hip.ptr(self._wp[0]), hip.ptr(self._wp[1]), self._wp.stride(1),
-                    hip.stream()), "cadre_clip_adam_pack_graph")
-            else:
-                hip.check(hip.lib().cadre_clip_adam_graph(
-                    hip.ptr(a.params), hip.ptr(a.grads), hip.ptr(a.exp_avg), hip.ptr(a.exp_avg_sq), hip.ptr(a.seg_off),
-                    2 * a.Z, hip.ptr(a.norms2), key[2], key[1], key[3], key[4], key[5], hip.ptr(a.step_dev),
-                    hip.stream()), "cadre_clip_adam_graph")
 
         def done():
             self._adam_fresh = self._pkey() if fused else None      # (the copies now match the stepped parameters)
@@ -1177,37 +1132,28 @@ class PPOLearnerHIP:
             a.exp_avg_sq = torch.zeros(hi - lo, device=a.device)
         a.step += 1
         L, st, nm = hip.lib(), hip.stream(), 2 * a.Z
-        if self._hp_on:
+        hp, b1, b2 = self._hp_on, float(betas[0]), float(betas[1])
+        if hp:      # the `_hp` pair: the block stands where lr (norms) and max_norm (apply) stand by value
             self._sync_hyper(lr, max_grad_norm)
-            hip.check(L.cadre_clip_adam_norms_hp(hip.ptr(a.grads), hip.ptr(a.seg_off), nm, hip.ptr(a.norms2), hip.ptr(self._hp),
-                                                 float(betas[0]), float(betas[1]), hip.ptr(a.step_dev), lo, hi, st),
-                      "cadre_clip_adam_norms_hp")
-            all_reduce_norms(a.norms2[:nm])
-            hip.check(L.cadre_clip_adam_apply_hp(hip.ptr(a.params), hip.ptr(a.grads), hip.ptr(a.exp_avg), hip.ptr(a.exp_avg_sq),
-                                                 hip.ptr(a.seg_off), nm, hip.ptr(a.norms2), hip.ptr(self._hp),
-                                                 float(betas[0]), float(betas[1]), float(eps), lo, hi, st),
-                      "cadre_clip_adam_apply_hp")
-            return self._write_norms()
-        hip.check(L.cadre_clip_adam_norms(hip.ptr(a.grads), hip.ptr(a.seg_off), nm, hip.ptr(a.norms2), float(lr),
-                                          float(betas[0]), float(betas[1]), hip.ptr(a.step_dev), lo, hi, st),
-                  "cadre_clip_adam_norms")
+        sfx = "_hp" if hp else ""
+        lr_arg, norm_arg = (hip.ptr(self._hp), hip.ptr(self._hp)) if hp else (float(lr), float(max_grad_norm))
+        hip.check(getattr(L, "cadre_clip_adam_norms" + sfx)(
+            hip.ptr(a.grads), hip.ptr(a.seg_off), nm, hip.ptr(a.norms2), lr_arg, b1, b2, hip.ptr(a.step_dev), lo, hi, st),
+            "cadre_clip_adam_norms" + sfx)
         all_reduce_norms(a.norms2[:nm])
-        hip.check(L.cadre_clip_adam_apply(hip.ptr(a.params), hip.ptr(a.grads), hip.ptr(a.exp_avg), hip.ptr(a.exp_avg_sq),
-                                          hip.ptr(a.seg_off), nm, hip.ptr(a.norms2), float(max_grad_norm),
-                                          float(betas[0]), float(betas[1]), float(eps), lo, hi, st),
-                  "cadre_clip_adam_apply")
+        hip.check(getattr(L, "cadre_clip_adam_apply" + sfx)(
+            hip.ptr(a.params), hip.ptr(a.grads), hip.ptr(a.exp_avg), hip.ptr(a.exp_avg_sq), hip.ptr(a.seg_off), nm,
+            hip.ptr(a.norms2), norm_arg, b1, b2, float(eps), lo, hi, st), "cadre_clip_adam_apply" + sfx)
         self._write_norms()
 
     def _write_norms(self):
         """The per-model gradient norms of the optimiser step just enqueued into the pending stats row (one launch after
         the step's graph; nothing read on the host)."""
         row, self._norm_row = self._norm_row, None
-        if row is not None and self._hp_on:      # (also the learning rate the step used: field hip.PPO_STATS_LR of head 0)
-            hip.check(hip.lib().cadre_grad_norms_hp(hip.ptr(self.a.norms2), self.a.C, hip.ptr(row), row.shape[-1],
-                                                    hip.ptr(self._hp), hip.stream()), "cadre_grad_norms_hp")
-        elif row is not None:
-            hip.check(hip.lib().cadre_grad_norms(hip.ptr(self.a.norms2), self.a.C, hip.ptr(row), row.shape[-1], hip.stream()),
-                      "cadre_grad_norms")
+        if row is not None:      # (`_hp`: also the learning rate the step used, field hip.PPO_STATS_LR of head 0)
+            name = "cadre_grad_norms_hp" if self._hp_on else "cadre_grad_norms"
+            blk = (hip.ptr(self._hp),) if self._hp_on else ()
+            hip.check(getattr(hip.lib(), name)(hip.ptr(self.a.norms2), self.a.C, hip.ptr(row), row.shape[-1], *blk, hip.stream()), name)
 
     # ------------------------------------------------------------------ inference (act / get_value)
     def infer(self, feats, commands, h0=None, c0=None):

@@ -9,7 +9,15 @@ from collections import OrderedDict
 f = sorted(glob.glob(sys.argv[1] + "/**/*kernel_trace.csv", recursive=True))[0]
 rows = list(csv.DictReader(open(f)))
 rows.sort(key=lambda r: int(r["Start_Timestamp"]))
-idx = [i for i, r in enumerate(rows) if r["Kernel_Name"].startswith("adam_dev_kernel")]
+
+
+def is_kernel(r, prefix):
+    """(a templated kernel demangles with its return type in front: "void adam_dev_kernel<false, false>(...)")"""
+    n = r["Kernel_Name"]
+    return (n[5:] if n.startswith("void ") else n).startswith(prefix)
+
+
+idx = [i for i, r in enumerate(rows) if is_kernel(r, "adam_dev_kernel")]
 a, b = idx[len(idx) // 2], idx[len(idx) // 2 + 1]
 agg = OrderedDict()
 for r in rows[a + 1:b + 1]:
@@ -43,7 +51,7 @@ if len(sys.argv) > 2:                                  # gap analysis of the las
     # idle time inside the update phase of the round
     a0, a1 = first, last8[-1]
     lo = a0
-    while lo > 0 and not rows[lo - 1]["Kernel_Name"].startswith("adam_dev") and (int(rows[lo]["Start_Timestamp"]) - int(rows[lo - 1]["End_Timestamp"])) < 200000:
+    while lo > 0 and not is_kernel(rows[lo - 1], "adam_dev") and (int(rows[lo]["Start_Timestamp"]) - int(rows[lo - 1]["End_Timestamp"])) < 200000:
         lo -= 1
     tot = (int(rows[a1]["End_Timestamp"]) - int(rows[lo]["Start_Timestamp"])) / 1e3
     kb = sum((int(r["End_Timestamp"]) - int(r["Start_Timestamp"])) / 1e3 for r in rows[lo:a1 + 1])
