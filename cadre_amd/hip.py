@@ -200,6 +200,18 @@ SYMBOLS = {
     "cadre_deconv3x3_s2_out": [vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, vp],
     "cadre_argmax_rows": [vp, i64, i32, i32, vp, vp],
     "cadre_bc_head": [vp, i64, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, f32, vp],
+    # self-imitation: logits, ldl, l_ns, values, ldv, v_ns, actions, commands, old_values, returns, old_logp, adv, row_kind, B,
+    # C, K_steer, K_throttle, hp (may be NULL), clip, value_coeff, clip_coeff, ent_coeff, inv_b, sil_coeff, sil_value_coeff,
+    # inv_bs, losses[3], sil_losses[2], sil_w, dlogits, dvalues, scratch, SIL scratch, poison, PPO stats row (may be NULL), F,
+    # stats scratch, target_kl, stop, SIL stats row (may be NULL), its F, ord, stream / {rewards, masks, time_limits or 0,
+    # value_preds, returns, flags, q} table, n, T, gamma, state (may be NULL), clip_r, tail, alpha, prio_eps, stream /
+    # q, Rcap, filled rows, u, n, idx, scratch, stream / q, Rcap, idx, n, sil_w, pos (NULL: identity), B, B_ppo, alpha,
+    # prio_eps, stream
+    "cadre_ppo_sil_loss": [vp, i64, i64, vp, i64, i64, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, vp, f32, f32, f32, f32,
+                           f32, f32, f32, f32, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, vp, f32, vp, vp, i32, vp, vp],
+    "cadre_sil_prepare": [vp, i32, i32, f32, vp, f32, i32, f64, f64, vp],
+    "cadre_sil_draw": [vp, i64, i64, vp, i32, vp, vp, vp],
+    "cadre_sil_scatter": [vp, i64, vp, i32, vp, vp, i32, i32, f64, f64, vp],
 }
 # entry points of the A/B build only (include/cadre_hip_ab.h; CADRE_BUILD_AB=1 python -m cadre_amd.build, then
 # CADRE_HIP_LIB=.../libcadre_hip_ab.so): bound when the loaded library has them
@@ -260,12 +272,16 @@ HP_DEMO_COEFF, HP_DEMO_VALUE_COEFF = 10, 11
 HP_INDEX = dict(HP, demo_coeff=HP_DEMO_COEFF, demo_value_coeff=HP_DEMO_VALUE_COEFF)
 # a third reserved field (the enumerator CADRE_HP_SUGGEST_COEFF), read by cadre_ppo_sug_loss only; set_hyper(suggest_coeff=)
 HP_SUGGEST_COEFF = 12
+# two more (the enumerators CADRE_HP_SIL_COEFF / CADRE_HP_SIL_VALUE_COEFF), read by cadre_ppo_sil_loss only;
+# set_hyper(sil_coeff=, sil_value_coeff=)
+HP_SIL_COEFF, HP_SIL_VALUE_COEFF = 13, 14
 PPO_STATS_LR = 7      # CADRE_PPO_STATS_LR: field of head 0 of a stats row that cadre_grad_norms_hp fills with the step's lr
 
 PPO_STATS_FIELDS = 8  # CADRE_PPO_STATS_FIELDS (include/cadre_hip.h): loss diagnostics per head before the gradient norms
 BC_STATS_FIELDS = 6   # CADRE_BC_STATS_FIELDS: accuracy, NLL, entropy, |v - R|, weight sum, rows counted (means over inv_b)
 AUX_STATS_FIELDS = 6  # CADRE_AUX_STATS_FIELDS: mean KL, max KL, mean |v - R|, mean entropy, mean (v - R)^2, rows counted
 SUG_STATS_FIELDS = 4  # CADRE_SUG_STATS_FIELDS: marked rows, mean KL over the minibatch, max KL, mean p[prior's mode] over marked rows
+SIL_STATS_FIELDS = 6  # CADRE_SIL_STATS_FIELDS: mean w, share w > 0, mean -lp, mean |R - v|, max w, rows counted (over the SIL rows)
 VTRACE_DIAG_FIELDS = 4  # CADRE_VTRACE_DIAG_FIELDS: mean ratio, share truncated, max |log ratio|, effective-sample share
 
 RS_SCALE, RS_CARRY = 6, 8 # CADRE_RS_SCALE / CADRE_RS_CARRY: the return-statistics block (count, mean, M2 per head first)

@@ -120,11 +120,14 @@ class PPOLearnerHIP:
         self._sug_tables = None    # (prior: device float32 [2][Z + 1][64], Z); the address and Z are part of the hipGraph keys
         self._sug_ord = None       # the rank table of two categorical heads (the entry point wants one), when the arena has none
         self._last_sug_stats = None  # workspace(B)["sug_stats"] of the "ppo+suggest" update that ran last
+        # "ppo+sil": cadre_ppo_sil_loss — PPO rows and self-imitation rows (the agent's own past rollouts) in one minibatch
+        self._sil = (0.0, 0.0)     # (sil_coeff, sil_value_coeff)
+        self._sil_rows = None      # B_ppo: the leading unsorted rows of the minibatch that are PPO rows (set_sil_rows)
         hip.lib()
 
     # ------------------------------------------------------------------ loss selection
     def set_loss(self, mode, label_smoothing=0.0, bc_coeff=1.0, demo_coeff=None, demo_value_coeff=None, beta_clone=1.0,
-                 aux_value_coeff=1.0, suggest_coeff=None):
+                 aux_value_coeff=1.0, suggest_coeff=None, sil_coeff=None, sil_value_coeff=None):
         """"ppo" (default): the clipped-surrogate loss.  "bc": behaviour cloning — cross-entropy against the demonstrated bin
         (workspace `actions`; -1 = no label for that head) with `label_smoothing` in [0, 1) and weight `bc_coeff`, the critic
         regressed on workspace `returns`, the learner's own value_coeff / ent_coeff, per-row weights from the `adv` slot;
@@ -151,9 +154,29 @@ class PPOLearnerHIP:
         (cadre_ppo_sug_loss, ONE launch).  Diagnostics, the KL gate, the adaptive lr and rank consensus work as in "ppo" and
         see what they see there.  In device-hyper mode the coefficient lives in the block (set_hyper(suggest_coeff=)): a
         changed value needs no new graph.  None keeps the current coefficient.  The suggestion loss / statistics of a step
-        (hip.SUG_STATS_FIELDS per head) are in workspace(B)["sug_losses"] / ["sug_stats"]."""
-        if mode not in ("ppo", "bc", "ppo+demo", "aux", "ppo+suggest"):
-            raise ValueError("set_loss: mode %r (known: 'ppo', 'bc', 'ppo+demo', 'aux', 'ppo+suggest')" % (mode,))
+        (hip.SUG_STATS_FIELDS per head) are in workspace(B)["sug_losses"] / ["sug_stats"].
+        "ppo+sil": the clipped-surrogate loss on the first set_sil_rows() unsorted rows of the minibatch and the
+        self-imitation terms on the rest — w = max(R - v, 0) with R from the `returns` column, `sil_coeff` * mean(-lp w) +
+        `sil_value_coeff` * mean(0.5 w^2) over the SIL rows — in ONE launch (cadre_ppo_sil_loss).  Diagnostics, the KL gate,
+        the adaptive lr and rank consensus work as in "ppo" and see the PPO rows only.  In device-hyper mode the two
+        coefficients live in the block (set_hyper(sil_coeff=, sil_value_coeff=)): a changed value needs no new graph.  None
+        keeps the current coefficient.  The SIL losses / statistics / per-row w of a step are in workspace(B)["sil_losses"] /
+        ["sil_stats"] / ["sil_w"] (static tensors, as the kinds in ["row_kind"])."""
+        if mode not in ("ppo", "bc", "ppo+demo", "aux", "ppo+suggest", "ppo+sil"):
+            raise ValueError("set_loss: mode %r (known: 'ppo', 'bc', 'ppo+demo', 'aux', 'ppo+suggest', 'ppo+sil')" % (mode,))
+        if mode == "ppo+sil":
+            if any(isinstance(v, bool) for v in (sil_coeff, sil_value_coeff)):
+                raise ValueError("set_loss: sil_coeff=%r, sil_value_coeff=%r" % (sil_coeff, sil_value_coeff))
+            try:
+                sc = self._sil[0] if sil_coeff is None else float(sil_coeff)
+                svc = self._sil[1] if sil_value_coeff is None else float(sil_value_coeff)
+            except (TypeError, ValueError):
+                raise ValueError("set_loss: sil_coeff=%r, sil_value_coeff=%r" % (sil_coeff, sil_value_coeff))
+            if not (np.isfinite(sc) and np.isfinite(svc)):
+                raise ValueError("set_loss: sil_coeff=%r, sil_value_coeff=%r" % (sil_coeff, sil_value_coeff))
+            self._sil = (sc, svc)
+            if self._hp_on:
+                self.set_hyper(sil_coeff=sc, sil_value_coeff=svc)
         if mode == "ppo+suggest":
             if isinstance(suggest_coeff, bool):
                 raise ValueError("set_loss: suggest_coeff=%r" % (suggest_coeff,))
@@ -237,6 +260,54 @@ class PPOLearnerHIP:
                                         hip.ptr(self._stop) if (stats and self.target_kl is not None) else None,
                                         hip.ptr(w["demo_stats"]), hip.BC_STATS_FIELDS, hip.ptr(ord_t), st),
                   "cadre_ppo_demo_loss")
+
+    # ------------------------------------------------------------------ self-imitation
+    def set_sil_rows(self, B_ppo):
+        """"ppo+sil": unsorted rows 0 .. B_ppo - 1 of the next minibatches are PPO rows, the rest SIL rows."""
+        if B_ppo is not None and int(B_ppo) < 0:
+            raise ValueError("set_sil_rows: B_ppo=%r" % (B_ppo,))
+        self._sil_rows = None if B_ppo is None else int(B_ppo)
+
+    def _sil_ws(self, w, B):
+        """The static tensors of the "ppo+sil" loss in workspace(B)."""
+        if "sil_w" not in w:
+            dev, nblk = self.a.device, (B + 15) // 16
+            if "row_kind" not in w:
+                w["row_kind"] = torch.zeros(2, B, dtype=torch.int32, device=dev)
+            w["sil_w"] = torch.zeros(2, B, device=dev)
+            w["sil_losses"] = torch.zeros(2, device=dev)
+            w["sil_stats"] = torch.zeros(2, hip.SIL_STATS_FIELDS, device=dev)
+            w["sil_scratch"] = torch.zeros(2 * nblk * (2 + hip.SIL_STATS_FIELDS), device=dev)
+        return w["sil_w"]
+
+    def _sil_launch(self, w, B, inv_b, sorted_rows):
+        """cadre_mix_row_kinds + cadre_ppo_sil_loss on the tower outputs in workspace(B), in the place of the PPO loss."""
+        a, S = self.a, self.S
+        L, st = hip.lib(), hip.stream()
+        O3, dO3, NP = w["O3"], w["dO3"], a.NP
+        B_ppo = self._sil_rows
+        if B_ppo is None or B_ppo > B:
+            raise hip.CadreHipError("the 'ppo+sil' loss needs set_sil_rows(B_ppo) with 0 <= B_ppo <= B (got %r, B = %d)" % (B_ppo, B))
+        self._sil_ws(w, B)
+        hip.check(L.cadre_mix_row_kinds(hip.ptr(w["pos"]) if sorted_rows else None, B, B_ppo, hip.ptr(w["row_kind"]), st),
+                  "cadre_mix_row_kinds")
+        stats = self._loss_stats()
+        srow, sscr = self._stats_ws(w, B) if stats else (None, None)
+        sc, svc = self._sil
+        inv_bs = 1.0 / (B - B_ppo) if B > B_ppo else 1.0
+        ord_t = getattr(a, "ord", None)
+        hip.check(L.cadre_ppo_sil_loss(hip.ptr(O3), NP, 2 * B * NP, hip.ptr(O3[1]), NP, 2 * B * NP,
+                                       hip.ptr(w["actions"]), hip.ptr(w["commands"]), hip.ptr(w["old_values"]),
+                                       hip.ptr(w["returns"]), hip.ptr(w["old_logp"]), hip.ptr(w["adv"]),
+                                       hip.ptr(w["row_kind"]), B, a.C, a.n_out[0], a.n_out[1],
+                                       hip.ptr(self._hp) if self._hp_on else None, self.clip, self.vc, self.cc, self.ec, inv_b,
+                                       sc, svc, inv_bs, hip.ptr(w["losses"]), hip.ptr(w["sil_losses"]), hip.ptr(w["sil_w"]),
+                                       hip.ptr(dO3), hip.ptr(dO3[1]), hip.ptr(w["loss_scratch"]), hip.ptr(w["sil_scratch"]),
+                                       hip.ptr(w["sync"][a.Z * S:]), hip.ptr(srow), srow.shape[1] if stats else 0,
+                                       hip.ptr(sscr), self._loss_tkl(),
+                                       hip.ptr(self._stop) if (stats and self.target_kl is not None) else None,
+                                       hip.ptr(w["sil_stats"]), hip.SIL_STATS_FIELDS, hip.ptr(ord_t), st),
+                  "cadre_ppo_sil_loss")
 
     # ------------------------------------------------------------------ exploration suggestions
     def set_suggest_tables(self, prior, Z=None):
@@ -501,6 +572,9 @@ class PPOLearnerHIP:
             t = self._sug_tables
             key = key + ((("suggest",) + ((None, 0) if t is None else (t[0].data_ptr(), t[1])) +
                           (() if self._hp_on else (self._sug_coeff,))),)
+        # the self-imitation loss is a mode: B_ppo by value always, the two coefficients unless they live in the block
+        if self.loss_mode == "ppo+sil":
+            key = key + ((("sil", self._sil_rows) + (() if self._hp_on else self._sil)),)
         return key
 
     # ------------------------------------------------------------------ device-resident hyper-parameters
@@ -550,6 +624,7 @@ class PPOLearnerHIP:
         m[hip.HP["clip_coeff"]], m[hip.HP["ent_coeff"]] = self._cc, self._ec
         m[hip.HP_DEMO_COEFF], m[hip.HP_DEMO_VALUE_COEFF] = self._demo[1], self._demo[2]
         m[hip.HP_SUGGEST_COEFF] = self._sug_coeff
+        m[hip.HP_SIL_COEFF], m[hip.HP_SIL_VALUE_COEFF] = self._sil
         if np.isnan(m[hip.HP["lr"]]):
             m[hip.HP["lr"]] = 3e-4
         self._hp_on = True
@@ -575,23 +650,30 @@ class PPOLearnerHIP:
         moves it on the device (the value each step used is in the step's stats row), NaN after set_adaptive_lr(None) until
         the next clip_adam / set_hyper supplies one."""
         self._need_hp("hyper")
-        return float(self._hp_host[hip.HP_SUGGEST_COEFF if name == "suggest_coeff" else hip.HP_INDEX[name]])
+        return float(self._hp_host[self._hp_index(name)])
+
+    @staticmethod
+    def _hp_index(name):
+        """Block index of a named field: hip.HP_INDEX, or one of the fields a single loss kernel reads."""
+        own = dict(suggest_coeff=hip.HP_SUGGEST_COEFF, sil_coeff=hip.HP_SIL_COEFF, sil_value_coeff=hip.HP_SIL_VALUE_COEFF)
+        return own[name] if name in own else hip.HP_INDEX[name]
 
     def _need_hp(self, what):
         if not self._hp_on:
             raise hip.CadreHipError("%s needs device-hyper mode: call set_device_hyper() first" % what)
 
     def set_hyper(self, lr=None, clip=None, ent_coeff=None, value_coeff=None, clip_coeff=None, max_grad_norm=None,
-                  demo_coeff=None, demo_value_coeff=None, suggest_coeff=None):
+                  demo_coeff=None, demo_value_coeff=None, suggest_coeff=None, sil_coeff=None, sil_value_coeff=None):
         """New values for the given block fields: the mirror is updated and ONE asynchronous host-to-device copy (of the
         span of fields that changed) is enqueued on the current stream — no synchronisation, no new graph.  Steps enqueued
         afterwards use the new values.  An explicit lr also resets the KL-adaptive controller's current value.
         demo_coeff / demo_value_coeff: the two coefficients of the "ppo+demo" loss (read by cadre_ppo_demo_loss only).
-        suggest_coeff: the coefficient of the "ppo+suggest" loss (read by cadre_ppo_sug_loss only)."""
+        suggest_coeff: the coefficient of the "ppo+suggest" loss (read by cadre_ppo_sug_loss only).
+        sil_coeff / sil_value_coeff: the two coefficients of the "ppo+sil" loss (read by cadre_ppo_sil_loss only)."""
         self._need_hp("set_hyper")
         new = dict(lr=lr, clip=clip, ent_coeff=ent_coeff, value_coeff=value_coeff, clip_coeff=clip_coeff,
                    max_grad_norm=max_grad_norm, demo_coeff=demo_coeff, demo_value_coeff=demo_value_coeff,
-                   suggest_coeff=suggest_coeff)
+                   suggest_coeff=suggest_coeff, sil_coeff=sil_coeff, sil_value_coeff=sil_value_coeff)
         idx = []
         for name, v in new.items():
             if v is None:
@@ -599,7 +681,7 @@ class PPOLearnerHIP:
             v = float(v)
             if not np.isfinite(v):
                 raise ValueError("set_hyper: %s=%r" % (name, v))
-            i = hip.HP_SUGGEST_COEFF if name == "suggest_coeff" else hip.HP_INDEX[name]
+            i = self._hp_index(name)
             if v != self._hp_host[i]:             # (a NaN mirror entry — lr after the controller — always differs)
                 self._hp_host[i] = v
                 idx.append(i)
@@ -609,6 +691,7 @@ class PPOLearnerHIP:
         self._cc, self._ec = float(m[hip.HP["clip_coeff"]]), float(m[hip.HP["ent_coeff"]])
         self._demo = (self._demo[0], float(m[hip.HP_DEMO_COEFF]), float(m[hip.HP_DEMO_VALUE_COEFF]))
         self._sug_coeff = float(m[hip.HP_SUGGEST_COEFF])
+        self._sil = (float(m[hip.HP_SIL_COEFF]), float(m[hip.HP_SIL_VALUE_COEFF]))
         if any(hip.HP["clip"] <= i <= hip.HP["ent_coeff"] for i in idx):
             self._hp_moved = True
         if idx:
@@ -990,6 +1073,8 @@ class PPOLearnerHIP:
             self._demo_launch(w, B, inv_b, sorted_rows)  # PPO rows + demonstration rows: two launches, the rest is indifferent
         elif front and self.loss_mode == "aux":
             self._aux_launch(w, B, inv_b, sorted_rows)  # critic + KL clone against the recorded table: the rest is indifferent
+        elif front and self.loss_mode == "ppo+sil":
+            self._sil_launch(w, B, inv_b, sorted_rows)   # PPO rows + self-imitation rows: two launches, the rest is indifferent
         elif front and self.loss_mode == "ppo+suggest":
             self._sug_launch(w, B, inv_b)               # PPO + the event priors on marked rows: the rest is indifferent
         elif front:

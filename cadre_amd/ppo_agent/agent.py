@@ -544,7 +544,7 @@ class CadreAgent(object):
 
     def update_policy_from_storages(self, batches, sync=True, mlp_grads_ready=None, stats_row=None, evaluate=False,
                                     demo=None, demo_stats_row=None, demo_label_smoothing=None, demo_coeff=None,
-                                    demo_value_coeff=None):
+                                    demo_value_coeff=None, sil=None, sil_stats_row=None):
         """Fast path of the learner section: `batches` = [(steer_storage, steer_idx, steer_adv,
         throttle_storage, throttle_idx, throttle_adv), ...] one entry per worker (equal sizes).
         Same math as feed_forward_generator -> update_policy, but the minibatch gather writes
@@ -561,7 +561,32 @@ class CadreAgent(object):
         The three floats returned are the PPO terms over the PPO rows; the two demo terms stay on the device in
         learner.workspace(B)["demo_losses"], the imitation statistics go to `demo_stats_row` (device float32
         [2][>= hip.BC_STATS_FIELDS]); `stats_row` receives the PPO rows' diagnostics.  demo_label_smoothing / demo_coeff /
-        demo_value_coeff: None keeps the learner's current settings (in device-hyper mode the coefficients are the block's)."""
+        demo_value_coeff: None keeps the learner's current settings (in device-hyper mode the coefficients are the block's).
+        `sil` (self-imitation): a list of entries of the same form whose rows are the agent's own past transitions
+        (SelfImitationBuffer.entries: the index tensors live on the device, filled by the prioritised draw).  They are appended
+        behind the workers' entries and the step runs the mixed loss (PPOLearnerHIP.set_loss("ppo+sil"), for the duration of
+        the call) with the learner's current SIL coefficients: total = the PPO loss + sil_coeff * mean(-lp w) +
+        sil_value_coeff * mean(0.5 w^2), w = max(R - v, 0), the means over ALL SIL rows.  The three floats returned are the
+        PPO terms; the two SIL terms and the rows' w stay on the device in learner.workspace(B)["sil_losses"] / ["sil_w"],
+        the SIL statistics go to `sil_stats_row` (device float32 [2][>= hip.SIL_STATS_FIELDS]).  Excludes `demo`."""
+        if sil:
+            if evaluate or demo:
+                raise ValueError("update_policy_from_storages: sil rows have no evaluation form and exclude demo rows "
+                                 "(a row carries one kind array)")
+            lrn = self.learner
+            prev = (lrn.loss_mode, lrn._sil_rows)
+            lrn.set_loss("ppo+sil")
+            lrn.set_sil_rows(len(batches) * batches[0][1].numel())
+            try:
+                out = self._update_from_storages(list(batches) + list(sil), sync, mlp_grads_ready, stats_row, False)
+                if sil_stats_row is not None:
+                    B = (len(batches) + len(sil)) * batches[0][1].numel()
+                    sil_stats_row[:, :hip.SIL_STATS_FIELDS].copy_(lrn.workspace(B)["sil_stats"])
+                return out
+            finally:
+                lrn.loss_mode, lrn._sil_rows = prev
+        if sil_stats_row is not None:
+            raise ValueError("update_policy_from_storages: sil_stats_row without sil entries")
         if demo:
             if evaluate:
                 raise ValueError("update_policy_from_storages: demo rows have no evaluation form here (imitate_from_storages(evaluate=True))")
@@ -668,10 +693,16 @@ class CadreAgent(object):
         ring["pos"] = (ring["pos"] + 1) % len(ring["slots"])
         if stage[2] is not None:
             stage[2].synchronize()
+        on_dev = []                                   # index vectors that are on the device already (a prioritised draw)
         for i, (ss, si, sa, ts, ti, ta) in enumerate(batches):
-            stage[0][2 * i].copy_(si.reshape(-1))
-            stage[0][2 * i + 1].copy_(ti.reshape(-1))
+            for k, x in ((2 * i, si), (2 * i + 1, ti)):
+                if x.is_cuda:
+                    on_dev.append((k, x))
+                else:
+                    stage[0][k].copy_(x.reshape(-1))
         stage[1].copy_(stage[0], non_blocking=True)
+        for k, x in on_dev:                           # behind the host-to-device copy: device-to-device, no sync
+            stage[1][k].copy_(x.reshape(-1))
         if aux:
             aux_rows.copy_(stage[1])                  # (nW = 1: the index pair [steer; throttle] is row_id, head-major)
         if self.learner.loss_mode == "ppo+suggest" and record is None and not evaluate:

@@ -384,6 +384,51 @@ def _suggest_stats(stats, suggest):
             stats["suggest"] = summary
 
 
+def self_imitation(agent, train_cfg, shared_grad_buffers=None, rank=0, in_process_chief=True, fused_gather=True,
+                   ck_interval=None, ck_resume=None):
+    """train_cfg["self_imitation"] (absent / None: None — nothing runs, nothing is allocated, nothing is drawn): the SilRunner
+    of a run that replays its own past successes (cadre_amd.selfimit.sil_config for the keys, sil_runner for what is refused
+    at start-up and why)."""
+    cfg = _get(train_cfg, "self_imitation")
+    if cfg is None:
+        return None
+    from ..selfimit import sil_runner
+    return sil_runner(agent, cfg, shared_grad_buffers, rank, in_process_chief, fused_gather, ck_interval, ck_resume,
+                      _get(train_cfg, "demo_mix"), _get(train_cfg, "suggest"), _get(train_cfg, "sample_reuse"))
+
+
+def apply_sil(agent, sil, episode, max_episode):
+    """The SIL coefficients of `episode` (SilRunner.coeff through schedule_value, value_coeff as it is) into the learner's
+    device hyper-parameter block, beside apply_demo_mix: a moving coefficient replays the captured graphs as they are.
+    Returns the coefficient set (None without self-imitation)."""
+    if sil is None:
+        return None
+    v = schedule_value(sil.coeff, episode, max_episode)
+    agent.learner.set_device_hyper(True)
+    agent.learner.set_hyper(sil_coeff=v, sil_value_coeff=sil.value_coeff)
+    return v
+
+
+def _sil_kw(sil, Bw, episode, epoch, step):
+    """Keyword arguments of update_policy_from_storages for step `step` of epoch `epoch` ({} without a buffer, or while it
+    has no eligible row: the step is then the plain PPO step, launch for launch)."""
+    if sil is None:
+        return {}
+    entries = sil.entries(Bw, episode, epoch, step)
+    if not entries:
+        return {}
+    kw = dict(sil=entries)
+    row = sil.next_stats_row()
+    if row is not None:
+        kw["sil_stats_row"] = row
+    return kw
+
+
+def _sil_stats(stats, sil):
+    if stats is not None and sil is not None:
+        stats["sil"] = sil.summary()
+
+
 def _demo_kw(demo, Bw, episode, step, sec):
     """Keyword arguments of update_policy_from_storages for step `step` of the section ({} without a mixer)."""
     if demo is None:
@@ -573,13 +618,27 @@ def stats_line(episode, stats):
     if "suggest" in stats:                             # exploration suggestions: marked rows and the KL towards the priors
         from ..suggest import suggest_stats_text
         line += suggest_stats_text(stats)
+    if "sil" in stats:                                 # self-imitation: the weights of the section's SIL rows
+        from ..selfimit import sil_stats_text
+        line += sil_stats_text(stats)
     return line
+
+
+def _check_sil(sil, demo, suggest, reuse, path_ok=True):
+    if sil is None:
+        return
+    if demo is not None or suggest is not None:
+        raise ValueError("sil excludes demo and suggest (a row carries one kind array)")
+    if reuse is not None:
+        raise ValueError("sil excludes reuse (the SIL rows are the rows behind the PPO rows, where the stale rows ride)")
+    if not path_ok:
+        raise ValueError("sil needs fused_gather=True and the in-process chief")
 
 
 def learner_section(agent, steer_rollout, throttle_rollout, done, train_cfg, shared_grad_buffers,
                     optimizer=None, traffic_light=None, counter=None, shared_model_list=None, in_process_chief=True,
                     fused_gather=True, losses_on_device=False, step_events=None, stats=None, reward_scaler=None,
-                    demo=None, episode=0, reuse=None, suggest=None):
+                    demo=None, episode=0, reuse=None, suggest=None, sil=None):
     """train.py:76-110.  Returns (value_loss_list, policy_loss_list, ent_loss_list).
     With `in_process_chief` (one process per GPU) the optimiser step runs right after the gradient
     all-reduce instead of waiting on a separate chief process.  `fused_gather` uses the storage ->
@@ -614,9 +673,12 @@ def learner_section(agent, steer_rollout, throttle_rollout, done, train_cfg, sha
     `reuse` (a cadre_amd.reuse.ReuseWindow for one environment, needs fused_gather and the in-process chief) with
     `episode`: sample reuse, as in learner_section_multi.
     `suggest` (a cadre_amd.suggest.Suggestions, needs fused_gather, excludes `demo`): exploration suggestions, as in
-    learner_section_multi."""
+    learner_section_multi.
+    `sil` (a cadre_amd.selfimit.SelfImitationBuffer for one environment; needs fused_gather and the in-process chief,
+    excludes `demo`, `suggest` and `reuse`) with `episode`: self-imitation, as in learner_section_multi."""
     if demo is not None and not fused_gather:
         raise ValueError("demo needs fused_gather=True")
+    _check_sil(sil, demo, suggest, reuse, fused_gather and in_process_chief)
     if suggest is not None and (not fused_gather or demo is not None):
         raise ValueError("suggest needs fused_gather=True and excludes demo (a row carries one kind array)")
     if reuse is not None and not (fused_gather and in_process_chief):
@@ -636,7 +698,7 @@ def learner_section(agent, steer_rollout, throttle_rollout, done, train_cfg, sha
         out = _learner_section(agent, steer_rollout, throttle_rollout, done, train_cfg, shared_grad_buffers, optimizer,
                                traffic_light, counter, shared_model_list, in_process_chief, fused_gather, losses_on_device,
                                step_events, use_adv_norm, sec, lr, reward_scaler, cons, demo, episode, reuse, suggest,
-                               stats)
+                               stats, sil)
     finally:
         if sec is not None:
             agent.learner.set_update_modes()
@@ -647,12 +709,14 @@ def learner_section(agent, steer_rollout, throttle_rollout, done, train_cfg, sha
         _scale_stats(stats, reward_scaler)
         _reuse_stats(stats, reuse)
         _suggest_stats(stats, suggest)
+        _sil_stats(stats, sil)
         return out
     dev_losses, (vl, pl, el) = out
     host = sec.finish(stats, tkl is not None, losses=torch.stack(dev_losses) if dev_losses else None)
     _scale_stats(stats, reward_scaler)
     _reuse_stats(stats, reuse)
     _suggest_stats(stats, suggest)
+    _sil_stats(stats, sil)
     if host is not None:
         for v, p, e in host.tolist():
             vl.append(v); pl.append(p); el.append(e)
@@ -661,7 +725,8 @@ def learner_section(agent, steer_rollout, throttle_rollout, done, train_cfg, sha
 
 def _learner_section(agent, steer_rollout, throttle_rollout, done, train_cfg, shared_grad_buffers, optimizer, traffic_light,
                      counter, shared_model_list, in_process_chief, fused_gather, losses_on_device, step_events, use_adv_norm,
-                     sec, lr, reward_scaler=None, cons=False, demo=None, episode=0, reuse=None, suggest=None, stats=None):
+                     sec, lr, reward_scaler=None, cons=False, demo=None, episode=0, reuse=None, suggest=None, stats=None,
+                     sil=None):
     nv_s, nv_t = agent.get_value(done, steer_rollout.get_last(as_tensor=True), throttle_rollout.get_last(as_tensor=True))
     if reward_scaler is not None or steer_rollout._tl_used or throttle_rollout._tl_used:
         steer_adv, throttle_adv = RolloutStorage.finish_rollouts(
@@ -677,10 +742,12 @@ def _learner_section(agent, steer_rollout, throttle_rollout, done, train_cfg, sh
         reuse.refresh(use_adv_norm, reward_scaler)
     sug_prev = _suggest_begin(agent, suggest, [steer_rollout, throttle_rollout], stats,
                               train_cfg["ppo_epoch"] * _steps_per_epoch(steer_rollout))
+    if sil is not None:
+        sil.begin_section(train_cfg["ppo_epoch"] * _steps_per_epoch(steer_rollout) if stats is not None else 0)
     try:
         return _learner_steps(agent, steer_rollout, throttle_rollout, steer_adv, throttle_adv, train_cfg, shared_grad_buffers,
                               optimizer, traffic_light, counter, shared_model_list, in_process_chief, fused_gather,
-                              losses_on_device, step_events, sec, lr, demo, episode, reuse, suggest)
+                              losses_on_device, step_events, sec, lr, demo, episode, reuse, suggest, sil)
     finally:
         if suggest is not None:
             agent.learner.loss_mode = sug_prev
@@ -688,7 +755,7 @@ def _learner_section(agent, steer_rollout, throttle_rollout, done, train_cfg, sh
 
 def _learner_steps(agent, steer_rollout, throttle_rollout, steer_adv, throttle_adv, train_cfg, shared_grad_buffers, optimizer,
                    traffic_light, counter, shared_model_list, in_process_chief, fused_gather, losses_on_device, step_events, sec,
-                   lr, demo, episode, reuse, suggest):
+                   lr, demo, episode, reuse, suggest, sil=None):
     dev_losses = []
     vl, pl, el = [], [], []
     n_step = 0
@@ -711,9 +778,12 @@ def _learner_steps(agent, steer_rollout, throttle_rollout, steer_adv, throttle_a
                 stale = [] if reuse is None else reuse.entries(episode, epoch, j, a.numel())
                 dev_losses.append(agent.update_policy_from_storages(
                     [(steer_rollout, a, steer_adv, throttle_rollout, b, throttle_adv)] + stale, sync=False, mlp_grads_ready=hook,
-                    stats_row=row, **_demo_kw(demo, a.numel(), episode, n_step, sec)))
+                    stats_row=row, **_demo_kw(demo, a.numel(), episode, n_step, sec),
+                    **_sil_kw(sil, a.numel(), episode, epoch, j)))
                 if suggest is not None:
                     suggest.collect(agent.learner)
+                if sil is not None:
+                    sil.after_step(a.numel())
             else:
                 v, p, e = agent.update_policy(a, b, stats_row=row)
                 vl.append(v); pl.append(p); el.append(e)
@@ -784,6 +854,7 @@ def train(rank, train_cfg, agent_cfg, env_cfg, rollout_cfg, traffic_light=None, 
                       shared_model_list)
     reuse = _reuse_runner(agent, train_cfg, shared_grad_buffers, rank, traffic_light is None, ck_interval, ck_resume,
                           shared_model_list)
+    sil = self_imitation(agent, train_cfg, shared_grad_buffers, rank, traffic_light is None, True, ck_interval, ck_resume)
     obs = env.reset()
     done = False
     log_stats = bool(_get(train_cfg, "log_stats", False))
@@ -812,19 +883,23 @@ def train(rank, train_cfg, agent_cfg, env_cfg, rollout_cfg, traffic_light=None, 
         apply_schedules(agent, train_cfg, episode)
         apply_demo_mix(agent, demo, episode, train_cfg.max_episode)
         apply_suggest(agent, suggest, episode, train_cfg.max_episode)
+        apply_sil(agent, sil, episode, train_cfg.max_episode)
         vl, pl, el = learner_section(agent, steer_rollout, throttle_rollout, done, train_cfg, shared_grad_buffers,
                                      traffic_light=traffic_light, counter=counter,
                                      shared_model_list=shared_model_list,
                                      in_process_chief=traffic_light is None, stats=stats,   # no chief process -> step in-process
                                      reward_scaler=agent.reward_scaler, demo=demo, episode=episode,
                                      **({} if reuse is None else dict(reuse=reuse.window_for([(steer_rollout, throttle_rollout)]))),
-                                     **({} if suggest is None else dict(suggest=suggest)))
+                                     **({} if suggest is None else dict(suggest=suggest)),
+                                     **({} if sil is None else dict(sil=sil.buffer_for([(steer_rollout, throttle_rollout)]))))
         log_now = episode % train_cfg.log_interval == 0 and rank == 0 and logger is not None
         # (the auxiliary phase: before the log line, the snapshot and the checkpoint, which then see its result)
         aux_records = _aux_after_section(aux, agent, train_cfg, episode, [(steer_rollout, throttle_rollout)],
                                          shared_grad_buffers, None, logger if log_now else None)
         if reuse is not None:                    # (after the PPG buffer took its copy: the two are independent)
             reuse.after_section([(steer_rollout, throttle_rollout)], [done])
+        if sil is not None:                      # (the section's rollouts become replayable from the next section on)
+            sil.after_section([(steer_rollout, throttle_rollout)], [done], agent.reward_scaler)
         if log_now:
             logger.log("Episode: {}, value loss: {:.4f}, policy loss: {:.4f}, entropy loss: {:.4f}".format(
                 episode, np.mean(vl), np.mean(pl), np.mean(el)))
@@ -847,7 +922,7 @@ def train(rank, train_cfg, agent_cfg, env_cfg, rollout_cfg, traffic_light=None, 
 
 # ----------------------------------------------------------------------------- N environments in one process
 def learner_section_multi(agent, rollouts, dones, train_cfg, shared_grad_buffers, optimizer=None, losses_on_device=False,
-                          stats=None, reward_scaler=None, demo=None, episode=0, reuse=None, suggest=None):
+                          stats=None, reward_scaler=None, demo=None, episode=0, reuse=None, suggest=None, sil=None):
     """train.py:76-110 for N workers that share one agent (`num_processes = N` on one GPU, chief.py:13-21 semantics):
     rollouts = [(steer_rollout, throttle_rollout), ...] per worker, dones[i] = worker i's last `done`.  Bootstrap values
     of all workers in one pass (get_values), GAE + advantage normalisation per storage, then for each ppo_epoch and
@@ -878,9 +953,17 @@ def learner_section_multi(agent, rollouts, dones, train_cfg, shared_grad_buffers
     "ppo+suggest" for the section, and every step carries the kinds of its rows into the update's layout
     (cadre_suggest_rows) before the update; the rows of stale `reuse` entries get kind 0.  Marks are rank-local, and the
     gradient is summed by the exchange that sums the PPO gradient.  `stats` gains "suggest" (marked_rows, kl, max_kl,
-    p_mode as (steer, throttle) pairs over the section's steps; one more small device-to-host copy)."""
+    p_mode as (steer, throttle) pairs over the section's steps; one more small device-to-host copy).
+    `sil` (a cadre_amd.selfimit.SelfImitationBuffer for N environments; excludes `demo`, `suggest` and `reuse`) with `episode`:
+    self-imitation.  Every step draws sil.entries(rows per minibatch, episode, epoch, step) on the device (cadre_sil_draw), the
+    entries ride behind the workers' and the step runs the mixed loss (update_policy_from_storages(sil=)), then
+    sil.after_step() writes the drawn rows' priorities back from the w the step computed (cadre_sil_scatter).  While the buffer
+    has no eligible row in a head the step is the plain PPO step, launch for launch.  `stats` gains "sil" (filled, steps,
+    w_mean, positive_share, nll, value_error, w_max, rows as (steer, throttle) pairs; one more small device-to-host copy).  The
+    caller appends the section's rollouts to the buffer afterwards (sil.append)."""
     if suggest is not None and demo is not None:
         raise ValueError("suggest excludes demo (a row carries one kind array)")
+    _check_sil(sil, demo, suggest, reuse)
     _check_scaler(reward_scaler, shared_grad_buffers, train_cfg)
     tkl = _target_kl(train_cfg, shared_grad_buffers)
     cons = _consensus_on(train_cfg, shared_grad_buffers)
@@ -906,6 +989,8 @@ def learner_section_multi(agent, rollouts, dones, train_cfg, shared_grad_buffers
     try:
         sug_prev = _suggest_begin(agent, suggest, [x for pair in rollouts for x in pair], stats,
                                   train_cfg["ppo_epoch"] * _steps_per_epoch(rollouts[0][0]))
+        if sil is not None:
+            sil.begin_section(train_cfg["ppo_epoch"] * _steps_per_epoch(rollouts[0][0]) if stats is not None else 0)
         for epoch in range(train_cfg["ppo_epoch"]):
             idx = [(s.sample_indices(), t.sample_indices()) for s, t in rollouts]
             for j in range(len(idx[0][0])):
@@ -914,9 +999,12 @@ def learner_section_multi(agent, rollouts, dones, train_cfg, shared_grad_buffers
                     batches += reuse.entries(episode, epoch, j, batches[0][1].numel())
                 dev_losses.append(agent.update_policy_from_storages(
                     batches, sync=False, stats_row=None if sec is None else sec.next_row(),
-                    **_demo_kw(demo, batches[0][1].numel(), episode, len(dev_losses), sec)))
+                    **_demo_kw(demo, batches[0][1].numel(), episode, len(dev_losses), sec),
+                    **_sil_kw(sil, batches[0][1].numel(), episode, epoch, j)))
                 if suggest is not None:
                     suggest.collect(agent.learner)
+                if sil is not None:
+                    sil.after_step(len(batches) * batches[0][1].numel())
                 shared_grad_buffers.add_gradient(agent.model_dict)
                 chief_step(shared_grad_buffers, optimizer, train_cfg["max_grad_norm"], lr=lr, zero_grads=False)
     finally:
@@ -930,12 +1018,14 @@ def learner_section_multi(agent, rollouts, dones, train_cfg, shared_grad_buffers
         _scale_stats(stats, reward_scaler)
         _reuse_stats(stats, reuse)
         _suggest_stats(stats, suggest)
+        _sil_stats(stats, sil)
         return tuple(list(c) for c in zip(*host.tolist()))
     if sec is not None:
         sec.finish(stats, tkl is not None)
         _scale_stats(stats, reward_scaler)
         _reuse_stats(stats, reuse)
         _suggest_stats(stats, suggest)
+        _sil_stats(stats, sil)
     if losses_on_device:
         return losses
     vl, pl, el = [], [], []
@@ -1015,6 +1105,7 @@ def train_vec(rank, train_cfg, agent_cfg, env_cfg, rollout_cfg, num_envs, env_cl
     _pretrain(agent, train_cfg, rollout_cfg, shared_grad_buffers, rank, logger, ck_resume)
     aux = _aux_runner(agent, train_cfg, shared_grad_buffers, rank, True, ck_interval, first_episode)
     reuse = _reuse_runner(agent, train_cfg, shared_grad_buffers, rank, True, ck_interval, ck_resume)
+    sil = self_imitation(agent, train_cfg, shared_grad_buffers, rank, True, True, ck_interval, ck_resume)
     obs = [env.reset() for env in envs]
     dones = [False] * num_envs
     log_stats = bool(_get(train_cfg, "log_stats", False))
@@ -1047,16 +1138,20 @@ def train_vec(rank, train_cfg, agent_cfg, env_cfg, rollout_cfg, num_envs, env_cl
         apply_schedules(agent, train_cfg, episode)
         apply_demo_mix(agent, demo, episode, train_cfg.max_episode)
         apply_suggest(agent, suggest, episode, train_cfg.max_episode)
+        apply_sil(agent, sil, episode, train_cfg.max_episode)
         vl, pl, el = learner_section_multi(agent, rollouts, dones, train_cfg, shared_grad_buffers, optimizer=optimizer,
                                            stats=stats, reward_scaler=agent.reward_scaler, demo=demo, episode=episode,
                                            **({} if reuse is None else dict(reuse=reuse.window_for(rollouts))),
-                                           **({} if suggest is None else dict(suggest=suggest)))
+                                           **({} if suggest is None else dict(suggest=suggest)),
+                                           **({} if sil is None else dict(sil=sil.buffer_for(rollouts))))
         log_now = episode % train_cfg.log_interval == 0 and rank == 0 and logger is not None
         # (the auxiliary phase: before the log line, the snapshot and the checkpoint, which then see its result)
         aux_records = _aux_after_section(aux, agent, train_cfg, episode, rollouts, shared_grad_buffers, optimizer,
                                          logger if log_now else None)
         if reuse is not None:                    # (after the PPG buffer took its copy: the two are independent)
             reuse.after_section(rollouts, dones)
+        if sil is not None:                      # (the section's rollouts become replayable from the next section on)
+            sil.after_section(rollouts, dones, agent.reward_scaler)
         if log_now:
             logger.log("Episode: {}, value loss: {:.4f}, policy loss: {:.4f}, entropy loss: {:.4f}".format(
                 episode, np.mean(vl), np.mean(pl), np.mean(el)))

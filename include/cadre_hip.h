@@ -428,7 +428,7 @@ int cadre_grad_norms(const double* norms2, int32_t C, float* stats_row, int32_t 
 /* ---------------------------------------------------------------- device-resident hyper-parameters
  * The hyper-parameter block: a device array of CADRE_HP_FIELDS doubles (8-byte aligned) that the `_hp` entry points read
  * at RUN time, so a captured hipGraph follows whatever the block holds when it is replayed.  Fields past
- * CADRE_HP_SUGGEST_COEFF are reserved and zero.  betas and eps stay by-value arguments.  The block is written by ordinary
+ * CADRE_HP_SIL_VALUE_COEFF are reserved and zero.  betas and eps stay by-value arguments.  The block is written by ordinary
  * stream-ordered copies from the host, and by the KL-adaptive controller below. */
 #define CADRE_HP_FIELDS 16
 #define CADRE_HP_LR 0
@@ -448,6 +448,9 @@ enum { CADRE_HP_DEMO_COEFF = 10, CADRE_HP_DEMO_VALUE_COEFF = 11 };
 /* A third reserved field, read by cadre_ppo_sug_loss only and zero for everyone else: the weight of the exploration-suggestion
  * KL term. */
 enum { CADRE_HP_SUGGEST_COEFF = 12 };
+/* Two more, read by cadre_ppo_sil_loss only and zero for everyone else: the weight of the self-imitation policy term and of
+ * its value term. */
+enum { CADRE_HP_SIL_COEFF = 13, CADRE_HP_SIL_VALUE_COEFF = 14 };
 /* cadre_ppo_loss / cadre_ppo_loss_stats with clip, value_coeff, clip_coeff, ent_coeff = (float)hp[CADRE_HP_*] (the same
  * kernel bodies, the scalars read once per thread before the row loop; the stats variant uses the same clip for its clip
  * fractions).  Equal values give results bit-identical to the by-value entry points.
@@ -759,6 +762,77 @@ int cadre_ppo_sug_loss(const float* logits, int64_t ldl, int64_t l_ns, const flo
                        float* dlogits, float* dvalues, float* scratch, float* sug_scratch, const int32_t* poison,
                        float* stats_row, int32_t F, float* stats_scratch, float target_kl, int32_t* stop, float* sug_stats_row,
                        int32_t sug_F, const int32_t* ord, void* stream);
+
+/* ---------------------------------------------------------------- self-imitation learning (csrc/selfimit.hip)
+ * Oh et al. 2018, "Self-Imitation Learning": rows of the agent's own past rollouts whose realised return R beat the critic
+ * are replayed with weight w = max(R - v, 0).  A buffer of past storages keeps, per head and row, the return R, a flag word and
+ * a priority q (uint32, 0: never drawn); SIL rows are drawn by priority on the device, ride behind the workers' rows of a
+ * minibatch (kind 1 of cadre_mix_row_kinds), and the priorities of the drawn rows follow the w the step computed.
+ *   quantise(w) = clamp(floor((w + prio_eps)^alpha * 2^16), 1, 2^31 - 1), the power in double (alpha == 1 takes none: exact).
+ *
+ * cadre_ppo_sil_loss: ONE loss launch where cadre_ppo_loss_ord / cadre_ppo_demo_loss stand in the update — the same addressing,
+ * grid, `scratch` protocol (arrival counter zero on entry and left zero, partials combined by the last arriving workgroup in
+ * workgroup order: equal inputs give equal bits), `poison`, rank table `ord`, hp-or-by-value scalars and stats / target_kl /
+ * stop.  row_kind int32 [2][B] in workspace order.
+ *   A row of kind 0 runs exactly the statements of cadre_ppo_loss_ord; the PPO sums, losses[3], the PPO diagnostics and the KL
+ *   gate / adaptive lr see these rows only (means over inv_b).
+ *   A row of kind != 0 is a SIL row (it needs a command in range and an action in 0 .. K - 1, else it writes zeros): with lp
+ *   the log-prob of its action, p the probabilities, v its own net's value and R = returns[row],
+ *     w = fmaxf(R - v, 0)     dlogits_k = (sil_coeff inv_bs w) (p_k - [k = a])  (through ord_backward on an ordinal head)
+ *     dvalues = -(sil_value_coeff inv_bs w)      no entropy term; old_values, old_logp and adv are not read.
+ *   A row with R <= v has w, every logit gradient and the value gradient exactly zero.
+ *   sil_losses[2]  sil_coeff inv_bs sum(-lp w),  sil_value_coeff 0.5 inv_bs sum(w^2)
+ *                  total = losses[0] + losses[1] - losses[2] + sil_losses[0] + sil_losses[1]
+ *   sil_w [2][B]   the row's w in the update's layout, 0 for a PPO row or a row that does not count
+ * sil_coeff / sil_value_coeff are the by-value arguments, or (float)hp[CADRE_HP_SIL_COEFF / CADRE_HP_SIL_VALUE_COEFF] when hp is
+ * not NULL.  inv_bs = 1 / SIL rows per step.
+ * sil_stats_row (may be NULL) float [2][sil_F], sil_F >= CADRE_SIL_STATS_FIELDS, per head over the SIL rows:
+ *   0 mean w   1 share of rows with w > 0   2 mean -lp   3 mean |R - v|   (sums times inv_bs)   4 max w   5 rows counted
+ * sil_scratch (always required): 2 * ceil(B / 16) * (2 + CADRE_SIL_STATS_FIELDS) floats; it needs no initialisation.
+ * Refused before any launch: the argument checks of cadre_ppo_demo_loss, NULL row_kind, sil_losses, sil_w or sil_scratch,
+ * by-value coefficients that are not finite, an inv_bs that is not finite and > 0 when hp, a non-zero coefficient or
+ * sil_stats_row needs it, sil_F too small, a misaligned hp. */
+#define CADRE_SIL_STATS_FIELDS 6
+int cadre_ppo_sil_loss(const float* logits, int64_t ldl, int64_t l_ns, const float* values, int64_t ldv, int64_t v_ns,
+                       const int64_t* actions, const int32_t* commands, const float* old_values, const float* returns,
+                       const float* old_logp, const float* adv, const int32_t* row_kind, int32_t B, int32_t C,
+                       int32_t n_out_steer, int32_t n_out_throttle, double* hp, float clip, float value_coeff, float clip_coeff,
+                       float ent_coeff, float inv_b, float sil_coeff, float sil_value_coeff, float inv_bs, float* losses,
+                       float* sil_losses, float* sil_w, float* dlogits, float* dvalues, float* scratch, float* sil_scratch,
+                       const int32_t* poison, float* stats_row, int32_t F, float* stats_scratch, float target_kl, int32_t* stop,
+                       float* sil_stats_row, int32_t sil_F, const int32_t* ord, void* stream);
+/* cadre_sil_prepare: one launch for the n storages of a buffer slot, storage k belonging to head k & 1.  row_table = n records
+ * of seven device pointers (int64) {rewards f32 [T + 1], masks f32 [T + 1], time_limits f32 [T + 1] or 0, value_preds f32
+ * [T + 1], returns f32 [T + 1] (out), flags int32 [T + 1] (out), q uint32 [T + 1] (out)}.  2 <= T <= 3000.
+ * Rewards are staged as cadre_gae_multi stages them (state NULL: raw; else clamp(r * (float)state[CADRE_RS_SCALE + head],
+ * -clip_r, clip_r)), and the scan is cadre_gae_multi's with tau = 1 and V = 0, statement for statement in strict fp32:
+ *   R_t = (r_t + (gamma m_t) R_{t+1}) (1 - time_limit_t),  R_T = 0.
+ * A row is CLOSED when the nearest row t' >= t with m == 0 or a time-limit flag has m == 0 and no flag (its episode ended
+ * inside the rollout by a true termination).  tail = 0 ("drop"): only closed rows are eligible.  tail = 1 ("bootstrap"): every
+ * row is eligible, and the chains start from the stored values, R_T = value_preds[T] and R_t = value_preds[t] at a flagged
+ * row; a closing row multiplies that start away, so R on closed rows carries the same bits under both settings.
+ * Written for t < T: returns[t] = R_t, flags[t] = closed | eligible << 1, q[t] = quantise(fmaxf(R_t - value_preds[t], 0)) on
+ * eligible rows and 0 elsewhere; flags[T] = 0 and q[T] = 0.  returns[T] is not written.
+ * Refused before any launch: NULL table, n outside 1 .. 65535, T outside 2 .. 3000, gamma outside [0, 1], clip_r <= 0 with a
+ * state, tail not 0 / 1, alpha not finite or <= 0, prio_eps not finite or < 0. */
+int cadre_sil_prepare(const void* row_table, int32_t n, int32_t T, float gamma, const double* state, float clip_r, int32_t tail,
+                      double alpha, double prio_eps, void* stream);
+/* cadre_sil_draw: the prioritised draw, with replacement.  q uint32 [2][Rcap]; rows >= filled count as 0.  For head h, draw j:
+ *   idx[h][j] = the smallest row r with cum[h][r] > (uint64)u[h][j] mod total[h],
+ * cum the inclusive prefix sum of q[h] in uint64, total[h] = cum[h][filled - 1]: integers throughout, so the result does not
+ * depend on the order of summation, and a row with q == 0 is never returned.  u int64 [2][n] non-negative random words, idx
+ * int64 [2][n].  Three launches: sums of blocks of 1024 rows, their scan, one wave per draw.  scratch: 4 * ceil(Rcap / 1024) + 2
+ * uint64, no initialisation.  The caller guarantees total[h] >= 1 (a head without an eligible row gets idx 0).
+ * Refused before any launch: NULL q, u, idx or scratch, Rcap outside 1 .. 2^30, filled outside 1 .. Rcap, n outside 1 .. 65535. */
+int cadre_sil_draw(const uint32_t* q, int64_t Rcap, int64_t filled, const int64_t* u, int32_t n, int64_t* idx, uint64_t* scratch,
+                   void* stream);
+/* cadre_sil_scatter: after the step, q[h][idx[h][j]] = quantise(fmaxf(sil_w[h][pos[h * B + B_ppo + j]], 0)) for j < n — SIL row
+ * j is unsorted row B_ppo + j of the minibatch, pos as cadre_mix_row_kinds takes it (NULL: the identity).  A row drawn twice
+ * gets the same value twice.  An index outside 0 .. Rcap - 1 or a position outside 0 .. B - 1 writes nothing.
+ * Refused before any launch: NULL q, idx or sil_w, Rcap < 1, n < 1, B < 1, B_ppo < 0, B_ppo + n > B, alpha not finite or <= 0,
+ * prio_eps not finite or < 0. */
+int cadre_sil_scatter(uint32_t* q, int64_t Rcap, const int64_t* idx, int32_t n, const float* sil_w, const int32_t* pos, int32_t B,
+                      int32_t B_ppo, double alpha, double prio_eps, void* stream);
 
 /* ---------------------------------------------------------------- ensemble evaluation (csrc/ensemble.hip)
  * eval.py:53-63 for N environments and M snapshots.  A group of Mg agents (Mg * C <= 16) shares one stacked arena with
