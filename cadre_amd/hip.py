@@ -212,6 +212,16 @@ SYMBOLS = {
     "cadre_sil_prepare": [vp, i32, i32, f32, vp, f32, i32, f64, f64, vp],
     "cadre_sil_draw": [vp, i64, i64, vp, i32, vp, vp, vp],
     "cadre_sil_scatter": [vp, i64, vp, i32, vp, vp, i32, i32, f64, f64, vp],
+    # temporal smoothness: {masks, time_limits or 0, command} table, idx, nW, E, Bw, T, C, rotation, pos (NULL: identity), Bt,
+    # row_kind, mate, stream / logits, ldl, l_ns, values, ldv, v_ns, actions, commands, old_values, returns, old_logp, adv,
+    # row_kind, mate, ctrl, B, C, K_steer, K_throttle, hp (may be NULL), clip, value_coeff, clip_coeff, ent_coeff, inv_b,
+    # smooth_coeff, scale_steer, scale_throttle, inv_bp, losses[3], smooth_losses[1], smooth_d, dlogits, dvalues, scratch,
+    # smoothness scratch, poison, PPO stats row (may be NULL), F, stats scratch, target_kl, stop, smoothness stats row (may be
+    # NULL), its F, ord, stream / {action, masks, time_limits or 0, command} table, n, T, C, K_steer, K_throttle, ctrl, out, stream
+    "cadre_smooth_mates": [vp, vp, i32, i32, i32, i32, i32, i64, vp, i32, vp, vp, vp],
+    "cadre_ppo_smooth_loss": [vp, i64, i64, vp, i64, i64, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, vp, f32, f32, f32,
+                              f32, f32, f32, f32, f32, f32, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, vp, f32, vp, vp, i32, vp, vp],
+    "cadre_action_jitter": [vp, i32, i32, i32, i32, i32, vp, vp, vp],
 }
 # entry points of the A/B build only (include/cadre_hip_ab.h; CADRE_BUILD_AB=1 python -m cadre_amd.build, then
 # CADRE_HIP_LIB=.../libcadre_hip_ab.so): bound when the loaded library has them
@@ -275,6 +285,8 @@ HP_SUGGEST_COEFF = 12
 # two more (the enumerators CADRE_HP_SIL_COEFF / CADRE_HP_SIL_VALUE_COEFF), read by cadre_ppo_sil_loss only;
 # set_hyper(sil_coeff=, sil_value_coeff=)
 HP_SIL_COEFF, HP_SIL_VALUE_COEFF = 13, 14
+# the last field (the enumerator CADRE_HP_SMOOTH_COEFF), read by cadre_ppo_smooth_loss only; set_hyper(smooth_coeff=)
+HP_SMOOTH_COEFF = 15
 PPO_STATS_LR = 7      # CADRE_PPO_STATS_LR: field of head 0 of a stats row that cadre_grad_norms_hp fills with the step's lr
 
 PPO_STATS_FIELDS = 8  # CADRE_PPO_STATS_FIELDS (include/cadre_hip.h): loss diagnostics per head before the gradient norms
@@ -282,6 +294,7 @@ BC_STATS_FIELDS = 6   # CADRE_BC_STATS_FIELDS: accuracy, NLL, entropy, |v - R|, 
 AUX_STATS_FIELDS = 6  # CADRE_AUX_STATS_FIELDS: mean KL, max KL, mean |v - R|, mean entropy, mean (v - R)^2, rows counted
 SUG_STATS_FIELDS = 4  # CADRE_SUG_STATS_FIELDS: marked rows, mean KL over the minibatch, max KL, mean p[prior's mode] over marked rows
 SIL_STATS_FIELDS = 6  # CADRE_SIL_STATS_FIELDS: mean w, share w > 0, mean -lp, mean |R - v|, max w, rows counted (over the SIL rows)
+SMOOTH_STATS_FIELDS = 4  # CADRE_SMOOTH_STATS_FIELDS: valid pairs, inv_bp sum |d|, max |d|, inv_bp sum d^2 (per head)
 VTRACE_DIAG_FIELDS = 4  # CADRE_VTRACE_DIAG_FIELDS: mean ratio, share truncated, max |log ratio|, effective-sample share
 
 RS_SCALE, RS_CARRY = 6, 8 # CADRE_RS_SCALE / CADRE_RS_CARRY: the return-statistics block (count, mean, M2 per head first)

@@ -123,11 +123,15 @@ class PPOLearnerHIP:
         # "ppo+sil": cadre_ppo_sil_loss — PPO rows and self-imitation rows (the agent's own past rollouts) in one minibatch
         self._sil = (0.0, 0.0)     # (sil_coeff, sil_value_coeff)
         self._sil_rows = None      # B_ppo: the leading unsorted rows of the minibatch that are PPO rows (set_sil_rows)
+        # "ppo+smooth": cadre_ppo_smooth_loss — PPO rows and their successor rows in one minibatch, coupled in pairs
+        self._smooth_coeff = 0.0
+        self._smooth_rows = None   # B_ppo: the leading unsorted rows of the minibatch that are PPO rows (set_smooth_rows)
+        self._smooth_tables = None  # (ctrl: device float32 [2][64], (scale_steer, scale_throttle)); the address is part of the graph keys
         hip.lib()
 
     # ------------------------------------------------------------------ loss selection
     def set_loss(self, mode, label_smoothing=0.0, bc_coeff=1.0, demo_coeff=None, demo_value_coeff=None, beta_clone=1.0,
-                 aux_value_coeff=1.0, suggest_coeff=None, sil_coeff=None, sil_value_coeff=None):
+                 aux_value_coeff=1.0, suggest_coeff=None, sil_coeff=None, sil_value_coeff=None, smooth_coeff=None):
         """"ppo" (default): the clipped-surrogate loss.  "bc": behaviour cloning — cross-entropy against the demonstrated bin
         (workspace `actions`; -1 = no label for that head) with `label_smoothing` in [0, 1) and weight `bc_coeff`, the critic
         regressed on workspace `returns`, the learner's own value_coeff / ent_coeff, per-row weights from the `adv` slot;
@@ -161,9 +165,29 @@ class PPOLearnerHIP:
         the adaptive lr and rank consensus work as in "ppo" and see the PPO rows only.  In device-hyper mode the two
         coefficients live in the block (set_hyper(sil_coeff=, sil_value_coeff=)): a changed value needs no new graph.  None
         keeps the current coefficient.  The SIL losses / statistics / per-row w of a step are in workspace(B)["sil_losses"] /
-        ["sil_stats"] / ["sil_w"] (static tensors, as the kinds in ["row_kind"])."""
-        if mode not in ("ppo", "bc", "ppo+demo", "aux", "ppo+suggest", "ppo+sil"):
-            raise ValueError("set_loss: mode %r (known: 'ppo', 'bc', 'ppo+demo', 'aux', 'ppo+suggest', 'ppo+sil')" % (mode,))
+        ["sil_stats"] / ["sil_w"] (static tensors, as the kinds in ["row_kind"]).
+        "ppo+smooth": the clipped-surrogate loss on the first set_smooth_rows() unsorted rows of the minibatch, the rest being
+        their successor rows (row t + 1 of the same storages), plus `smooth_coeff` * head_scale * mean over the pair slots of
+        d^2, d the difference of the two rows' mean controls (CAPS's temporal term; set_smooth_tables gives the control tables)
+        — in ONE launch (cadre_ppo_smooth_loss); the gradient goes into both rows of a pair.  Diagnostics, the KL gate, the
+        adaptive lr and rank consensus work as in "ppo" and see the PPO rows only, without the term.  In device-hyper mode
+        the coefficient lives in the block (set_hyper(smooth_coeff=)): a changed value needs no new graph.  None keeps the
+        current coefficient.  The pairs of a step are in workspace(B)["row_kind"] / ["mate"] (cadre_smooth_mates writes them
+        before the step), its smoothness loss / statistics / per-row d in ["smooth_losses"] / ["smooth_stats"] / ["smooth_d"]."""
+        if mode not in ("ppo", "bc", "ppo+demo", "aux", "ppo+suggest", "ppo+sil", "ppo+smooth"):
+            raise ValueError("set_loss: mode %r (known: 'ppo', 'bc', 'ppo+demo', 'aux', 'ppo+suggest', 'ppo+sil', 'ppo+smooth')" % (mode,))
+        if mode == "ppo+smooth":
+            if isinstance(smooth_coeff, bool):
+                raise ValueError("set_loss: smooth_coeff=%r" % (smooth_coeff,))
+            try:
+                sm = self._smooth_coeff if smooth_coeff is None else float(smooth_coeff)
+            except (TypeError, ValueError):
+                raise ValueError("set_loss: smooth_coeff=%r" % (smooth_coeff,))
+            if not np.isfinite(sm):
+                raise ValueError("set_loss: smooth_coeff=%r" % (smooth_coeff,))
+            self._smooth_coeff = sm
+            if self._hp_on:
+                self.set_hyper(smooth_coeff=sm)
         if mode == "ppo+sil":
             if any(isinstance(v, bool) for v in (sil_coeff, sil_value_coeff)):
                 raise ValueError("set_loss: sil_coeff=%r, sil_value_coeff=%r" % (sil_coeff, sil_value_coeff))
@@ -308,6 +332,69 @@ class PPOLearnerHIP:
                                        hip.ptr(self._stop) if (stats and self.target_kl is not None) else None,
                                        hip.ptr(w["sil_stats"]), hip.SIL_STATS_FIELDS, hip.ptr(ord_t), st),
                   "cadre_ppo_sil_loss")
+
+    # ------------------------------------------------------------------ temporal smoothness
+    def set_smooth_rows(self, B_ppo):
+        """"ppo+smooth": unsorted rows 0 .. B_ppo - 1 of the next minibatches are PPO rows, the rest successor rows."""
+        if B_ppo is not None and int(B_ppo) < 0:
+            raise ValueError("set_smooth_rows: B_ppo=%r" % (B_ppo,))
+        self._smooth_rows = None if B_ppo is None else int(B_ppo)
+
+    def set_smooth_tables(self, ctrl, head_scale=(1.0, 1.0)):
+        """The control tables of the "ppo+smooth" loss: device float32 [2][64], contiguous, the control value of bin k of head h
+        in [h][k] (cadre_amd.smooth.smooth_tables; None: forget them), and the two head scales (finite, >= 0).  The table's
+        address is baked into captured graphs, so it is part of their key, as the scales are."""
+        if ctrl is None:
+            self._smooth_tables = None
+            return
+        if (not ctrl.is_cuda or ctrl.dtype != torch.float32 or tuple(ctrl.shape) != (2, 64) or not ctrl.is_contiguous()):
+            raise ValueError("set_smooth_tables: expected a contiguous device float32 tensor [2][64]")
+        try:
+            hs = (float(head_scale[0]), float(head_scale[1]))
+            ok = len(head_scale) == 2 and all(np.isfinite(x) and x >= 0.0 for x in hs)
+        except (TypeError, ValueError, IndexError):
+            ok = False
+        if not ok:
+            raise ValueError("set_smooth_tables: head_scale=%r (two finite numbers >= 0)" % (head_scale,))
+        self._smooth_tables = (ctrl, hs)
+
+    def _smooth_ws(self, w, B):
+        """The static tensors of the "ppo+smooth" loss in workspace(B): (row_kind, mate), which cadre_smooth_mates overwrites
+        before every step."""
+        if "mate" not in w:
+            dev, nblk = self.a.device, (B + 15) // 16
+            if "row_kind" not in w:
+                w["row_kind"] = torch.zeros(2, B, dtype=torch.int32, device=dev)
+            w["mate"] = torch.full((2, B), -1, dtype=torch.int32, device=dev)
+            w["smooth_d"] = torch.zeros(2, B, device=dev)
+            w["smooth_losses"] = torch.zeros(1, device=dev)
+            w["smooth_stats"] = torch.zeros(2, hip.SMOOTH_STATS_FIELDS, device=dev)
+            w["smooth_scratch"] = torch.zeros(2 * nblk * hip.SMOOTH_STATS_FIELDS, device=dev)
+        return w["row_kind"], w["mate"]
+
+    def _smooth_launch(self, w, B, inv_b):
+        """cadre_ppo_smooth_loss on the tower outputs in workspace(B), in the place of the PPO loss."""
+        a, S = self.a, self.S
+        O3, dO3, NP = w["O3"], w["dO3"], a.NP
+        B_ppo = self._smooth_rows
+        if B_ppo is None or not 0 < B_ppo < B:
+            raise hip.CadreHipError("the 'ppo+smooth' loss needs set_smooth_rows(B_ppo) with 0 < B_ppo < B (got %r, B = %d)" % (B_ppo, B))
+        if self._smooth_tables is None:
+            raise hip.CadreHipError("the 'ppo+smooth' loss needs set_smooth_tables(ctrl, head_scale) first")
+        ctrl, hs = self._smooth_tables
+        self._smooth_ws(w, B)
+        stats = self._loss_stats()
+        srow, sscr = self._stats_ws(w, B) if stats else (None, None)
+        ord_t = getattr(a, "ord", None)
+        hip.check(hip.lib().cadre_ppo_smooth_loss(
+            hip.ptr(O3), NP, 2 * B * NP, hip.ptr(O3[1]), NP, 2 * B * NP, hip.ptr(w["actions"]), hip.ptr(w["commands"]),
+            hip.ptr(w["old_values"]), hip.ptr(w["returns"]), hip.ptr(w["old_logp"]), hip.ptr(w["adv"]), hip.ptr(w["row_kind"]),
+            hip.ptr(w["mate"]), hip.ptr(ctrl), B, a.C, a.n_out[0], a.n_out[1], hip.ptr(self._hp) if self._hp_on else None,
+            self.clip, self.vc, self.cc, self.ec, inv_b, self._smooth_coeff, hs[0], hs[1], 1.0 / (B - B_ppo), hip.ptr(w["losses"]),
+            hip.ptr(w["smooth_losses"]), hip.ptr(w["smooth_d"]), hip.ptr(dO3), hip.ptr(dO3[1]), hip.ptr(w["loss_scratch"]),
+            hip.ptr(w["smooth_scratch"]), hip.ptr(w["sync"][a.Z * S:]), hip.ptr(srow), srow.shape[1] if stats else 0,
+            hip.ptr(sscr), self._loss_tkl(), hip.ptr(self._stop) if (stats and self.target_kl is not None) else None,
+            hip.ptr(w["smooth_stats"]), hip.SMOOTH_STATS_FIELDS, hip.ptr(ord_t), hip.stream()), "cadre_ppo_smooth_loss")
 
     # ------------------------------------------------------------------ exploration suggestions
     def set_suggest_tables(self, prior, Z=None):
@@ -575,6 +662,12 @@ class PPOLearnerHIP:
         # the self-imitation loss is a mode: B_ppo by value always, the two coefficients unless they live in the block
         if self.loss_mode == "ppo+sil":
             key = key + ((("sil", self._sil_rows) + (() if self._hp_on else self._sil)),)
+        # the smoothness loss is a mode: B_ppo, the control table's address and the head scales by value always, the coefficient
+        # unless it lives in the block
+        if self.loss_mode == "ppo+smooth":
+            t = self._smooth_tables
+            key = key + ((("smooth", self._smooth_rows) + ((None,) if t is None else (t[0].data_ptr(),) + t[1]) +
+                          (() if self._hp_on else (self._smooth_coeff,))),)
         return key
 
     # ------------------------------------------------------------------ device-resident hyper-parameters
@@ -625,6 +718,7 @@ class PPOLearnerHIP:
         m[hip.HP_DEMO_COEFF], m[hip.HP_DEMO_VALUE_COEFF] = self._demo[1], self._demo[2]
         m[hip.HP_SUGGEST_COEFF] = self._sug_coeff
         m[hip.HP_SIL_COEFF], m[hip.HP_SIL_VALUE_COEFF] = self._sil
+        m[hip.HP_SMOOTH_COEFF] = self._smooth_coeff
         if np.isnan(m[hip.HP["lr"]]):
             m[hip.HP["lr"]] = 3e-4
         self._hp_on = True
@@ -655,7 +749,8 @@ class PPOLearnerHIP:
     @staticmethod
     def _hp_index(name):
         """Block index of a named field: hip.HP_INDEX, or one of the fields a single loss kernel reads."""
-        own = dict(suggest_coeff=hip.HP_SUGGEST_COEFF, sil_coeff=hip.HP_SIL_COEFF, sil_value_coeff=hip.HP_SIL_VALUE_COEFF)
+        own = dict(suggest_coeff=hip.HP_SUGGEST_COEFF, sil_coeff=hip.HP_SIL_COEFF, sil_value_coeff=hip.HP_SIL_VALUE_COEFF,
+                   smooth_coeff=hip.HP_SMOOTH_COEFF)
         return own[name] if name in own else hip.HP_INDEX[name]
 
     def _need_hp(self, what):
@@ -663,17 +758,20 @@ class PPOLearnerHIP:
             raise hip.CadreHipError("%s needs device-hyper mode: call set_device_hyper() first" % what)
 
     def set_hyper(self, lr=None, clip=None, ent_coeff=None, value_coeff=None, clip_coeff=None, max_grad_norm=None,
-                  demo_coeff=None, demo_value_coeff=None, suggest_coeff=None, sil_coeff=None, sil_value_coeff=None):
+                  demo_coeff=None, demo_value_coeff=None, suggest_coeff=None, sil_coeff=None, sil_value_coeff=None,
+                  smooth_coeff=None):
         """New values for the given block fields: the mirror is updated and ONE asynchronous host-to-device copy (of the
         span of fields that changed) is enqueued on the current stream — no synchronisation, no new graph.  Steps enqueued
         afterwards use the new values.  An explicit lr also resets the KL-adaptive controller's current value.
         demo_coeff / demo_value_coeff: the two coefficients of the "ppo+demo" loss (read by cadre_ppo_demo_loss only).
         suggest_coeff: the coefficient of the "ppo+suggest" loss (read by cadre_ppo_sug_loss only).
-        sil_coeff / sil_value_coeff: the two coefficients of the "ppo+sil" loss (read by cadre_ppo_sil_loss only)."""
+        sil_coeff / sil_value_coeff: the two coefficients of the "ppo+sil" loss (read by cadre_ppo_sil_loss only).
+        smooth_coeff: the coefficient of the "ppo+smooth" loss (read by cadre_ppo_smooth_loss only)."""
         self._need_hp("set_hyper")
         new = dict(lr=lr, clip=clip, ent_coeff=ent_coeff, value_coeff=value_coeff, clip_coeff=clip_coeff,
                    max_grad_norm=max_grad_norm, demo_coeff=demo_coeff, demo_value_coeff=demo_value_coeff,
-                   suggest_coeff=suggest_coeff, sil_coeff=sil_coeff, sil_value_coeff=sil_value_coeff)
+                   suggest_coeff=suggest_coeff, sil_coeff=sil_coeff, sil_value_coeff=sil_value_coeff,
+                   smooth_coeff=smooth_coeff)
         idx = []
         for name, v in new.items():
             if v is None:
@@ -692,6 +790,7 @@ class PPOLearnerHIP:
         self._demo = (self._demo[0], float(m[hip.HP_DEMO_COEFF]), float(m[hip.HP_DEMO_VALUE_COEFF]))
         self._sug_coeff = float(m[hip.HP_SUGGEST_COEFF])
         self._sil = (float(m[hip.HP_SIL_COEFF]), float(m[hip.HP_SIL_VALUE_COEFF]))
+        self._smooth_coeff = float(m[hip.HP_SMOOTH_COEFF])
         if any(hip.HP["clip"] <= i <= hip.HP["ent_coeff"] for i in idx):
             self._hp_moved = True
         if idx:
@@ -1075,6 +1174,8 @@ class PPOLearnerHIP:
             self._aux_launch(w, B, inv_b, sorted_rows)  # critic + KL clone against the recorded table: the rest is indifferent
         elif front and self.loss_mode == "ppo+sil":
             self._sil_launch(w, B, inv_b, sorted_rows)   # PPO rows + self-imitation rows: two launches, the rest is indifferent
+        elif front and self.loss_mode == "ppo+smooth":
+            self._smooth_launch(w, B, inv_b)            # PPO rows + their successor rows, coupled in pairs: the rest is indifferent
         elif front and self.loss_mode == "ppo+suggest":
             self._sug_launch(w, B, inv_b)               # PPO + the event priors on marked rows: the rest is indifferent
         elif front:

@@ -544,7 +544,8 @@ class CadreAgent(object):
 
     def update_policy_from_storages(self, batches, sync=True, mlp_grads_ready=None, stats_row=None, evaluate=False,
                                     demo=None, demo_stats_row=None, demo_label_smoothing=None, demo_coeff=None,
-                                    demo_value_coeff=None, sil=None, sil_stats_row=None):
+                                    demo_value_coeff=None, sil=None, sil_stats_row=None, smooth=None,
+                                    smooth_stats_row=None):
         """Fast path of the learner section: `batches` = [(steer_storage, steer_idx, steer_adv,
         throttle_storage, throttle_idx, throttle_adv), ...] one entry per worker (equal sizes).
         Same math as feed_forward_generator -> update_policy, but the minibatch gather writes
@@ -568,7 +569,46 @@ class CadreAgent(object):
         the call) with the learner's current SIL coefficients: total = the PPO loss + sil_coeff * mean(-lp w) +
         sil_value_coeff * mean(0.5 w^2), w = max(R - v, 0), the means over ALL SIL rows.  The three floats returned are the
         PPO terms; the two SIL terms and the rows' w stay on the device in learner.workspace(B)["sil_losses"] / ["sil_w"],
-        the SIL statistics go to `sil_stats_row` (device float32 [2][>= hip.SIL_STATS_FIELDS]).  Excludes `demo`."""
+        the SIL statistics go to `sil_stats_row` (device float32 [2][>= hip.SIL_STATS_FIELDS]).  Excludes `demo`.
+        `smooth` (temporal smoothness): what cadre_amd.smooth.Smoothness.step(batches) returns — (entries, rotation): E <= nW
+        successor entries of the same form (entry k: the storages and advantages of worker (rotation + k) mod nW, the index
+        vectors min(t + 1, T - 1) on the host) and the step's rotation.  They are appended behind the workers' entries, one
+        cadre_smooth_mates launch behind the gather / sort places the pairs, and the step runs the mixed loss
+        (PPOLearnerHIP.set_loss("ppo+smooth"), for the duration of the call) with the learner's current coefficient and
+        tables: total = the PPO loss + smooth_coeff * head_scale * mean over the pair slots of d^2.  The three floats returned
+        are the PPO terms; the smoothness term and the rows' d stay on the device in learner.workspace(B)["smooth_losses"] /
+        ["smooth_d"], the statistics go to `smooth_stats_row` (device float32 [2][>= hip.SMOOTH_STATS_FIELDS]).  Excludes
+        `demo` and `sil`."""
+        if smooth is not None:
+            if evaluate or demo or sil:
+                raise ValueError("update_policy_from_storages: successor rows have no evaluation form and exclude demo and sil "
+                                 "rows (a row carries one kind array)")
+            entries, rotation = smooth
+            nW, E = len(batches), len(entries)
+            if isinstance(rotation, bool) or not isinstance(rotation, int) or rotation < 0 or not 1 <= E <= nW:
+                raise ValueError("update_policy_from_storages: smooth=(entries, rotation) with 1 <= len(entries) <= %d worker "
+                                 "entries and an integer rotation >= 0 (got %d, %r)" % (nW, E, rotation))
+            for k, e in enumerate(entries):
+                b = batches[(rotation + k) % nW]
+                if e[0] is not b[0] or e[3] is not b[3] or e[2] is not b[2] or e[5] is not b[5]:
+                    raise ValueError("update_policy_from_storages: successor entry %d does not carry the storages and advantages "
+                                     "of worker %d" % (k, (rotation + k) % nW))
+            lrn = self.learner
+            prev = (lrn.loss_mode, lrn._smooth_rows)
+            lrn.set_loss("ppo+smooth")
+            lrn.set_smooth_rows(nW * batches[0][1].numel())
+            self._smooth_step = (nW, E, rotation)
+            try:
+                out = self._update_from_storages(list(batches) + list(entries), sync, mlp_grads_ready, stats_row, False)
+                if smooth_stats_row is not None:
+                    B = (nW + E) * batches[0][1].numel()
+                    smooth_stats_row[:, :hip.SMOOTH_STATS_FIELDS].copy_(lrn.workspace(B)["smooth_stats"])
+                return out
+            finally:
+                lrn.loss_mode, lrn._smooth_rows = prev
+                self._smooth_step = None
+        if smooth_stats_row is not None:
+            raise ValueError("update_policy_from_storages: smooth_stats_row without smooth entries")
         if sil:
             if evaluate or demo:
                 raise ValueError("update_policy_from_storages: sil rows have no evaluation form and exclude demo rows "
@@ -642,9 +682,9 @@ class CadreAgent(object):
         if any((st_._ldo, st_.seq_length, st_._ldh) != geo for b in batches for st_ in (b[0], b[3])):
             # storages of different geometry (feature pitch / window length): one gather launch per storage with its
             # own strides (cadre_gather_minibatch) — the one-launch table below assumes a single geometry
-            if self.learner.loss_mode == "ppo+suggest":
-                raise ValueError("the 'ppo+suggest' loss needs storages of one geometry: the kinds of the minibatch are placed "
-                                 "by one launch beside the one-launch gather")
+            if self.learner.loss_mode in ("ppo+suggest", "ppo+smooth"):
+                raise ValueError("the %r loss needs storages of one geometry: the kinds of the minibatch are placed "
+                                 "by one launch beside the one-launch gather" % (self.learner.loss_mode,))
             self._gather_entry = "cadre_gather_minibatch_ft" if ft else "cadre_gather_minibatch"
             for i, (ss, si, sa, ts, ti, ta) in enumerate(batches):
                 for hd, (stor, idx, adv) in enumerate(((ss, si, sa), (ts, ti, ta))):
@@ -713,6 +753,16 @@ class CadreAgent(object):
             if stable is None:
                 stable = cache[("suggest",) + sptrs] = torch.tensor(sptrs, dtype=torch.int64).to(self.device)
             self._suggest_src = (stable, stage[1], Bw, s0.num_steps)
+        if self.learner.loss_mode == "ppo+smooth" and record is None and not evaluate:
+            # {masks, time_limits or 0, command} of the workers' storages, source by source; the launch itself follows the
+            # gather / sort, which writes `pos`
+            nWs = self._smooth_step[0]
+            sptrs = tuple(p for stor, _ in pairs[:2 * nWs]
+                          for p in (hip.ptr(stor.masks), hip.ptr(stor.time_limits) if stor._tl_used else 0, hip.ptr(stor.command)))
+            stable = cache.get(("smooth",) + sptrs)
+            if stable is None:
+                stable = cache[("smooth",) + sptrs] = torch.tensor(sptrs, dtype=torch.int64).to(self.device)
+            self._smooth_src = (stable, stage[1], Bw, s0.num_steps)
         stage[2] = torch.cuda.Event()
         stage[2].record()
         gs = getattr(self, "gather_sorted", None)     # None: CADRE_GATHER_SORTED decides (the default); True / False: this agent's switch
@@ -767,6 +817,14 @@ class CadreAgent(object):
             stable, idx_d, Bw, T = self._suggest_src
             hip.check(L.cadre_suggest_rows(hip.ptr(stable), 2 * nW, hip.ptr(idx_d), Bw, T, hip.ptr(w["pos"]) if srt else None, B,
                                            hip.ptr(self.learner._sug_ws(w, B)), st), "cadre_suggest_rows")
+        if self.learner.loss_mode == "ppo+smooth" and not evaluate:
+            # the kinds and the partners of the minibatch's rows into the static workspace tensors the captured loss launch reads
+            stable, idx_d, Bw, T = self._smooth_src
+            nWs, E, rotation = self._smooth_step
+            kinds, mates = self.learner._smooth_ws(w, B)
+            hip.check(L.cadre_smooth_mates(hip.ptr(stable), hip.ptr(idx_d), nWs, E, Bw, T, a.C, rotation,
+                                           hip.ptr(w["pos"]) if srt else None, B, hip.ptr(kinds), hip.ptr(mates), st),
+                      "cadre_smooth_mates")
         if evaluate and self.learner.loss_mode == "aux":   # aux_record_from_storages: forward + the record launch only
             return self.learner.aux_record(B, sorted_rows=srt)
         if evaluate:                                     # imitate_from_storages(evaluate=True): forward + loss only

@@ -409,6 +409,66 @@ def apply_sil(agent, sil, episode, max_episode):
     return v
 
 
+def smoothness(agent, train_cfg, fused_gather=True):
+    """train_cfg["smoothness"] (absent / None: None — nothing runs, nothing is allocated): the Smoothness of a run with the
+    temporal action-smoothness term in the PPO step (cadre_amd.smooth.smooth_config for the keys, smooth_runner for what is
+    refused at start-up and why)."""
+    cfg = _get(train_cfg, "smoothness")
+    if cfg is None:
+        return None
+    from ..smooth import smooth_runner
+    return smooth_runner(agent, cfg, fused_gather, _get(train_cfg, "demo_mix"), _get(train_cfg, "suggest"),
+                         _get(train_cfg, "self_imitation"), _get(train_cfg, "sample_reuse"))
+
+
+def apply_smooth(agent, smooth, episode, max_episode):
+    """The smoothness coefficient of `episode` (Smoothness.coeff through schedule_value) into the learner's device
+    hyper-parameter block, beside apply_sil: a moving coefficient replays the captured graphs as they are.  Returns the
+    coefficient set (None without the term)."""
+    if smooth is None:
+        return None
+    v = schedule_value(smooth.coeff, episode, max_episode)
+    agent.learner.set_device_hyper(True)
+    agent.learner.set_hyper(smooth_coeff=v)
+    return v
+
+
+def _rewind(smooth, rollouts):
+    """With the smoothness term every rollout starts at row 0 of its storages, so that rows 0 .. T - 1 are one rollout in
+    time order (without it the cursors keep the reference's modulo-(T + 1) drift)."""
+    if smooth is not None:
+        for pair in rollouts:
+            for s in pair:
+                s.step = 0
+
+
+def _smooth_kw(smooth, batches):
+    """Keyword arguments of update_policy_from_storages for the next step of the section ({} without the term)."""
+    if smooth is None:
+        return {}
+    kw = dict(smooth=smooth.step(batches))
+    row = smooth.next_stats_row()
+    if row is not None:
+        kw["smooth_stats_row"] = row
+    return kw
+
+
+def _smooth_stats(stats, smooth):
+    if stats is not None and smooth is not None:
+        stats["smooth"] = smooth.summary()
+
+
+def _check_smooth(smooth, demo, suggest, reuse, sil, fused_gather=True):
+    if smooth is None:
+        return
+    if demo is not None or suggest is not None or sil is not None:
+        raise ValueError("smooth excludes demo, suggest and sil (a row carries one kind array)")
+    if reuse is not None:
+        raise ValueError("smooth excludes reuse (the successor rows are the rows behind the PPO rows, where the stale rows ride)")
+    if not fused_gather:
+        raise ValueError("smooth needs fused_gather=True")
+
+
 def _sil_kw(sil, Bw, episode, epoch, step):
     """Keyword arguments of update_policy_from_storages for step `step` of epoch `epoch` ({} without a buffer, or while it
     has no eligible row: the step is then the plain PPO step, launch for launch)."""
@@ -621,6 +681,9 @@ def stats_line(episode, stats):
     if "sil" in stats:                                 # self-imitation: the weights of the section's SIL rows
         from ..selfimit import sil_stats_text
         line += sil_stats_text(stats)
+    if "smooth" in stats:                              # temporal smoothness: the pairs' |d| and the realised jitter
+        from ..smooth import smooth_stats_text
+        line += smooth_stats_text(stats)
     return line
 
 
@@ -638,7 +701,7 @@ def _check_sil(sil, demo, suggest, reuse, path_ok=True):
 def learner_section(agent, steer_rollout, throttle_rollout, done, train_cfg, shared_grad_buffers,
                     optimizer=None, traffic_light=None, counter=None, shared_model_list=None, in_process_chief=True,
                     fused_gather=True, losses_on_device=False, step_events=None, stats=None, reward_scaler=None,
-                    demo=None, episode=0, reuse=None, suggest=None, sil=None):
+                    demo=None, episode=0, reuse=None, suggest=None, sil=None, smooth=None):
     """train.py:76-110.  Returns (value_loss_list, policy_loss_list, ent_loss_list).
     With `in_process_chief` (one process per GPU) the optimiser step runs right after the gradient
     all-reduce instead of waiting on a separate chief process.  `fused_gather` uses the storage ->
@@ -675,7 +738,10 @@ def learner_section(agent, steer_rollout, throttle_rollout, done, train_cfg, sha
     `suggest` (a cadre_amd.suggest.Suggestions, needs fused_gather, excludes `demo`): exploration suggestions, as in
     learner_section_multi.
     `sil` (a cadre_amd.selfimit.SelfImitationBuffer for one environment; needs fused_gather and the in-process chief,
-    excludes `demo`, `suggest` and `reuse`) with `episode`: self-imitation, as in learner_section_multi."""
+    excludes `demo`, `suggest` and `reuse`) with `episode`: self-imitation, as in learner_section_multi.
+    `smooth` (a cadre_amd.smooth.Smoothness; needs fused_gather, excludes `demo`, `suggest`, `sil` and `reuse`): the temporal
+    smoothness term, as in learner_section_multi.  Raises ValueError when a storage's cursor does not stand at T."""
+    _check_smooth(smooth, demo, suggest, reuse, sil, fused_gather)
     if demo is not None and not fused_gather:
         raise ValueError("demo needs fused_gather=True")
     _check_sil(sil, demo, suggest, reuse, fused_gather and in_process_chief)
@@ -698,7 +764,7 @@ def learner_section(agent, steer_rollout, throttle_rollout, done, train_cfg, sha
         out = _learner_section(agent, steer_rollout, throttle_rollout, done, train_cfg, shared_grad_buffers, optimizer,
                                traffic_light, counter, shared_model_list, in_process_chief, fused_gather, losses_on_device,
                                step_events, use_adv_norm, sec, lr, reward_scaler, cons, demo, episode, reuse, suggest,
-                               stats, sil)
+                               stats, sil, smooth)
     finally:
         if sec is not None:
             agent.learner.set_update_modes()
@@ -710,6 +776,7 @@ def learner_section(agent, steer_rollout, throttle_rollout, done, train_cfg, sha
         _reuse_stats(stats, reuse)
         _suggest_stats(stats, suggest)
         _sil_stats(stats, sil)
+        _smooth_stats(stats, smooth)
         return out
     dev_losses, (vl, pl, el) = out
     host = sec.finish(stats, tkl is not None, losses=torch.stack(dev_losses) if dev_losses else None)
@@ -717,6 +784,7 @@ def learner_section(agent, steer_rollout, throttle_rollout, done, train_cfg, sha
     _reuse_stats(stats, reuse)
     _suggest_stats(stats, suggest)
     _sil_stats(stats, sil)
+    _smooth_stats(stats, smooth)
     if host is not None:
         for v, p, e in host.tolist():
             vl.append(v); pl.append(p); el.append(e)
@@ -726,7 +794,10 @@ def learner_section(agent, steer_rollout, throttle_rollout, done, train_cfg, sha
 def _learner_section(agent, steer_rollout, throttle_rollout, done, train_cfg, shared_grad_buffers, optimizer, traffic_light,
                      counter, shared_model_list, in_process_chief, fused_gather, losses_on_device, step_events, use_adv_norm,
                      sec, lr, reward_scaler=None, cons=False, demo=None, episode=0, reuse=None, suggest=None, stats=None,
-                     sil=None):
+                     sil=None, smooth=None):
+    if smooth is not None:                           # (the cursor check comes before any launch of the section)
+        smooth.begin_section([(steer_rollout, throttle_rollout)],
+                             train_cfg["ppo_epoch"] * _steps_per_epoch(steer_rollout) if stats is not None else 0)
     nv_s, nv_t = agent.get_value(done, steer_rollout.get_last(as_tensor=True), throttle_rollout.get_last(as_tensor=True))
     if reward_scaler is not None or steer_rollout._tl_used or throttle_rollout._tl_used:
         steer_adv, throttle_adv = RolloutStorage.finish_rollouts(
@@ -747,7 +818,7 @@ def _learner_section(agent, steer_rollout, throttle_rollout, done, train_cfg, sh
     try:
         return _learner_steps(agent, steer_rollout, throttle_rollout, steer_adv, throttle_adv, train_cfg, shared_grad_buffers,
                               optimizer, traffic_light, counter, shared_model_list, in_process_chief, fused_gather,
-                              losses_on_device, step_events, sec, lr, demo, episode, reuse, suggest, sil)
+                              losses_on_device, step_events, sec, lr, demo, episode, reuse, suggest, sil, smooth)
     finally:
         if suggest is not None:
             agent.learner.loss_mode = sug_prev
@@ -755,7 +826,7 @@ def _learner_section(agent, steer_rollout, throttle_rollout, done, train_cfg, sh
 
 def _learner_steps(agent, steer_rollout, throttle_rollout, steer_adv, throttle_adv, train_cfg, shared_grad_buffers, optimizer,
                    traffic_light, counter, shared_model_list, in_process_chief, fused_gather, losses_on_device, step_events, sec,
-                   lr, demo, episode, reuse, suggest, sil=None):
+                   lr, demo, episode, reuse, suggest, sil=None, smooth=None):
     dev_losses = []
     vl, pl, el = [], [], []
     n_step = 0
@@ -776,10 +847,11 @@ def _learner_steps(agent, steer_rollout, throttle_rollout, steer_adv, throttle_a
             row = None if sec is None else sec.next_row()
             if kind == "idx":
                 stale = [] if reuse is None else reuse.entries(episode, epoch, j, a.numel())
+                live = [(steer_rollout, a, steer_adv, throttle_rollout, b, throttle_adv)]
                 dev_losses.append(agent.update_policy_from_storages(
-                    [(steer_rollout, a, steer_adv, throttle_rollout, b, throttle_adv)] + stale, sync=False, mlp_grads_ready=hook,
+                    live + stale, sync=False, mlp_grads_ready=hook,
                     stats_row=row, **_demo_kw(demo, a.numel(), episode, n_step, sec),
-                    **_sil_kw(sil, a.numel(), episode, epoch, j)))
+                    **_sil_kw(sil, a.numel(), episode, epoch, j), **_smooth_kw(smooth, live)))
                 if suggest is not None:
                     suggest.collect(agent.learner)
                 if sil is not None:
@@ -855,10 +927,12 @@ def train(rank, train_cfg, agent_cfg, env_cfg, rollout_cfg, traffic_light=None, 
     reuse = _reuse_runner(agent, train_cfg, shared_grad_buffers, rank, traffic_light is None, ck_interval, ck_resume,
                           shared_model_list)
     sil = self_imitation(agent, train_cfg, shared_grad_buffers, rank, traffic_light is None, True, ck_interval, ck_resume)
+    smooth = smoothness(agent, train_cfg)
     obs = env.reset()
     done = False
     log_stats = bool(_get(train_cfg, "log_stats", False))
     for episode in range(first_episode, train_cfg.max_episode):
+        _rewind(smooth, [(steer_rollout, throttle_rollout)])
         for _ in range(num_steps):
             command = obs["command"]
             raw = dict(obs, rgb=obs["rgb"].copy(), route_fig=obs["route_fig"].copy()) if recorder is not None else None
@@ -884,6 +958,7 @@ def train(rank, train_cfg, agent_cfg, env_cfg, rollout_cfg, traffic_light=None, 
         apply_demo_mix(agent, demo, episode, train_cfg.max_episode)
         apply_suggest(agent, suggest, episode, train_cfg.max_episode)
         apply_sil(agent, sil, episode, train_cfg.max_episode)
+        apply_smooth(agent, smooth, episode, train_cfg.max_episode)
         vl, pl, el = learner_section(agent, steer_rollout, throttle_rollout, done, train_cfg, shared_grad_buffers,
                                      traffic_light=traffic_light, counter=counter,
                                      shared_model_list=shared_model_list,
@@ -891,7 +966,8 @@ def train(rank, train_cfg, agent_cfg, env_cfg, rollout_cfg, traffic_light=None, 
                                      reward_scaler=agent.reward_scaler, demo=demo, episode=episode,
                                      **({} if reuse is None else dict(reuse=reuse.window_for([(steer_rollout, throttle_rollout)]))),
                                      **({} if suggest is None else dict(suggest=suggest)),
-                                     **({} if sil is None else dict(sil=sil.buffer_for([(steer_rollout, throttle_rollout)]))))
+                                     **({} if sil is None else dict(sil=sil.buffer_for([(steer_rollout, throttle_rollout)]))),
+                                     **({} if smooth is None else dict(smooth=smooth)))
         log_now = episode % train_cfg.log_interval == 0 and rank == 0 and logger is not None
         # (the auxiliary phase: before the log line, the snapshot and the checkpoint, which then see its result)
         aux_records = _aux_after_section(aux, agent, train_cfg, episode, [(steer_rollout, throttle_rollout)],
@@ -922,7 +998,8 @@ def train(rank, train_cfg, agent_cfg, env_cfg, rollout_cfg, traffic_light=None, 
 
 # ----------------------------------------------------------------------------- N environments in one process
 def learner_section_multi(agent, rollouts, dones, train_cfg, shared_grad_buffers, optimizer=None, losses_on_device=False,
-                          stats=None, reward_scaler=None, demo=None, episode=0, reuse=None, suggest=None, sil=None):
+                          stats=None, reward_scaler=None, demo=None, episode=0, reuse=None, suggest=None, sil=None,
+                          smooth=None):
     """train.py:76-110 for N workers that share one agent (`num_processes = N` on one GPU, chief.py:13-21 semantics):
     rollouts = [(steer_rollout, throttle_rollout), ...] per worker, dones[i] = worker i's last `done`.  Bootstrap values
     of all workers in one pass (get_values), GAE + advantage normalisation per storage, then for each ppo_epoch and
@@ -960,7 +1037,17 @@ def learner_section_multi(agent, rollouts, dones, train_cfg, shared_grad_buffers
     sil.after_step() writes the drawn rows' priorities back from the w the step computed (cadre_sil_scatter).  While the buffer
     has no eligible row in a head the step is the plain PPO step, launch for launch.  `stats` gains "sil" (filled, steps,
     w_mean, positive_share, nll, value_error, w_max, rows as (steer, throttle) pairs; one more small device-to-host copy).  The
-    caller appends the section's rollouts to the buffer afterwards (sil.append)."""
+    caller appends the section's rollouts to the buffer afterwards (sil.append).
+    `smooth` (a cadre_amd.smooth.Smoothness; excludes `demo`, `suggest`, `sil` and `reuse`): the temporal action-smoothness
+    term.  Every step carries smooth.step(batches) — E successor entries (row min(t + 1, T - 1) of the storages of E of the N
+    workers, rotating with the step number of the section) behind the workers' entries — and runs the mixed loss
+    (update_policy_from_storages(smooth=)); the KL gate, the diagnostics and the adaptive lr see the PPO rows only.  The
+    rows of every storage must lie in time order in 0 .. T - 1: ValueError when a storage's cursor does not stand at T when
+    the section starts.  `stats` gains "smooth" (pairs, mean_abs_d, max_abs_d, d2 as (steer, throttle) pairs and "jitter",
+    what the section's rollouts did: one cadre_action_jitter launch per section; one more small device-to-host copy)."""
+    _check_smooth(smooth, demo, suggest, reuse, sil)
+    if smooth is not None:                           # (the cursor check comes before any launch of the section)
+        smooth.begin_section(rollouts, train_cfg["ppo_epoch"] * _steps_per_epoch(rollouts[0][0]) if stats is not None else 0)
     if suggest is not None and demo is not None:
         raise ValueError("suggest excludes demo (a row carries one kind array)")
     _check_sil(sil, demo, suggest, reuse)
@@ -995,12 +1082,13 @@ def learner_section_multi(agent, rollouts, dones, train_cfg, shared_grad_buffers
             idx = [(s.sample_indices(), t.sample_indices()) for s, t in rollouts]
             for j in range(len(idx[0][0])):
                 batches = [(s, idx[i][0][j], advs[i][0], t, idx[i][1][j], advs[i][1]) for i, (s, t) in enumerate(rollouts)]
+                smooth_kw = _smooth_kw(smooth, batches)
                 if reuse is not None:
                     batches += reuse.entries(episode, epoch, j, batches[0][1].numel())
                 dev_losses.append(agent.update_policy_from_storages(
                     batches, sync=False, stats_row=None if sec is None else sec.next_row(),
                     **_demo_kw(demo, batches[0][1].numel(), episode, len(dev_losses), sec),
-                    **_sil_kw(sil, batches[0][1].numel(), episode, epoch, j)))
+                    **_sil_kw(sil, batches[0][1].numel(), episode, epoch, j), **smooth_kw))
                 if suggest is not None:
                     suggest.collect(agent.learner)
                 if sil is not None:
@@ -1019,6 +1107,7 @@ def learner_section_multi(agent, rollouts, dones, train_cfg, shared_grad_buffers
         _reuse_stats(stats, reuse)
         _suggest_stats(stats, suggest)
         _sil_stats(stats, sil)
+        _smooth_stats(stats, smooth)
         return tuple(list(c) for c in zip(*host.tolist()))
     if sec is not None:
         sec.finish(stats, tkl is not None)
@@ -1026,6 +1115,7 @@ def learner_section_multi(agent, rollouts, dones, train_cfg, shared_grad_buffers
         _reuse_stats(stats, reuse)
         _suggest_stats(stats, suggest)
         _sil_stats(stats, sil)
+        _smooth_stats(stats, smooth)
     if losses_on_device:
         return losses
     vl, pl, el = [], [], []
@@ -1106,6 +1196,7 @@ def train_vec(rank, train_cfg, agent_cfg, env_cfg, rollout_cfg, num_envs, env_cl
     aux = _aux_runner(agent, train_cfg, shared_grad_buffers, rank, True, ck_interval, first_episode)
     reuse = _reuse_runner(agent, train_cfg, shared_grad_buffers, rank, True, ck_interval, ck_resume)
     sil = self_imitation(agent, train_cfg, shared_grad_buffers, rank, True, True, ck_interval, ck_resume)
+    smooth = smoothness(agent, train_cfg)
     obs = [env.reset() for env in envs]
     dones = [False] * num_envs
     log_stats = bool(_get(train_cfg, "log_stats", False))
@@ -1113,6 +1204,7 @@ def train_vec(rank, train_cfg, agent_cfg, env_cfg, rollout_cfg, num_envs, env_cl
     if callback is not None:
         callback("start", **state())
     for episode in range(first_episode, train_cfg.max_episode):
+        _rewind(smooth, rollouts)
         for _ in range(num_steps):
             commands = [o["command"] for o in obs]
             outs = agent.act_batch(obs)
@@ -1139,11 +1231,13 @@ def train_vec(rank, train_cfg, agent_cfg, env_cfg, rollout_cfg, num_envs, env_cl
         apply_demo_mix(agent, demo, episode, train_cfg.max_episode)
         apply_suggest(agent, suggest, episode, train_cfg.max_episode)
         apply_sil(agent, sil, episode, train_cfg.max_episode)
+        apply_smooth(agent, smooth, episode, train_cfg.max_episode)
         vl, pl, el = learner_section_multi(agent, rollouts, dones, train_cfg, shared_grad_buffers, optimizer=optimizer,
                                            stats=stats, reward_scaler=agent.reward_scaler, demo=demo, episode=episode,
                                            **({} if reuse is None else dict(reuse=reuse.window_for(rollouts))),
                                            **({} if suggest is None else dict(suggest=suggest)),
-                                           **({} if sil is None else dict(sil=sil.buffer_for(rollouts))))
+                                           **({} if sil is None else dict(sil=sil.buffer_for(rollouts))),
+                                           **({} if smooth is None else dict(smooth=smooth)))
         log_now = episode % train_cfg.log_interval == 0 and rank == 0 and logger is not None
         # (the auxiliary phase: before the log line, the snapshot and the checkpoint, which then see its result)
         aux_records = _aux_after_section(aux, agent, train_cfg, episode, rollouts, shared_grad_buffers, optimizer,

@@ -427,8 +427,9 @@ int cadre_grad_norms(const double* norms2, int32_t C, float* stats_row, int32_t 
 
 /* ---------------------------------------------------------------- device-resident hyper-parameters
  * The hyper-parameter block: a device array of CADRE_HP_FIELDS doubles (8-byte aligned) that the `_hp` entry points read
- * at RUN time, so a captured hipGraph follows whatever the block holds when it is replayed.  Fields past
- * CADRE_HP_SIL_VALUE_COEFF are reserved and zero.  betas and eps stay by-value arguments.  The block is written by ordinary
+ * at RUN time, so a captured hipGraph follows whatever the block holds when it is replayed.  The fields past
+ * CADRE_HP_SIL_VALUE_COEFF are reserved no longer: the one that was left, 15, is CADRE_HP_SMOOTH_COEFF, so every field of the
+ * block is in use.  betas and eps stay by-value arguments.  The block is written by ordinary
  * stream-ordered copies from the host, and by the KL-adaptive controller below. */
 #define CADRE_HP_FIELDS 16
 #define CADRE_HP_LR 0
@@ -451,6 +452,8 @@ enum { CADRE_HP_SUGGEST_COEFF = 12 };
 /* Two more, read by cadre_ppo_sil_loss only and zero for everyone else: the weight of the self-imitation policy term and of
  * its value term. */
 enum { CADRE_HP_SIL_COEFF = 13, CADRE_HP_SIL_VALUE_COEFF = 14 };
+/* The last field, read by cadre_ppo_smooth_loss only and zero for everyone else: the weight of the temporal smoothness term. */
+enum { CADRE_HP_SMOOTH_COEFF = 15 };
 /* cadre_ppo_loss / cadre_ppo_loss_stats with clip, value_coeff, clip_coeff, ent_coeff = (float)hp[CADRE_HP_*] (the same
  * kernel bodies, the scalars read once per thread before the row loop; the stats variant uses the same clip for its clip
  * fractions).  Equal values give results bit-identical to the by-value entry points.
@@ -833,6 +836,78 @@ int cadre_sil_draw(const uint32_t* q, int64_t Rcap, int64_t filled, const int64_
  * prio_eps not finite or < 0. */
 int cadre_sil_scatter(uint32_t* q, int64_t Rcap, const int64_t* idx, int32_t n, const float* sil_w, const int32_t* pos, int32_t B,
                       int32_t B_ppo, double alpha, double prio_eps, void* stream);
+
+/* ---------------------------------------------------------------- temporal action smoothness (csrc/smooth.hip)
+ * Mysore et al. 2021, "Regularizing Action Policies for Smooth Control" (CAPS), the temporal term: the squared distance between
+ * the policy's mean control at consecutive states, differentiated into both rows.  Successor rows (row t + 1 of a worker's own
+ * storages) ride behind the workers' rows of a minibatch; this is the first loss here that couples two rows.
+ *   c      float32 [2][64]: the control value of each bin per head (host-built; none is built into the kernels)
+ *   mu     = sum_k p_k c_k of a row (p: the policy's probabilities, an ordinal head through ordinal.h first), one wave sum with
+ *            every product and sum rounded on its own, lanes >= K contributing 0
+ *   d      = mu(row t) - mu(row t + 1)
+ *   total += smooth_coeff scale_head inv_bp sum over pair slots of d^2,   inv_bp = 1 / pair slots per step and head — invalid
+ *            slots included, so the coefficient's meaning does not move with the number of valid pairs (cadre_ppo_sug_loss's rule)
+ *
+ * The pair (row t, row t + 1) of a storage is VALID iff t <= T - 2, masks[t] != 0 (the factor cadre_gae_multi multiplies V[t + 1]
+ * by in row t's delta), time_limits[t] == 0 (NULL: no cuts), command[t] == command[t + 1] in 0 .. C - 1.  One device function
+ * states this for cadre_smooth_mates and cadre_action_jitter.
+ *
+ * cadre_smooth_mates: one launch after the gather / sort (where cadre_suggest_rows runs), outside the captured graph.  The
+ * minibatch has nW worker entries and E successor entries (1 <= E <= nW) of Bw rows; successor entry k belongs to worker
+ * (rotation + k) mod nW.  src_table = 2 nW records of three device pointers (int64) {masks f32 [T + 1], time_limits f32 [T + 1]
+ * or 0, command int32 [T + 1]}, record 2 w + head; idx = the step's staged index block int64 [2 (nW + E)][Bw], row 2 entry + head.
+ * Slot (worker w, row r) is valid iff the pair at t = idx[2 w + head][r] is valid and idx[2 (nW + k) + head][r] == t + 1.
+ *   row_kind int32 [2][Bt]  in workspace order (through pos [2][Bt]; NULL: the identity): 0 a PPO row, 1 a successor row
+ *   mate     int32 [2][Bt]  in workspace order: the partner's workspace position; -1 on both rows of an invalid slot and on the
+ *                           rows of a worker without a successor entry this step
+ * Both arrays are overwritten completely.  Refused before any launch: a NULL table, idx, row_kind or mate, nW outside 1 .. 16384,
+ * E outside 1 .. nW, Bw < 1, T < 2, C < 1, rotation < 0, Bt != (nW + E) Bw. */
+int cadre_smooth_mates(const void* src_table, const int64_t* idx, int32_t nW, int32_t E, int32_t Bw, int32_t T, int32_t C,
+                       int64_t rotation, const int32_t* pos, int32_t Bt, int32_t* row_kind, int32_t* mate, void* stream);
+/* cadre_ppo_smooth_loss: ONE loss launch where cadre_ppo_loss_ord / cadre_ppo_sil_loss stand in the update — the same addressing,
+ * grid (one wave per row, 16 rows per workgroup), `scratch` protocol (arrival counter zero on entry and left zero, partials
+ * combined by the last arriving workgroup in workgroup order: equal inputs give equal bits), `poison`, rank table `ord`,
+ * hp-or-by-value scalars and stats / target_kl / stop.  row_kind, mate int32 [2][B] as cadre_smooth_mates writes them.
+ *   kind 0, mate < 0   exactly the statements of cadre_ppo_loss_ord, bit for bit
+ *   kind 0, mate >= 0  those statements; then the wave reads the mate's logits row (the mate's own command net and position),
+ *                      forms mu_mate with the device function that forms mu_own, and adds, with d_own = mu_own - mu_mate,
+ *                        dlogits_k += (smooth_coeff scale_head inv_bp) (2 d_own) p_k (c_k - mu_own)
+ *                      (the sum of both gradients goes through ord_backward once on an ordinal head) and d^2 to the smoothness
+ *                      sum: only the kind-0 partner counts the pair
+ *   kind 1, mate >= 0  the smoothness gradient only (CAPS does not stop the gradient), dvalues = 0; old_values, old_logp, adv,
+ *                      returns, actions and values of the row are not read
+ *   kind 1, mate < 0, or a command out of range: zeros everywhere the row owns.  A mate outside 0 .. B - 1 or with a command out
+ *   of range counts as no mate.  Other nets' dlogits / dvalues rows are zeroed as cadre_ppo_sil_loss does.
+ * The PPO sums, losses[3], the PPO diagnostics, the KL gate and the adaptive lr see the kind-0 rows only, without the smoothness term.
+ *   smooth_losses[1]  sum over heads of (smooth_coeff scale_head inv_bp) sum d^2
+ *                     total = losses[0] + losses[1] - losses[2] + smooth_losses[0]
+ *   smooth_d [2][B]   each row's d_own, 0 for an unpaired row; the two partners' entries are exact negatives of each other
+ * smooth_coeff is the by-value argument, or (float)hp[CADRE_HP_SMOOTH_COEFF] when hp is not NULL; scale_steer / scale_throttle
+ * are by value always.
+ * smooth_stats_row (may be NULL) float [2][smooth_F], smooth_F >= CADRE_SMOOTH_STATS_FIELDS, per head:
+ *   0 valid pairs   1 inv_bp sum |d|   2 max |d|   3 inv_bp sum d^2
+ * smooth_scratch (always required): 2 * ceil(B / 16) * CADRE_SMOOTH_STATS_FIELDS floats; it needs no initialisation.
+ * Refused before any launch: the argument checks of cadre_ppo_sil_loss, NULL row_kind, mate, ctrl, smooth_losses, smooth_d or
+ * smooth_scratch, a by-value smooth_coeff that is not finite, a scale that is not finite and >= 0, an inv_bp that is not finite
+ * and > 0, smooth_F too small, a misaligned hp. */
+#define CADRE_SMOOTH_STATS_FIELDS 4
+int cadre_ppo_smooth_loss(const float* logits, int64_t ldl, int64_t l_ns, const float* values, int64_t ldv, int64_t v_ns,
+                          const int64_t* actions, const int32_t* commands, const float* old_values, const float* returns,
+                          const float* old_logp, const float* adv, const int32_t* row_kind, const int32_t* mate, const float* ctrl,
+                          int32_t B, int32_t C, int32_t n_out_steer, int32_t n_out_throttle, double* hp, float clip,
+                          float value_coeff, float clip_coeff, float ent_coeff, float inv_b, float smooth_coeff, float scale_steer,
+                          float scale_throttle, float inv_bp, float* losses, float* smooth_losses, float* smooth_d, float* dlogits,
+                          float* dvalues, float* scratch, float* smooth_scratch, const int32_t* poison, float* stats_row, int32_t F,
+                          float* stats_scratch, float target_kl, int32_t* stop, float* smooth_stats_row, int32_t smooth_F,
+                          const int32_t* ord, void* stream);
+/* cadre_action_jitter: what the rollouts did.  One launch for n storages (storage k belongs to head k & 1), one wave each:
+ * src_table = n records of four device pointers (int64) {action int64 [T + 1], masks f32 [T + 1], time_limits f32 [T + 1] or 0,
+ * command int32 [T + 1]}.  out float64 [n][3]: the valid pairs t = 0 .. T - 2 (the rule above; an action outside 0 .. K - 1 makes
+ * the pair invalid), sum |c[a_{t+1}] - c[a_t]| and its max.  The terms are fp32 differences widened to double; lane l adds the
+ * terms of t = l, l + 64, ... in ascending order and the lanes are combined by the xor tree (32, 16, .. 1): a fixed order.
+ * Refused before any launch: a NULL table, ctrl or out, n outside 1 .. 65535, T < 2, C < 1, bins outside 1 .. 64, a misaligned out. */
+int cadre_action_jitter(const void* src_table, int32_t n, int32_t T, int32_t C, int32_t n_out_steer, int32_t n_out_throttle,
+                        const float* ctrl, double* out, void* stream);
 
 /* ---------------------------------------------------------------- ensemble evaluation (csrc/ensemble.hip)
  * eval.py:53-63 for N environments and M snapshots.  A group of Mg agents (Mg * C <= 16) shares one stacked arena with
