@@ -222,6 +222,14 @@ SYMBOLS = {
     "cadre_ppo_smooth_loss": [vp, i64, i64, vp, i64, i64, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, vp, f32, f32, f32,
                               f32, f32, f32, f32, f32, f32, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, vp, f32, vp, vp, i32, vp, vp],
     "cadre_action_jitter": [vp, i32, i32, i32, i32, i32, vp, vp, vp],
+    # curiosity (random network distillation): obs table, N, T, S, ldo, D, update, state, stream / obs table, N, T, S, ldo, D, H, E,
+    # row0, rows, state, eps_obs, clip, target, predictor, err, xh, h1, h2, diff (the last four may be NULL), stream / err, N, T,
+    # {rewards, mixed} table, state, D, gamma, eps, update, stream / xh, h1, h2, diff, err, rows, D, H, E, predictor, state, thresh,
+    # grads, loss[2], scratch, stream
+    "cadre_rnd_obs_stats": [vp, i32, i32, i32, i64, i32, i32, vp, vp],
+    "cadre_rnd_forward": [vp, i32, i32, i32, i64, i32, i32, i32, i32, i32, vp, f64, f32, vp, vp, vp, vp, vp, vp, vp, vp],
+    "cadre_rnd_reward": [vp, i32, i32, vp, vp, i32, f64, f64, i32, vp],
+    "cadre_rnd_backward": [vp, vp, vp, vp, vp, i32, i32, i32, i32, vp, vp, i32, vp, vp, vp, vp],
 }
 # entry points of the A/B build only (include/cadre_hip_ab.h; CADRE_BUILD_AB=1 python -m cadre_amd.build, then
 # CADRE_HIP_LIB=.../libcadre_hip_ab.so): bound when the loaded library has them
@@ -297,6 +305,8 @@ SIL_STATS_FIELDS = 6  # CADRE_SIL_STATS_FIELDS: mean w, share w > 0, mean -lp, m
 SMOOTH_STATS_FIELDS = 4  # CADRE_SMOOTH_STATS_FIELDS: valid pairs, inv_bp sum |d|, max |d|, inv_bp sum d^2 (per head)
 VTRACE_DIAG_FIELDS = 4  # CADRE_VTRACE_DIAG_FIELDS: mean ratio, share truncated, max |log ratio|, effective-sample share
 
+# CADRE_RND_*: the curiosity state block (float64; mu [D], M2 [D], carry [N] from RND_HEAD on)
+RND_N, RND_BETA, RND_EXT, RND_RHO_N, RND_RHO_MEAN, RND_RHO_M2, RND_SIGMA, RND_KEY, RND_CTR, RND_HEAD = 0, 1, 2, 3, 4, 5, 6, 7, 8, 16
 RS_SCALE, RS_CARRY = 6, 8 # CADRE_RS_SCALE / CADRE_RS_CARRY: the return-statistics block (count, mean, M2 per head first)
 
 CAPTURE_MAX_RANGES = 65535        # CADRE_CAPTURE_MAX_RANGES

@@ -234,7 +234,8 @@ class RolloutStorage(object):
         return self.advantages
 
     @staticmethod
-    def finish_rollouts(storages, next_values, normalise=True, reward_scaler=None, explained_variance=None, consensus=None):
+    def finish_rollouts(storages, next_values, normalise=True, reward_scaler=None, explained_variance=None, consensus=None,
+                        intrinsic=None):
         """compute_returns of every storage of a learner section in ONE launch (cadre_gae_multi): storages = the flat list
         [steer_0, throttle_0, steer_1, ...] (storage k belongs to head k & 1), next_values = one bootstrap value each.
         Returns the list of `advantages` tensors.  Without time-limit flags and without a scaler, returns, advantages and
@@ -251,9 +252,14 @@ class RolloutStorage(object):
         [world][6] float64 buffer, the buffer is summed over the ranks (consensus.all_reduce_small: a gather, x + 0 is
         exact) and cadre_return_scale_merge forms the scale of each head from the ranks' statistics merged in rank order —
         the same two scales on every rank.  The rank's own statistics and carries stay its own.  Every rank must pass it
-        at the same rollouts (the collective is issued whenever the scaler is training); a no-op without an exchange."""
+        at the same rollouts (the collective is issued whenever the scaler is training); a no-op without an exchange.
+        `intrinsic` (a cadre_amd.curiosity.Curiosity whose begin_section ran on these storages; excludes `reward_scaler`): the
+        first pointer of every row of the table is the storage's `rewards_mixed` in place of `rewards`; the launch and every
+        other pointer are today's.  `storage.rewards` keeps the raw rewards."""
         import numpy as np
         n = len(storages)
+        if intrinsic is not None and reward_scaler is not None:
+            raise ValueError("finish_rollouts: intrinsic excludes reward_scaler (its statistics would be taken from the mixed rewards)")
         if n < 1 or len(next_values) != n:
             raise ValueError("finish_rollouts: %d storages, %d next values" % (n, len(next_values)))
         s0 = storages[0]
@@ -273,7 +279,8 @@ class RolloutStorage(object):
         for s, v in zip(storages, next_values):
             s._next.copy_(torch.as_tensor(v, dtype=torch.float32).reshape(-1)[:1])
         flags = any(s._tl_used for s in storages)
-        rows = [[hip.ptr(s.rewards), hip.ptr(s.value_preds), hip.ptr(s.masks), hip.ptr(s._next), hip.ptr(s.returns),
+        rows = [[hip.ptr(s.rewards if intrinsic is None else intrinsic.mixed_of(s)), hip.ptr(s.value_preds), hip.ptr(s.masks),
+                 hip.ptr(s._next), hip.ptr(s.returns),
                  hip.ptr(s.advantages), hip.ptr(s.time_limits) if flags else 0] for s in storages]
         key = tuple(p for row in rows for p in row)
         tables = RolloutStorage._finish_tables

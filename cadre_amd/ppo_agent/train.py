@@ -433,6 +433,54 @@ def apply_smooth(agent, smooth, episode, max_episode):
     return v
 
 
+def curiosity(agent, train_cfg, n_envs=1, shared_grad_buffers=None, fused_gather=True, ck_interval=None, ck_resume=None):
+    """train_cfg["curiosity"] (absent / None: None — nothing runs, nothing is allocated): the Curiosity of a run with the random
+    network distillation bonus (cadre_amd.curiosity.curiosity_config for the keys, curiosity_refusals for what is refused at
+    start-up and why)."""
+    cfg = _get(train_cfg, "curiosity")
+    if cfg is None:
+        return None
+    from ..curiosity import curiosity_runner
+    return curiosity_runner(agent, cfg, n_envs, reward_scaling=_get(train_cfg, "reward_scaling"),
+                            self_imitation=_get(train_cfg, "self_imitation"), sample_reuse=_get(train_cfg, "sample_reuse"),
+                            checkpoint_interval=ck_interval, resume_from=ck_resume,
+                            world=shared_grad_buffers.dist_world() if shared_grad_buffers is not None else 1,
+                            fused_gather=fused_gather)
+
+
+def apply_curiosity(cur, episode, max_episode):
+    """The bonus coefficient of `episode` (Curiosity.coeff through schedule_value) into the module's own device state block —
+    the learner's 16-field block is full.  No launch depends on the value.  Returns the coefficient set (None without the
+    module)."""
+    if cur is None:
+        return None
+    return cur.set_coeff(schedule_value(cur.coeff, episode, max_episode))
+
+
+def _check_curiosity(cur, reward_scaler, reuse, sil, shared_grad_buffers, fused_gather=True):
+    if cur is None:
+        return
+    if reward_scaler is not None:
+        raise ValueError("curiosity excludes reward_scaler (reward_scaling: its statistics would be taken from the mixed rewards)")
+    if reuse is not None or sil is not None:
+        raise ValueError("curiosity excludes reuse and sil (sample_reuse, self_imitation: they read storage.rewards)")
+    if shared_grad_buffers is not None and shared_grad_buffers.dist_world() > 1:
+        raise ValueError("curiosity needs a single rank: each rank would train its own predictor")
+    if not fused_gather:
+        raise ValueError("curiosity needs fused_gather=True")
+
+
+def _curiosity_end(stats, cur):
+    """Behind the PPO steps of a section: the predictor steps (with one more forward for the stats entry when one is wanted)."""
+    if cur is not None:
+        cur.update(stats=stats is not None)
+
+
+def _curiosity_stats(stats, cur):
+    if stats is not None and cur is not None:
+        stats["curiosity"] = cur.summary()
+
+
 def _rewind(smooth, rollouts):
     """With the smoothness term every rollout starts at row 0 of its storages, so that rows 0 .. T - 1 are one rollout in
     time order (without it the cursors keep the reference's modulo-(T + 1) drift)."""
@@ -684,6 +732,9 @@ def stats_line(episode, stats):
     if "smooth" in stats:                              # temporal smoothness: the pairs' |d| and the realised jitter
         from ..smooth import smooth_stats_text
         line += smooth_stats_text(stats)
+    if "curiosity" in stats:                           # curiosity: the predictor's error, its scale and the bonus paid
+        from ..curiosity import curiosity_stats_text
+        line += curiosity_stats_text(stats)
     return line
 
 
@@ -701,7 +752,7 @@ def _check_sil(sil, demo, suggest, reuse, path_ok=True):
 def learner_section(agent, steer_rollout, throttle_rollout, done, train_cfg, shared_grad_buffers,
                     optimizer=None, traffic_light=None, counter=None, shared_model_list=None, in_process_chief=True,
                     fused_gather=True, losses_on_device=False, step_events=None, stats=None, reward_scaler=None,
-                    demo=None, episode=0, reuse=None, suggest=None, sil=None, smooth=None):
+                    demo=None, episode=0, reuse=None, suggest=None, sil=None, smooth=None, curiosity=None):
     """train.py:76-110.  Returns (value_loss_list, policy_loss_list, ent_loss_list).
     With `in_process_chief` (one process per GPU) the optimiser step runs right after the gradient
     all-reduce instead of waiting on a separate chief process.  `fused_gather` uses the storage ->
@@ -740,8 +791,12 @@ def learner_section(agent, steer_rollout, throttle_rollout, done, train_cfg, sha
     `sil` (a cadre_amd.selfimit.SelfImitationBuffer for one environment; needs fused_gather and the in-process chief,
     excludes `demo`, `suggest` and `reuse`) with `episode`: self-imitation, as in learner_section_multi.
     `smooth` (a cadre_amd.smooth.Smoothness; needs fused_gather, excludes `demo`, `suggest`, `sil` and `reuse`): the temporal
-    smoothness term, as in learner_section_multi.  Raises ValueError when a storage's cursor does not stand at T."""
+    smoothness term, as in learner_section_multi.  Raises ValueError when a storage's cursor does not stand at T.
+    `curiosity` (a cadre_amd.curiosity.Curiosity for one environment; needs fused_gather and a single rank, excludes
+    `reward_scaler`, `reuse` and `sil`): the random network distillation bonus, as in learner_section_multi; the two storages
+    are then finished by RolloutStorage.finish_rollouts."""
     _check_smooth(smooth, demo, suggest, reuse, sil, fused_gather)
+    _check_curiosity(curiosity, reward_scaler, reuse, sil, shared_grad_buffers, fused_gather)
     if demo is not None and not fused_gather:
         raise ValueError("demo needs fused_gather=True")
     _check_sil(sil, demo, suggest, reuse, fused_gather and in_process_chief)
@@ -764,10 +819,11 @@ def learner_section(agent, steer_rollout, throttle_rollout, done, train_cfg, sha
         out = _learner_section(agent, steer_rollout, throttle_rollout, done, train_cfg, shared_grad_buffers, optimizer,
                                traffic_light, counter, shared_model_list, in_process_chief, fused_gather, losses_on_device,
                                step_events, use_adv_norm, sec, lr, reward_scaler, cons, demo, episode, reuse, suggest,
-                               stats, sil, smooth)
+                               stats, sil, smooth, curiosity)
     finally:
         if sec is not None:
             agent.learner.set_update_modes()
+    _curiosity_end(stats, curiosity)
     if sec is None:
         return out
     if losses_on_device:
@@ -777,6 +833,7 @@ def learner_section(agent, steer_rollout, throttle_rollout, done, train_cfg, sha
         _suggest_stats(stats, suggest)
         _sil_stats(stats, sil)
         _smooth_stats(stats, smooth)
+        _curiosity_stats(stats, curiosity)
         return out
     dev_losses, (vl, pl, el) = out
     host = sec.finish(stats, tkl is not None, losses=torch.stack(dev_losses) if dev_losses else None)
@@ -785,6 +842,7 @@ def learner_section(agent, steer_rollout, throttle_rollout, done, train_cfg, sha
     _suggest_stats(stats, suggest)
     _sil_stats(stats, sil)
     _smooth_stats(stats, smooth)
+    _curiosity_stats(stats, curiosity)
     if host is not None:
         for v, p, e in host.tolist():
             vl.append(v); pl.append(p); el.append(e)
@@ -794,16 +852,19 @@ def learner_section(agent, steer_rollout, throttle_rollout, done, train_cfg, sha
 def _learner_section(agent, steer_rollout, throttle_rollout, done, train_cfg, shared_grad_buffers, optimizer, traffic_light,
                      counter, shared_model_list, in_process_chief, fused_gather, losses_on_device, step_events, use_adv_norm,
                      sec, lr, reward_scaler=None, cons=False, demo=None, episode=0, reuse=None, suggest=None, stats=None,
-                     sil=None, smooth=None):
+                     sil=None, smooth=None, curiosity=None):
     if smooth is not None:                           # (the cursor check comes before any launch of the section)
         smooth.begin_section([(steer_rollout, throttle_rollout)],
                              train_cfg["ppo_epoch"] * _steps_per_epoch(steer_rollout) if stats is not None else 0)
     nv_s, nv_t = agent.get_value(done, steer_rollout.get_last(as_tensor=True), throttle_rollout.get_last(as_tensor=True))
-    if reward_scaler is not None or steer_rollout._tl_used or throttle_rollout._tl_used:
+    if curiosity is not None:
+        curiosity.begin_section([(steer_rollout, throttle_rollout)])
+    if curiosity is not None or reward_scaler is not None or steer_rollout._tl_used or throttle_rollout._tl_used:
         steer_adv, throttle_adv = RolloutStorage.finish_rollouts(
             [steer_rollout, throttle_rollout], [nv_s.detach(), nv_t.detach()], normalise=use_adv_norm,
             reward_scaler=reward_scaler, explained_variance=None if sec is None else sec.ev,
-            **_scaler_consensus(cons, reward_scaler, shared_grad_buffers))
+            **_scaler_consensus(cons, reward_scaler, shared_grad_buffers),
+            **({} if curiosity is None else dict(intrinsic=curiosity)))
     else:
         steer_adv = steer_rollout.compute_returns(nv_s.detach(), normalise=use_adv_norm,
                                                   explained_variance=None if sec is None else sec.ev[0:1])
@@ -914,6 +975,8 @@ def train(rank, train_cfg, agent_cfg, env_cfg, rollout_cfg, traffic_light=None, 
     rs = _reward_scaling(train_cfg, shared_grad_buffers)
     agent.reward_scaler = None if rs is None else ReturnScaler(1, rollout_cfg.gamma, device=device, **rs)
     ck_interval, ck_resume = _checkpointing(train_cfg, shared_grad_buffers)
+    # (refusals first: before a checkpoint is read or anything else is built)
+    cur = agent.curiosity = curiosity(agent, train_cfg, 1, shared_grad_buffers, True, ck_interval, ck_resume)
     ck, first_episode = None, 0
     if ck_interval is not None or ck_resume is not None:
         ck = _Checkpointer(env.work_dir, ck_interval, agent, [(steer_rollout, throttle_rollout)])
@@ -959,6 +1022,7 @@ def train(rank, train_cfg, agent_cfg, env_cfg, rollout_cfg, traffic_light=None, 
         apply_suggest(agent, suggest, episode, train_cfg.max_episode)
         apply_sil(agent, sil, episode, train_cfg.max_episode)
         apply_smooth(agent, smooth, episode, train_cfg.max_episode)
+        apply_curiosity(cur, episode, train_cfg.max_episode)
         vl, pl, el = learner_section(agent, steer_rollout, throttle_rollout, done, train_cfg, shared_grad_buffers,
                                      traffic_light=traffic_light, counter=counter,
                                      shared_model_list=shared_model_list,
@@ -967,7 +1031,8 @@ def train(rank, train_cfg, agent_cfg, env_cfg, rollout_cfg, traffic_light=None, 
                                      **({} if reuse is None else dict(reuse=reuse.window_for([(steer_rollout, throttle_rollout)]))),
                                      **({} if suggest is None else dict(suggest=suggest)),
                                      **({} if sil is None else dict(sil=sil.buffer_for([(steer_rollout, throttle_rollout)]))),
-                                     **({} if smooth is None else dict(smooth=smooth)))
+                                     **({} if smooth is None else dict(smooth=smooth)),
+                                     **({} if cur is None else dict(curiosity=cur)))
         log_now = episode % train_cfg.log_interval == 0 and rank == 0 and logger is not None
         # (the auxiliary phase: before the log line, the snapshot and the checkpoint, which then see its result)
         aux_records = _aux_after_section(aux, agent, train_cfg, episode, [(steer_rollout, throttle_rollout)],
@@ -999,7 +1064,7 @@ def train(rank, train_cfg, agent_cfg, env_cfg, rollout_cfg, traffic_light=None, 
 # ----------------------------------------------------------------------------- N environments in one process
 def learner_section_multi(agent, rollouts, dones, train_cfg, shared_grad_buffers, optimizer=None, losses_on_device=False,
                           stats=None, reward_scaler=None, demo=None, episode=0, reuse=None, suggest=None, sil=None,
-                          smooth=None):
+                          smooth=None, curiosity=None):
     """train.py:76-110 for N workers that share one agent (`num_processes = N` on one GPU, chief.py:13-21 semantics):
     rollouts = [(steer_rollout, throttle_rollout), ...] per worker, dones[i] = worker i's last `done`.  Bootstrap values
     of all workers in one pass (get_values), GAE + advantage normalisation per storage, then for each ppo_epoch and
@@ -1044,8 +1109,14 @@ def learner_section_multi(agent, rollouts, dones, train_cfg, shared_grad_buffers
     (update_policy_from_storages(smooth=)); the KL gate, the diagnostics and the adaptive lr see the PPO rows only.  The
     rows of every storage must lie in time order in 0 .. T - 1: ValueError when a storage's cursor does not stand at T when
     the section starts.  `stats` gains "smooth" (pairs, mean_abs_d, max_abs_d, d2 as (steer, throttle) pairs and "jitter",
-    what the section's rollouts did: one cadre_action_jitter launch per section; one more small device-to-host copy)."""
+    what the section's rollouts did: one cadre_action_jitter launch per section; one more small device-to-host copy).
+    `curiosity` (a cadre_amd.curiosity.Curiosity for N environments; single rank, excludes `reward_scaler`, `reuse` and `sil`):
+    the random network distillation bonus.  Before the storages are finished curiosity.begin_section(rollouts) scores the
+    section's rows and writes every storage's `rewards_mixed`, which finish_rollouts(intrinsic=) hands to the GAE launch in
+    place of `rewards`; behind the PPO steps curiosity.update() runs the predictor's steps.  `stats` gains "curiosity" (mean_e,
+    max_e, sigma, beta, mean_abs_bonus, mean_abs_ext, steps, loss_before, loss_after; one more small device-to-host copy)."""
     _check_smooth(smooth, demo, suggest, reuse, sil)
+    _check_curiosity(curiosity, reward_scaler, reuse, sil, shared_grad_buffers)
     if smooth is not None:                           # (the cursor check comes before any launch of the section)
         smooth.begin_section(rollouts, train_cfg["ppo_epoch"] * _steps_per_epoch(rollouts[0][0]) if stats is not None else 0)
     if suggest is not None and demo is not None:
@@ -1062,10 +1133,13 @@ def learner_section_multi(agent, rollouts, dones, train_cfg, shared_grad_buffers
         sec = _SectionStats(agent, train_cfg["ppo_epoch"] * _steps_per_epoch(rollouts[0][0]), 2 * len(rollouts),
                             consensus_world=shared_grad_buffers.dist_world() if cons else 0,
                             demo=demo is not None and stats is not None)
+    if curiosity is not None:
+        curiosity.begin_section(rollouts)
     flat = RolloutStorage.finish_rollouts([x for pair in rollouts for x in pair], [v.detach() for pair in nv for v in pair],
                                           normalise=use_adv_norm, reward_scaler=reward_scaler,
                                           explained_variance=None if sec is None else sec.ev,
-                                          **_scaler_consensus(cons, reward_scaler, shared_grad_buffers))
+                                          **_scaler_consensus(cons, reward_scaler, shared_grad_buffers),
+                                          **({} if curiosity is None else dict(intrinsic=curiosity)))
     advs = [(flat[2 * i], flat[2 * i + 1]) for i in range(len(rollouts))]
     if reuse is not None:
         reuse.refresh(use_adv_norm, reward_scaler)
@@ -1100,6 +1174,7 @@ def learner_section_multi(agent, rollouts, dones, train_cfg, shared_grad_buffers
             agent.learner.set_update_modes()
         if sug_prev is not None:
             agent.learner.loss_mode = sug_prev
+    _curiosity_end(stats, curiosity)
     losses = torch.stack(dev_losses)
     if sec is not None and not losses_on_device:
         host = sec.finish(stats, tkl is not None, losses=losses)
@@ -1108,6 +1183,7 @@ def learner_section_multi(agent, rollouts, dones, train_cfg, shared_grad_buffers
         _suggest_stats(stats, suggest)
         _sil_stats(stats, sil)
         _smooth_stats(stats, smooth)
+        _curiosity_stats(stats, curiosity)
         return tuple(list(c) for c in zip(*host.tolist()))
     if sec is not None:
         sec.finish(stats, tkl is not None)
@@ -1116,6 +1192,7 @@ def learner_section_multi(agent, rollouts, dones, train_cfg, shared_grad_buffers
         _suggest_stats(stats, suggest)
         _sil_stats(stats, sil)
         _smooth_stats(stats, smooth)
+        _curiosity_stats(stats, curiosity)
     if losses_on_device:
         return losses
     vl, pl, el = [], [], []
@@ -1185,6 +1262,8 @@ def train_vec(rank, train_cfg, agent_cfg, env_cfg, rollout_cfg, num_envs, env_cl
     rs = _reward_scaling(train_cfg, shared_grad_buffers)
     agent.reward_scaler = None if rs is None else ReturnScaler(num_envs, rollout_cfg.gamma, device=device, **rs)
     ck_interval, ck_resume = _checkpointing(train_cfg, shared_grad_buffers)
+    # (refusals first: before a checkpoint is read or anything else is built)
+    cur = agent.curiosity = curiosity(agent, train_cfg, num_envs, shared_grad_buffers, True, ck_interval, ck_resume)
     ck, first_episode = None, 0
     if ck_interval is not None or ck_resume is not None:
         ck = _Checkpointer(envs[0].work_dir, ck_interval, agent, rollouts, callback)
@@ -1232,12 +1311,14 @@ def train_vec(rank, train_cfg, agent_cfg, env_cfg, rollout_cfg, num_envs, env_cl
         apply_suggest(agent, suggest, episode, train_cfg.max_episode)
         apply_sil(agent, sil, episode, train_cfg.max_episode)
         apply_smooth(agent, smooth, episode, train_cfg.max_episode)
+        apply_curiosity(cur, episode, train_cfg.max_episode)
         vl, pl, el = learner_section_multi(agent, rollouts, dones, train_cfg, shared_grad_buffers, optimizer=optimizer,
                                            stats=stats, reward_scaler=agent.reward_scaler, demo=demo, episode=episode,
                                            **({} if reuse is None else dict(reuse=reuse.window_for(rollouts))),
                                            **({} if suggest is None else dict(suggest=suggest)),
                                            **({} if sil is None else dict(sil=sil.buffer_for(rollouts))),
-                                           **({} if smooth is None else dict(smooth=smooth)))
+                                           **({} if smooth is None else dict(smooth=smooth)),
+                                           **({} if cur is None else dict(curiosity=cur)))
         log_now = episode % train_cfg.log_interval == 0 and rank == 0 and logger is not None
         # (the auxiliary phase: before the log line, the snapshot and the checkpoint, which then see its result)
         aux_records = _aux_after_section(aux, agent, train_cfg, episode, rollouts, shared_grad_buffers, optimizer,

@@ -1231,6 +1231,53 @@ int cadre_bc_head(const float* lat, int64_t ld, const float* speed, const float*
                   const float* sb2, const float* bw1, const float* bb1, const float* bw2, const float* bb2, float* out, int32_t F,
                   float slope, void* stream);
 
+/* ---- curiosity (csrc/curiosity.hip): random network distillation on the newest frame row of every window row, fp32 towers
+ * on v_mfma_f32_32x32x2_f32.  Rows: r = w * T + t for worker w < N and storage row t < T; x = obs_w[t][S - 1][0 .. D-1], obs_table
+ * = N device pointers to the workers' window rows [T + 1][S][ldo] (the steer storage's: both heads hold the same rows).
+ * State block (float64): [CADRE_RND_N] rows merged into the feature statistics, [CADRE_RND_BETA] the bonus coefficient,
+ * [CADRE_RND_EXT] the factor of the raw reward, [CADRE_RND_RHO_N / _MEAN / _M2] the running statistics of the carried error
+ * sums, [CADRE_RND_SIGMA] sqrt(var + eps) of the last merge (1 before any), [CADRE_RND_KEY / _CTR] key and counter of the mask
+ * generator (whole numbers below 2^32 / 2^53), then from CADRE_RND_HEAD: mu [D], M2 [D], carry [N].
+ * A tower is one flat fp32 buffer: W1 [D][H], b1 [H], W2 [H][H], b2 [H], W3 [H][E], b3 [E] — every matrix input-major (row k
+ * holds the weights that input k feeds), so the gradient buffer of cadre_rnd_backward has the same layout.  H and E are
+ * multiples of 32, at most 256; 1 <= D <= 1024.
+ * cadre_rnd_obs_stats: with `update`, merges the N T rows into {n, mu, M2} (Chan): per feature the batch mean and the batch sum
+ * of squared deviations in two passes, rows summed in 16 interleaved groups, groups in order.  update == 0: no launch.  Columns
+ * D .. ldo-1 and frames s < S - 1 are not read.
+ * cadre_rnd_forward: rows row0 .. row0 + rows - 1.  xh = clamp((x - (float)mu) / (float)sqrt(M2 / n + eps_obs), -clip, clip)
+ * (variance 1 while n == 0), then for the target and the predictor, one code path: h1 = relu(xh W1 + b1), h2 = relu(h1 W2 + b2),
+ * o = h2 W3 + b3; err[i] = (sum_k (g_k - f_k)^2 in k order) / E for i = r - row0.  A row's result does not depend on the other
+ * rows of the launch.  xh [rows][D], h1, h2 [rows][H], diff [rows][E] (g - f): the predictor's, each NULL when not wanted.
+ * cadre_rnd_reward: one workgroup.  With `update`, per worker rho <- gamma rho + err[w][t] forward in time from the carry, the
+ * N T values merged into the rho statistics, sigma = sqrt(M2 / n + eps), carries stored.  Then for storage k < 2 N (worker
+ * k / 2) and t < T: mixed_k[t] = ext * rewards_k[t] + beta * (err[w][t] / (float)sigma).  row_table = 2 N records {rewards,
+ * mixed} of device pointers; row T of `mixed` is not written.
+ * cadre_rnd_backward: rows = the rows of one predictor step with their saved xh, h1, h2, diff and err.  m_i = 1 where the top 24
+ * bits of splitmix64(key * 0x9E3779B97F4A7C15 + ctr + i) are below `thresh` (update_proportion * 2^24), cnt = sum m; the
+ * counter then advances by `rows`.  loss[0] = sum m err / max(cnt, 1), loss[1] = cnt.  dO = 2 m diff / (E max(cnt, 1)); dW3 = h2^T
+ * dO, dH2 = (dO W3^T) [h2 > 0], dW2 = h1^T dH2, dH1 = (dH2 W2^T) [h1 > 0], dW1 = xh^T dH1, db = column sums; every sum over rows runs
+ * in row order inside one wave.  scratch: rows (E + 2 H + 1) + 2 floats.  Six launches, no atomics. */
+#define CADRE_RND_N 0
+#define CADRE_RND_BETA 1
+#define CADRE_RND_EXT 2
+#define CADRE_RND_RHO_N 3
+#define CADRE_RND_RHO_MEAN 4
+#define CADRE_RND_RHO_M2 5
+#define CADRE_RND_SIGMA 6
+#define CADRE_RND_KEY 7
+#define CADRE_RND_CTR 8
+#define CADRE_RND_HEAD 16
+int cadre_rnd_obs_stats(const void* obs_table, int32_t N, int32_t T, int32_t S, int64_t ldo, int32_t D, int32_t update,
+                        double* state, void* stream);
+int cadre_rnd_forward(const void* obs_table, int32_t N, int32_t T, int32_t S, int64_t ldo, int32_t D, int32_t H, int32_t E,
+                      int32_t row0, int32_t rows, const double* state, double eps_obs, float clip, const float* target,
+                      const float* predictor, float* err, float* xh, float* h1, float* h2, float* diff, void* stream);
+int cadre_rnd_reward(const float* err, int32_t N, int32_t T, const void* row_table, double* state, int32_t D, double gamma,
+                     double eps, int32_t update, void* stream);
+int cadre_rnd_backward(const float* xh, const float* h1, const float* h2, const float* diff, const float* err, int32_t rows,
+                       int32_t D, int32_t H, int32_t E, const float* predictor, double* state, int32_t thresh, float* grads,
+                       float* loss, float* scratch, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
