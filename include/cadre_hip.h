@@ -65,7 +65,10 @@ typedef struct {
   /* Row segments (cadre_gemm_f32 only; PPO update with the minibatch rows sorted by command,
      agent.py:170-182 evaluates every command net on every row and masks 3 of 4): batch entry z
      owns rows [row_seg[2*(z/seg_div)], +row_seg[2*(z/seg_div)+1]) of every period of
-     `seg_period` rows (seg_period % 32 == 0; the M tile must divide it: 32- or 64-row tiles).
+     `seg_period` rows.  seg_modes 1 and 2 skip in tiles and need seg_period % 32 == 0 (mode 1: the
+     M tile must divide the period — 32- or 64-row tiles, chosen by the library where the requested
+     tile does not); seg_mode 3 takes ANY seg_period >= 1 (the act path's period is the number of
+     environments) and needs only M % seg_period == 0.
      seg_mode 1: M-tiles that own no row of their period return without writing; seg_mode 2: k-tiles (k = row index, K % seg_period == 0) outside the segment are
      not multiplied.  Rows of other nets inside a computed tile are still multiplied — callers
      keep their gradients exactly zero (cadre_relu_bwd / cadre_lstm_pointwise_bwd masks).
