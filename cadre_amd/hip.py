@@ -230,6 +230,16 @@ SYMBOLS = {
     "cadre_rnd_forward": [vp, i32, i32, i32, i64, i32, i32, i32, i32, i32, vp, f64, f32, vp, vp, vp, vp, vp, vp, vp, vp],
     "cadre_rnd_reward": [vp, i32, i32, vp, vp, i32, f64, f64, i32, vp],
     "cadre_rnd_backward": [vp, vp, vp, vp, vp, i32, i32, i32, i32, vp, vp, i32, vp, vp, vp, vp],
+    # action masks: the `_ord` twins with the words `allowed` before the stream / allowed pointer table, slots, words, n, T,
+    # stream / allowed pointer table, n_src, idx, Bw, T, pos (NULL: identity), B, out, stream / the arguments of
+    # cadre_ppo_loss_ord, then allowed, mask stats row (may be NULL), its F, mask scratch, stream
+    "cadre_sample_am": [vp, i64, vp, i64, i32, i32, vp, vp, vp, vp, vp],
+    "cadre_sample_rows_am": [vp, i64, i64, vp, vp, i32, i32, vp, i32, i32, vp, vp, vp, vp, vp, vp],
+    "cadre_categorical_eval_am": [vp, i64, vp, i32, i32, vp, vp, vp, vp, vp],
+    "cadre_allowed_note": [vp, vp, vp, i32, i32, vp],
+    "cadre_allowed_rows": [vp, i32, vp, i32, i32, vp, i32, vp, vp],
+    "cadre_ppo_am_loss": [vp, i64, i64, vp, i64, i64, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, vp, f32, f32, f32, f32, f32,
+                          vp, vp, vp, vp, vp, vp, i32, vp, f32, vp, vp, vp, vp, i32, vp, vp],
 }
 # entry points of the A/B build only (include/cadre_hip_ab.h; CADRE_BUILD_AB=1 python -m cadre_amd.build, then
 # CADRE_HIP_LIB=.../libcadre_hip_ab.so): bound when the loaded library has them
@@ -303,6 +313,7 @@ AUX_STATS_FIELDS = 6  # CADRE_AUX_STATS_FIELDS: mean KL, max KL, mean |v - R|, m
 SUG_STATS_FIELDS = 4  # CADRE_SUG_STATS_FIELDS: marked rows, mean KL over the minibatch, max KL, mean p[prior's mode] over marked rows
 SIL_STATS_FIELDS = 6  # CADRE_SIL_STATS_FIELDS: mean w, share w > 0, mean -lp, mean |R - v|, max w, rows counted (over the SIL rows)
 SMOOTH_STATS_FIELDS = 4  # CADRE_SMOOTH_STATS_FIELDS: valid pairs, inv_bp sum |d|, max |d|, inv_bp sum d^2 (per head)
+AM_STATS_FIELDS = 4   # CADRE_AM_STATS_FIELDS: share of properly masked rows, mean allowed bins, mean pressure, action bits OR-ed in
 VTRACE_DIAG_FIELDS = 4  # CADRE_VTRACE_DIAG_FIELDS: mean ratio, share truncated, max |log ratio|, effective-sample share
 
 # CADRE_RND_*: the curiosity state block (float64; mu [D], M2 [D], carry [N] from RND_HEAD on)

@@ -127,6 +127,8 @@ class PPOLearnerHIP:
         self._smooth_coeff = 0.0
         self._smooth_rows = None   # B_ppo: the leading unsorted rows of the minibatch that are PPO rows (set_smooth_rows)
         self._smooth_tables = None  # (ctrl: device float32 [2][64], (scale_steer, scale_throttle)); the address is part of the graph keys
+        # "ppo+mask": cadre_ppo_am_loss — the PPO loss under the rows' allowed-bin words (workspace(B)["allowed"])
+        self._last_am_stats = None  # workspace(B)["am_stats"] of the "ppo+mask" update that ran last
         hip.lib()
 
     # ------------------------------------------------------------------ loss selection
@@ -173,9 +175,17 @@ class PPOLearnerHIP:
         adaptive lr and rank consensus work as in "ppo" and see the PPO rows only, without the term.  In device-hyper mode
         the coefficient lives in the block (set_hyper(smooth_coeff=)): a changed value needs no new graph.  None keeps the
         current coefficient.  The pairs of a step are in workspace(B)["row_kind"] / ["mate"] (cadre_smooth_mates writes them
-        before the step), its smoothness loss / statistics / per-row d in ["smooth_losses"] / ["smooth_stats"] / ["smooth_d"]."""
-        if mode not in ("ppo", "bc", "ppo+demo", "aux", "ppo+suggest", "ppo+sil", "ppo+smooth"):
-            raise ValueError("set_loss: mode %r (known: 'ppo', 'bc', 'ppo+demo', 'aux', 'ppo+suggest', 'ppo+sil', 'ppo+smooth')" % (mode,))
+        before the step), its smoothness loss / statistics / per-row d in ["smooth_losses"] / ["smooth_stats"] / ["smooth_d"].
+        "ppo+mask": the clipped-surrogate loss under action masks (cadre_ppo_am_loss, ONE launch where the PPO loss stands): a
+        row's word in workspace(B)["allowed"] (int64 [2][B] in workspace order, a static tensor that cadre_allowed_rows fills
+        before the update; bit k set: bin k may be chosen, no bit among the head's bins: unmasked) restricts the softmax, the
+        entropy and the gradient to the allowed bins; with every word unmasked the step is bit-identical to "ppo".  It has no
+        scalar of its own: diagnostics, the KL gate, the adaptive lr, device hyper-parameters, ordinal heads and rank
+        consensus work as in "ppo".  The mask statistics of a step (hip.AM_STATS_FIELDS per head) are in
+        workspace(B)["am_stats"]."""
+        if mode not in ("ppo", "bc", "ppo+demo", "aux", "ppo+suggest", "ppo+sil", "ppo+smooth", "ppo+mask"):
+            raise ValueError("set_loss: mode %r (known: 'ppo', 'bc', 'ppo+demo', 'aux', 'ppo+suggest', 'ppo+sil', 'ppo+smooth', "
+                             "'ppo+mask')" % (mode,))
         if mode == "ppo+smooth":
             if isinstance(smooth_coeff, bool):
                 raise ValueError("set_loss: smooth_coeff=%r" % (smooth_coeff,))
@@ -448,6 +458,42 @@ class PPOLearnerHIP:
             hip.ptr(self._stop) if (stats and self.target_kl is not None) else None, hip.ptr(w["sug_stats"]),
             hip.SUG_STATS_FIELDS, hip.ptr(ord_t), hip.stream()), "cadre_ppo_sug_loss")
 
+    # ------------------------------------------------------------------ action masks
+    def _am_ws(self, w, B):
+        """The static tensors of the "ppo+mask" loss in workspace(B); `allowed` is zeroed (every row unmasked) once, here."""
+        if "allowed" not in w:
+            dev = self.a.device
+            w["allowed"] = torch.zeros(2, B, dtype=torch.int64, device=dev)
+            w["am_stats"] = torch.zeros(2, hip.AM_STATS_FIELDS, device=dev)
+            w["am_scratch"] = torch.zeros(2 * 5 * ((B + 15) // 16), device=dev)
+        return w["allowed"]
+
+    def marker_ord(self):
+        """The rank table of two categorical heads (int32 [2][64] of -1) for the entry points that want a table when the arena has
+        none: one per learner, shared by the suggestion loss, the masked loss and the agent's masked samplers."""
+        if self._sug_ord is None:
+            self._sug_ord = torch.full((2, 64), -1, dtype=torch.int32, device=self.a.device)
+        return self._sug_ord
+
+    def _am_launch(self, w, B, inv_b):
+        """cadre_ppo_am_loss on the tower outputs in workspace(B), in the place of the PPO loss."""
+        a, S = self.a, self.S
+        O3, dO3, NP = w["O3"], w["dO3"], a.NP
+        self._am_ws(w, B)
+        ord_t = getattr(a, "ord", None)
+        if ord_t is None:
+            ord_t = self.marker_ord()
+        stats = self._loss_stats()
+        srow, sscr = self._stats_ws(w, B) if stats else (None, None)
+        hip.check(hip.lib().cadre_ppo_am_loss(
+            hip.ptr(O3), NP, 2 * B * NP, hip.ptr(O3[1]), NP, 2 * B * NP, hip.ptr(w["actions"]), hip.ptr(w["commands"]),
+            hip.ptr(w["old_values"]), hip.ptr(w["returns"]), hip.ptr(w["old_logp"]), hip.ptr(w["adv"]), B, a.C, a.n_out[0],
+            a.n_out[1], hip.ptr(self._hp) if self._hp_on else None, self.clip, self.vc, self.cc, self.ec, inv_b,
+            hip.ptr(w["losses"]), hip.ptr(dO3), hip.ptr(dO3[1]), hip.ptr(w["loss_scratch"]), hip.ptr(w["sync"][a.Z * S:]),
+            hip.ptr(srow), srow.shape[1] if stats else 0, hip.ptr(sscr), self._loss_tkl(),
+            hip.ptr(self._stop) if (stats and self.target_kl is not None) else None, hip.ptr(ord_t), hip.ptr(w["allowed"]),
+            hip.ptr(w["am_stats"]), hip.AM_STATS_FIELDS, hip.ptr(w["am_scratch"]), hip.stream()), "cadre_ppo_am_loss")
+
     # ------------------------------------------------------------------ PPG auxiliary phase
     def set_aux_table(self, table):
         """The table of recorded distributions the "aux" loss and aux_record work on: device float32 [2][R][64], contiguous
@@ -668,6 +714,9 @@ class PPOLearnerHIP:
             t = self._smooth_tables
             key = key + ((("smooth", self._smooth_rows) + ((None,) if t is None else (t[0].data_ptr(),) + t[1]) +
                           (() if self._hp_on else (self._smooth_coeff,))),)
+        # the masked loss is a mode without values: its graphs hold cadre_ppo_am_loss and the workspace's static tensors
+        if self.loss_mode == "ppo+mask":
+            key = key + (("mask",),)
         return key
 
     # ------------------------------------------------------------------ device-resident hyper-parameters
@@ -1064,6 +1113,8 @@ class PPOLearnerHIP:
         self._last_stats = w.get("stats")
         if self.loss_mode == "ppo+suggest":
             self._last_sug_stats = w.get("sug_stats")
+        if self.loss_mode == "ppo+mask":
+            self._last_am_stats = w.get("am_stats")
         if stats_row is not None:
             stats_row.copy_(w["stats"])
             self._norm_row = stats_row
@@ -1178,6 +1229,8 @@ class PPOLearnerHIP:
             self._smooth_launch(w, B, inv_b)            # PPO rows + their successor rows, coupled in pairs: the rest is indifferent
         elif front and self.loss_mode == "ppo+suggest":
             self._sug_launch(w, B, inv_b)               # PPO + the event priors on marked rows: the rest is indifferent
+        elif front and self.loss_mode == "ppo+mask":
+            self._am_launch(w, B, inv_b)                # PPO under the rows' allowed-bin words: the rest is indifferent
         elif front:
             self._ppo_launch(w, B, inv_b, ord_t)
         # ---------------- backward: MLP towers (16 = 2Z batched)

@@ -184,35 +184,50 @@ class CadreAgent(object):
         return feat[:, :self.lstm_input]
 
     # ------------------------------------------------------------------ act
-    def _sample(self, O3, tower_row, K, q_host):
+    def _sample(self, O3, tower_row, K, q_host, allowed=None):
         q = q_host.to(self.device, non_blocking=True)
         action = torch.empty(1, dtype=torch.int64, device=self.device)
         logp = torch.empty(1, 1, device=self.device)
-        self._sample_launch(O3, tower_row, K, q, action, logp)
+        self._sample_launch(O3, tower_row, K, q, action, logp, allowed)
         return action, logp
 
-    def _sample_launch(self, O3, tower_row, K, q, action, logp):
+    def _am_ord(self):
+        """The rank tables the `_am` samplers want: the arena's, or a marker table of two categorical heads."""
+        ord_t = self.arena.ord
+        return self.learner.marker_ord() if ord_t is None else ord_t
+
+    def _sample_launch(self, O3, tower_row, K, q, action, logp, allowed=None):
         """cadre_sample on actor-tower row `tower_row` of O3 (0 steer, 2 throttle), or cadre_sample_ord with the head's rank
-        table when the agent has ordinal heads."""
+        table when the agent has ordinal heads; with `allowed` (a device int64 tensor of one word) cadre_sample_am."""
         L, ord_t = hip.lib(), self.arena.ord
-        if ord_t is not None:
+        if allowed is not None:
+            hip.check(L.cadre_sample_am(hip.ptr(O3[tower_row]), O3.shape[-1], hip.ptr(q), K, 1, K, hip.ptr(action), hip.ptr(logp),
+                                        hip.ptr(self._am_ord()[tower_row // 2]), hip.ptr(allowed), hip.stream()), "cadre_sample_am")
+        elif ord_t is not None:
             hip.check(L.cadre_sample_ord(hip.ptr(O3[tower_row]), O3.shape[-1], hip.ptr(q), K, 1, K, hip.ptr(action),
                                          hip.ptr(logp), hip.ptr(ord_t[tower_row // 2]), hip.stream()), "cadre_sample_ord")
         else:
             hip.check(L.cadre_sample(hip.ptr(O3[tower_row]), O3.shape[-1], hip.ptr(q), K, 1, K, hip.ptr(action),
                                      hip.ptr(logp), hip.stream()), "cadre_sample")
 
-    def act(self, tick_data, deterministic=False):
+    def act(self, tick_data, deterministic=False, allowed=None):
         """agent.py:114-141.  Sampling consumes the global torch CPU generator exactly like the
         reference (one exponential_(1) draw of n_out floats per head, steer first).  The launch chain of an
         env step (packing, encoder, LSTM x 2, heads, sampling: ~150 kernels) has fixed shapes and pointers, so
         it is captured once per (window mode, command) into a hipGraph and replayed — same kernels, same order,
         same results; inputs and outputs go through static buffers.
         `deterministic=True`: the greedy action (the first largest probability) — the sampler's q is all ones (p / 1.0f is
-        exact), nothing is drawn from the generator."""
+        exact), nothing is drawn from the generator.
+        `allowed` (action masks, cadre_amd.actmask): a (steer_word, throttle_word) pair of Python ints (bit k set: bin k may be
+        chosen; an empty set is refused) or a device int64 [1][2] tensor.  The action is then argmax(p / q) over the allowed
+        bins, the log-probability the masked one; the generator is consumed exactly as without (q is drawn for all bins).
+        None launches exactly what is launched without the feature."""
+        if allowed is not None:
+            from ..actmask import words_tensor
+            allowed = words_tensor([allowed] if not torch.is_tensor(allowed) else allowed, 1, self.arena.n_out, self.device).view(2)
         if self.act_graph and self.latent_cache and self.vae_device == self.device:
-            return self._act_graphed(tick_data, deterministic)
-        return self.act_from_feature(self.get_latent_feature(tick_data), tick_data["command"], deterministic)
+            return self._act_graphed(tick_data, deterministic, allowed)
+        return self.act_from_feature(self.get_latent_feature(tick_data), tick_data["command"], deterministic, allowed)
 
     # ------------------------------------------------------------------ act() as a hipGraph
     def _act_static(self, S, H, W):
@@ -235,8 +250,9 @@ class CadreAgent(object):
                   graphs={}, warm=set(), gen=self.vae_model.ws_generation)
         return st
 
-    def _act_body(self, st, shifted, command):
-        """The device work of one env step on the static buffers (eager or under capture)."""
+    def _act_body(self, st, shifted, command, masked=False):
+        """The device work of one env step on the static buffers (eager or under capture); masked: the samplers read the
+        static words st["d_allowed"]."""
         S = st["shape"][0]
         L, stream = hip.lib(), hip.stream()
         enc, feat, lat = self.vae_model, st["feat"], st["lat"]
@@ -252,10 +268,11 @@ class CadreAgent(object):
         O3, _, _ = self.learner.infer(feat[:, :self.lstm_input], (command, command))
         nS, nT = self.arena.n_out
         for j, (row, K) in enumerate(((0, nS), (2, nT))):
-            self._sample_launch(O3, row, K, st["d_q"][j], st["action"][j:], st["logp"][j:])
+            self._sample_launch(O3, row, K, st["d_q"][j], st["action"][j:], st["logp"][j:],
+                                st["d_allowed"][j:] if masked else None)
         return O3
 
-    def _act_graphed(self, tick_data, deterministic=False):
+    def _act_graphed(self, tick_data, deterministic=False, allowed=None):
         rgb, route_np, command = tick_data["rgb"], tick_data["route_fig"], int(tick_data["command"])
         S, H, W = rgb.shape[0], rgb.shape[1], rgb.shape[2]
         st = self._ag
@@ -294,17 +311,22 @@ class CadreAgent(object):
         ev.record()
         lrn = self.learner
         lrn.packed_weights(0, 1, self.arena.Z)                    # refreshed here when the parameters changed, not in the graph
-        key = (shifted, command)
+        masked = allowed is not None
+        key = (shifted, command) + (("mask",) if masked else ())  # (a masked step is a graph of its own: another sampler)
+        if masked:
+            if "d_allowed" not in st:                             # static, as every pointer of a captured step
+                st["d_allowed"] = torch.zeros(2, dtype=torch.int64, device=self.device)
+            st["d_allowed"].copy_(allowed)
         g = st["graphs"].get(key)
         if g is not None:
             g.replay()
         else:
-            self._act_body(st, shifted, command)                  # eager (also the warm-up of every lazily built buffer)
+            self._act_body(st, shifted, command, masked)          # eager (also the warm-up of every lazily built buffer)
             if key in st["warm"] and lrn.use_graphs:
                 torch.cuda.synchronize()
                 lrn.pack_outside_capture = True
                 try:
-                    st["graphs"][key] = lrn._capture(lambda: self._act_body(st, shifted, command))
+                    st["graphs"][key] = lrn._capture(lambda: self._act_body(st, shifted, command, masked))
                 finally:
                     lrn.pack_outside_capture = False
             st["warm"].add(key)
@@ -328,8 +350,9 @@ class CadreAgent(object):
         # the reference discards the new hidden state and returns the zeros (agent.py:123-124,141)
         return feat, [a_s, a_t], [lp_s, lp_t], [v_s, v_t], self.hidden_state
 
-    def act_from_feature(self, ppo_feature, command, deterministic=False):
-        """The part of `act` after the encoder (agent.py:116-141) on a given [S,530] feature window."""
+    def act_from_feature(self, ppo_feature, command, deterministic=False, allowed=None):
+        """The part of `act` after the encoder (agent.py:116-141) on a given [S,530] feature window.  `allowed`: None, or a
+        device int64 [2] tensor of the (steer, throttle) words (act() builds it)."""
         O3, _, _ = self.learner.infer(ppo_feature, (command, command))
         nS, nT = self.arena.n_out
         if deterministic:
@@ -337,8 +360,8 @@ class CadreAgent(object):
         else:
             q_s = torch.empty(1, nS).exponential_(1)
             q_t = torch.empty(1, nT).exponential_(1)
-        a_s, lp_s = self._sample(O3, 0, nS, q_s)
-        a_t, lp_t = self._sample(O3, 2, nT, q_t)
+        a_s, lp_s = self._sample(O3, 0, nS, q_s, None if allowed is None else allowed[0:])
+        a_t, lp_t = self._sample(O3, 2, nT, q_t, None if allowed is None else allowed[1:])
         v_s = O3[1, :, :1].clone()
         v_t = O3[3, :, :1].clone()
         ctl_s = self.model_dict["steer_ppo_%d" % command].control
@@ -349,7 +372,7 @@ class CadreAgent(object):
         return ppo_feature, [a_s[0], a_t[0]], [lp_s, lp_t], [v_s, v_t], self.hidden_state
 
     # ------------------------------------------------------------------ act for N environments
-    def act_batch(self, obs_list, shifted=None, deterministic=False):
+    def act_batch(self, obs_list, shifted=None, deterministic=False, allowed=None):
         """`[self.act(o) for o in obs_list]` for N environments in ONE launch chain: one encoder pass over every fresh
         frame (the newest frame of each window that shifted, all S frames of the others), cadre_act_windows (the LSTM
         input rows of all windows, rows sorted by command), one LSTM + MLP pass over all 2C command nets
@@ -359,9 +382,15 @@ class CadreAgent(object):
         loop's: one exponential_(1) draw per environment and head, env 0 steer, env 0 throttle, env 1 steer, ...
         The route quirk (agent.py:51-54: the caller's route_fig normalised in place) is kept per environment.
         `deterministic=True`: the greedy action of every (environment, head) — q stays all ones, nothing is drawn.
+        `allowed` (action masks): per environment a (steer_word, throttle_word) pair of Python ints, or a device int64 [N][2]
+        tensor; the sampling launch is then cadre_sample_rows_am and the result carries the words as `.allowed` (what
+        RolloutStorage.insert_batch(allowed=) takes).  None launches exactly what is launched without the feature.
         Returns an ActBatch: N tuples in exactly act()'s format."""
         check_act_batch(obs_list, shifted, self.max_envs, self.device, self.vae_device, self.command_num)
         N = len(obs_list)
+        if allowed is not None:                             # (checked before anything is drawn or launched)
+            from ..actmask import words_tensor
+            allowed = words_tensor(allowed, N, self.arena.n_out, self.device)
         a, enc, dev = self.arena, self.vae_model, self.device
         S, H, W = obs_list[0]["rgb"].shape[:3]
         L, stream = hip.lib(), hip.stream()
@@ -425,7 +454,11 @@ class CadreAgent(object):
         action = torch.empty(N, 2, dtype=torch.int64, device=dev)
         logp = torch.empty(N, 2, device=dev)
         value = torch.empty(N, 2, device=dev)
-        if a.ord is not None:
+        if allowed is not None:
+            hip.check(L.cadre_sample_rows_am(hip.ptr(O3), O3.stride(1), O3.stride(0), hip.ptr(pos_d), hip.ptr(cmd_d), N, a.C,
+                                             hip.ptr(q_d), nS, nT, hip.ptr(action), hip.ptr(logp), hip.ptr(value),
+                                             hip.ptr(self._am_ord()), hip.ptr(allowed), stream), "cadre_sample_rows_am")
+        elif a.ord is not None:
             hip.check(L.cadre_sample_rows_ord(hip.ptr(O3), O3.stride(1), O3.stride(0), hip.ptr(pos_d), hip.ptr(cmd_d), N, a.C,
                                               hip.ptr(q_d), nS, nT, hip.ptr(action), hip.ptr(logp), hip.ptr(value),
                                               hip.ptr(a.ord), stream), "cadre_sample_rows_ord")
@@ -456,6 +489,8 @@ class CadreAgent(object):
             ctl_s._last_action, ctl_s._last_logp = action[e, 0:1], lp_s
             ctl_t._last_action, ctl_t._last_logp = action[e, 1:2], lp_t
         out.feat, out.action, out.logp, out.value = feat, action, logp, value
+        if allowed is not None:
+            out.allowed = allowed
         return out
 
     @staticmethod
@@ -545,7 +580,7 @@ class CadreAgent(object):
     def update_policy_from_storages(self, batches, sync=True, mlp_grads_ready=None, stats_row=None, evaluate=False,
                                     demo=None, demo_stats_row=None, demo_label_smoothing=None, demo_coeff=None,
                                     demo_value_coeff=None, sil=None, sil_stats_row=None, smooth=None,
-                                    smooth_stats_row=None):
+                                    smooth_stats_row=None, actmask=None):
         """Fast path of the learner section: `batches` = [(steer_storage, steer_idx, steer_adv,
         throttle_storage, throttle_idx, throttle_adv), ...] one entry per worker (equal sizes).
         Same math as feed_forward_generator -> update_policy, but the minibatch gather writes
@@ -578,7 +613,29 @@ class CadreAgent(object):
         tables: total = the PPO loss + smooth_coeff * head_scale * mean over the pair slots of d^2.  The three floats returned
         are the PPO terms; the smoothness term and the rows' d stay on the device in learner.workspace(B)["smooth_losses"] /
         ["smooth_d"], the statistics go to `smooth_stats_row` (device float32 [2][>= hip.SMOOTH_STATS_FIELDS]).  Excludes
-        `demo` and `sil`."""
+        `demo` and `sil`.
+        `actmask` (action masks: a cadre_amd.actmask.ActionMasks, or True): the step runs the masked loss
+        (PPOLearnerHIP.set_loss("ppo+mask"), for the duration of the call).  One cadre_allowed_rows launch behind the gather /
+        sort carries the `allowed` words of the step's storages (a storage without the tensor: unmasked rows) into
+        learner.workspace(B)["allowed"]; the mask statistics of the step stay on the device in workspace(B)["am_stats"] (an
+        ActionMasks collects them).  Excludes `demo`, `sil`, `smooth` and `evaluate`: their kernels do not read the mask."""
+        if actmask is not None and actmask is not False:
+            if evaluate or demo or sil or smooth is not None:
+                raise ValueError("update_policy_from_storages: actmask excludes demo, sil, smooth and evaluate (their kernels do "
+                                 "not read the rows' allowed-bin words yet)")
+            lrn = self.learner
+            prev = lrn.loss_mode
+            if prev not in ("ppo", "ppo+mask"):
+                raise ValueError("update_policy_from_storages: actmask with the learner's loss set to %r (its kernel does not "
+                                 "read the rows' allowed-bin words yet)" % (prev,))
+            lrn.set_loss("ppo+mask")
+            try:
+                out = self._update_from_storages(batches, sync, mlp_grads_ready, stats_row, False)
+                if hasattr(actmask, "step"):
+                    actmask.step(lrn)
+                return out
+            finally:
+                lrn.loss_mode = prev
         if smooth is not None:
             if evaluate or demo or sil:
                 raise ValueError("update_policy_from_storages: successor rows have no evaluation form and exclude demo and sil "
@@ -649,6 +706,11 @@ class CadreAgent(object):
 
     def _update_from_storages(self, batches, sync, mlp_grads_ready, stats_row, evaluate, demo_stats_row=None, record=None):
         nW = len(batches)
+        if (record is None and not evaluate and self.learner.loss_mode in ("ppo", "ppo+demo", "ppo+suggest", "ppo+sil", "ppo+smooth")
+                and any(getattr(b[k], "allowed", None) is not None for b in batches for k in (0, 3))):
+            raise ValueError("update_policy_from_storages: a storage of this step carries `allowed` words (its actions were sampled "
+                             "under action masks) but the loss is %r, which does not read them: old_logp would belong to another "
+                             "distribution than the ratio's; pass actmask= (learner_section(..., actmask=))" % (self.learner.loss_mode,))
         Bw = batches[0][1].numel()
         B = nW * Bw
         w = self.learner.workspace(B)
@@ -682,7 +744,7 @@ class CadreAgent(object):
         if any((st_._ldo, st_.seq_length, st_._ldh) != geo for b in batches for st_ in (b[0], b[3])):
             # storages of different geometry (feature pitch / window length): one gather launch per storage with its
             # own strides (cadre_gather_minibatch) — the one-launch table below assumes a single geometry
-            if self.learner.loss_mode in ("ppo+suggest", "ppo+smooth"):
+            if self.learner.loss_mode in ("ppo+suggest", "ppo+smooth", "ppo+mask"):
                 raise ValueError("the %r loss needs storages of one geometry: the kinds of the minibatch are placed "
                                  "by one launch beside the one-launch gather" % (self.learner.loss_mode,))
             self._gather_entry = "cadre_gather_minibatch_ft" if ft else "cadre_gather_minibatch"
@@ -753,6 +815,14 @@ class CadreAgent(object):
             if stable is None:
                 stable = cache[("suggest",) + sptrs] = torch.tensor(sptrs, dtype=torch.int64).to(self.device)
             self._suggest_src = (stable, stage[1], Bw, s0.num_steps)
+        if self.learner.loss_mode == "ppo+mask" and record is None and not evaluate:
+            # the `allowed` tensors of the step's storages, source by source (0: a storage that never saw a word: unmasked
+            # rows); the launch itself follows the gather / sort, which writes `pos`
+            sptrs = tuple(hip.ptr(getattr(stor, "allowed", None)) or 0 for stor, _ in pairs)
+            stable = cache.get(("allowed",) + sptrs)
+            if stable is None:
+                stable = cache[("allowed",) + sptrs] = torch.tensor(sptrs, dtype=torch.int64).to(self.device)
+            self._allowed_src = (stable, stage[1], Bw, s0.num_steps)
         if self.learner.loss_mode == "ppo+smooth" and record is None and not evaluate:
             # {masks, time_limits or 0, command} of the workers' storages, source by source; the launch itself follows the
             # gather / sort, which writes `pos`
@@ -817,6 +887,11 @@ class CadreAgent(object):
             stable, idx_d, Bw, T = self._suggest_src
             hip.check(L.cadre_suggest_rows(hip.ptr(stable), 2 * nW, hip.ptr(idx_d), Bw, T, hip.ptr(w["pos"]) if srt else None, B,
                                            hip.ptr(self.learner._sug_ws(w, B)), st), "cadre_suggest_rows")
+        if self.learner.loss_mode == "ppo+mask" and not evaluate:
+            # the words of the minibatch's rows into the static workspace tensor the captured loss launch reads
+            stable, idx_d, Bw, T = self._allowed_src
+            hip.check(L.cadre_allowed_rows(hip.ptr(stable), 2 * nW, hip.ptr(idx_d), Bw, T, hip.ptr(w["pos"]) if srt else None, B,
+                                           hip.ptr(self.learner._am_ws(w, B)), st), "cadre_allowed_rows")
         if self.learner.loss_mode == "ppo+smooth" and not evaluate:
             # the kinds and the partners of the minibatch's rows into the static workspace tensors the captured loss launch reads
             stable, idx_d, Bw, T = self._smooth_src
@@ -961,12 +1036,13 @@ class CadreAgent(object):
         return out
 
     @staticmethod
-    def ensemble_act_batch(agent_group, obs_list, shifted=None, deterministic=False):
+    def ensemble_act_batch(agent_group, obs_list, shifted=None, deterministic=False, allowed=None):
         """`[CadreAgent.ensemble_act(agent_group, o) for o in obs_list]` plus `avg_action` per environment (`.controls`) in
         one launch chain per agent group: ppo_agent/evaluate.py EnsembleEvaluator.act, with one evaluator per agent group
-        kept on the lead agent.  Returns an EnsembleActBatch."""
+        kept on the lead agent.  `allowed` (action masks) is refused: the ensemble sampler does not read masks.  Returns an
+        EnsembleActBatch."""
         from .evaluate import ensemble_act_batch
-        return ensemble_act_batch(agent_group, obs_list, shifted=shifted, deterministic=deterministic)
+        return ensemble_act_batch(agent_group, obs_list, shifted=shifted, deterministic=deterministic, allowed=allowed)
 
     # ------------------------------------------------------------------ snapshots
     def save_snapshot(self, model_path, fix_missing_lstm=False):

@@ -191,13 +191,16 @@ class EnsembleEvaluator(object):
     def _same_window(c, td):
         return CadreAgent._window_shifted_vs(c, td)
 
-    def act(self, obs_list, shifted=None, deterministic=False):
+    def act(self, obs_list, shifted=None, deterministic=False, allowed=None):
         """One env step for N <= max_envs environments.  `shifted[e]`: True — environment e's window moved by one frame
         since the last call at position e; False — it is fresh (a reset, or another environment sat at this position);
         None — compare the frames on the host (what `shifted=None` does for every environment).  Sampled mode draws from
         the global torch CPU generator in the loop's order (env 0 agent 0 steer, env 0 agent 0 throttle, env 0 agent 1
         steer, ..., then env 1), one `torch.empty(1, n_out).exponential_(1)` each; `deterministic=True` draws nothing and
-        takes the first largest probability.  Returns an EnsembleActBatch."""
+        takes the first largest probability.  `allowed` (action masks) is refused.  Returns an EnsembleActBatch."""
+        if allowed is not None:
+            raise ValueError("ensemble evaluation takes no allowed= words: cadre_sample_rows_ens does not read action masks yet "
+                             "(mask inside the environment loop of one agent with act_batch(allowed=))")
         lead = self.lead
         check_act_batch(obs_list, shifted, self.max_envs, lead.device, lead.vae_device, self.C)
         N, M, C = len(obs_list), self.M, self.C
@@ -312,8 +315,11 @@ class EnsembleEvaluator(object):
         return out
 
 
-def ensemble_act_batch(agent_group, obs_list, shifted=None, deterministic=False):
-    """CadreAgent.ensemble_act_batch: one EnsembleEvaluator per agent group, kept on the lead agent."""
+def ensemble_act_batch(agent_group, obs_list, shifted=None, deterministic=False, allowed=None):
+    """CadreAgent.ensemble_act_batch: one EnsembleEvaluator per agent group, kept on the lead agent.  `allowed` is refused."""
+    if allowed is not None:
+        raise ValueError("ensemble evaluation takes no allowed= words: cadre_sample_rows_ens does not read action masks yet "
+                         "(mask inside the environment loop of one agent with act_batch(allowed=))")
     lead = agent_group[0]
     key = tuple(id(a) for a in agent_group)
     cache = lead.__dict__.setdefault("_ens_eval", {})

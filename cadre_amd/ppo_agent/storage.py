@@ -72,6 +72,23 @@ class RolloutStorage(object):
             getattr(self, k).copy_(v)
         if getattr(self, "events", None) is not None:        # (exploration suggestions: the two tensors travel along)
             self.events, self.suggest = self.events.to(device), self.suggest.to(device)
+        if getattr(self, "allowed", None) is not None:       # (action masks: the words travel along)
+            self.allowed = self.allowed.to(device)
+
+    def _allowed_tensor(self):
+        """`allowed` int64 [T + 1] (the allowed-bin word of each row; 0: unmasked), allocated the first time a word is passed: a
+        storage that never saw one has no such tensor and keeps today's launches and tensors."""
+        if getattr(self, "allowed", None) is None:
+            self.allowed = torch.zeros(self.num_steps + 1, dtype=torch.int64, device=self.device)
+        return self.allowed
+
+    @staticmethod
+    def _allowed_word(w, K=None):
+        """A Python-int word -> its int64 bit pattern (cadre_amd.actmask.check_word / word_i64: the one statement of the check).  A
+        word that allows none of the head's K bins is refused: the kernels would read it as 'unmasked'.  A storage does not know its
+        head's K: without `K` only the all-zero word can be refused (K = 64)."""
+        from ..actmask import check_word, word_i64
+        return word_i64(check_word(w, 64 if K is None else K, "allowed word"))
 
     def _event_tensors(self):
         """`events` int32 [T + 1] (the terminal-event code of each row, 0: none) and `suggest` int32 [T] (the kind
@@ -89,13 +106,18 @@ class RolloutStorage(object):
         return e
 
     def insert(self, obs, action, action_log_probs, value_preds, rewards, masks, hidden_state, command, time_limit=False,
-               event=0):
+               event=0, allowed=None, allowed_bins=None):
         """storage.py:45-58.  `time_limit`: this row's episode was cut by a step budget, not ended (see finish_rollouts).
         `event`: the code of the terminal event this row ends with for this head (0: none; see cadre_amd.suggest).  Once a
         storage has seen a code every insert writes the slot, zeros included: a stale code never survives the cursor's
-        drift."""
+        drift.  `allowed` (action masks): the word this head's action was sampled under (a Python int; None: unmasked).  Once
+        a storage has seen a word every insert writes the slot, 0 = unmasked included.  `allowed_bins`: the head's K; with it a
+        word without a bit among the K bins is refused, without it only the all-zero word (the storage does not know K)."""
         s = self.step
         event = self._event_code(event)
+        word = None if allowed is None else self._allowed_word(allowed, allowed_bins)      # (checked before anything is written)
+        if allowed is not None or getattr(self, "allowed", None) is not None:
+            self._allowed_tensor()[s] = 0 if word is None else word
         if event or getattr(self, "events", None) is not None:
             self._event_tensors()[s] = event
         if time_limit or self._tl_used:          # (a storage that never saw a flag keeps the reference's launches)
@@ -115,7 +137,7 @@ class RolloutStorage(object):
         self.step = (s + 1) % (self.num_steps + 1)
 
     @staticmethod
-    def insert_batch(storages, outputs, rewards, masks, commands, time_limits=None, events=None):
+    def insert_batch(storages, outputs, rewards, masks, commands, time_limits=None, events=None, allowed=None, n_out=None):
         """`insert` (storage.py:45-58) of one env step of N environments into their 2N storages in ONE launch
         (cadre_insert_rows; with `time_limits` its twin cadre_insert_rows_tl, which writes the flags in the same launch):
         time_limits = None, or per environment a bool or a (steer, throttle) pair of bools.  storages = [(steer_rollout, throttle_rollout), ...] per environment, outputs = what
@@ -124,8 +146,23 @@ class RolloutStorage(object):
         host-side ints, exactly as `insert` keeps them.
         `events` (exploration suggestions): None, or per environment an int code or a (steer, throttle) pair of codes (0:
         none).  All 2N codes of the step are written by ONE extra launch (cadre_suggest_note), which is not issued when
-        `events` is None and no storage has the tensor."""
+        `events` is None and no storage has the tensor.
+        `allowed` (action masks): None, per environment a (steer, throttle) pair of Python-int words, or the device int64
+        [N][2] tensor act_batch sampled under.  All 2N words of the step are written by ONE extra launch (cadre_allowed_note),
+        which is not issued when `allowed` is None and no storage has the tensor (it then writes 0 = unmasked).  `n_out` =
+        (K_steer, K_throttle): with it a Python-int word without a bit among its head's bins is refused, without it only the
+        all-zero word (the storages do not know K); a device tensor is taken as it is, as act_batch took it."""
         N = len(storages)
+        al = None
+        if allowed is not None:              # (checked before anything is launched)
+            if torch.is_tensor(allowed):
+                if allowed.dtype != torch.int64 or tuple(allowed.shape) != (N, 2) or not allowed.is_cuda:
+                    raise ValueError("insert_batch: allowed must be a device int64 [%d][2] tensor or %d (steer, throttle) pairs" % (N, N))
+                al = allowed.contiguous()
+            else:
+                if len(allowed) != N or any(not isinstance(e, (tuple, list)) or len(e) != 2 for e in allowed):
+                    raise ValueError("insert_batch: %d storage pairs, allowed must hold as many (steer, throttle) pairs of words" % N)
+                al = [RolloutStorage._allowed_word(w, None if n_out is None else n_out[h]) for e in allowed for h, w in enumerate(e)]
         if events is not None and len(events) != N:
             raise ValueError("insert_batch: %d storage pairs, %d event codes" % (N, len(events)))
         ev = None
@@ -200,6 +237,19 @@ class RolloutStorage(object):
             codes = torch.tensor(ev, dtype=torch.int32).to(dev)
             hip.check(hip.lib().cadre_suggest_note(hip.ptr(etable), hip.ptr(ints), hip.ptr(codes), 2 * N, s0.num_steps,
                                                    hip.stream()), "cadre_suggest_note")
+        if al is not None or any(getattr(s, "allowed", None) is not None for s in flat):
+            aptrs = tuple(hip.ptr(s._allowed_tensor()) for s in flat)
+            atable = tables.get(("allowed",) + aptrs)
+            if atable is None:
+                atable = tables[("allowed",) + aptrs] = torch.tensor(aptrs, dtype=torch.int64).to(dev)
+            if al is None:
+                words = torch.zeros(2 * N, dtype=torch.int64, device=dev)
+            elif torch.is_tensor(al):
+                words = al.to(dev).reshape(-1)
+            else:
+                words = torch.tensor(al, dtype=torch.int64).to(dev)
+            hip.check(hip.lib().cadre_allowed_note(hip.ptr(atable), hip.ptr(ints), hip.ptr(words), 2 * N, s0.num_steps,
+                                                   hip.stream()), "cadre_allowed_note")
         for s in flat:
             s.step = (s.step + 1) % (s.num_steps + 1)
 

@@ -356,6 +356,42 @@ def suggestions(agent, train_cfg, fused_gather=True, ck_interval=None, ck_resume
     return suggest_runner(agent, cfg, fused_gather, _get(train_cfg, "demo_mix"), ck_interval, ck_resume)
 
 
+def action_masks(agent, train_cfg, fused_gather=True, ck_interval=None, ck_resume=None):
+    """train_cfg["action_mask"] (absent / None: None — nothing runs, nothing is allocated, every launch is what it was): the
+    ActionMasks of a run whose rule restricts the bins of each act (cadre_amd.actmask.actmask_config for the value,
+    check_composition for what is refused at start-up)."""
+    cfg = _get(train_cfg, "action_mask")
+    if cfg is None:
+        return None
+    from ..actmask import actmask_runner
+    return actmask_runner(agent, cfg, fused_gather=fused_gather, demo_mix=_get(train_cfg, "demo_mix"),
+                          suggest=_get(train_cfg, "suggest"), self_imitation=_get(train_cfg, "self_imitation"),
+                          smoothness=_get(train_cfg, "smoothness"), sample_reuse=_get(train_cfg, "sample_reuse"),
+                          aux_phase=_get(train_cfg, "aux_phase"), checkpoint_interval=ck_interval, resume_from=ck_resume)
+
+
+def _check_actmask(actmask, demo, suggest, reuse, sil, smooth, fused_gather=True):
+    """A section with action masks: the other loss twins do not read the mask, and the words enter beside the fused gather."""
+    if actmask is not None:
+        from ..actmask import check_composition
+        check_composition(fused_gather=fused_gather, demo_mix=demo, suggest=suggest, self_imitation=sil, smoothness=smooth,
+                          sample_reuse=reuse)
+
+
+def _actmask_begin(agent, actmask, stats, steps):
+    """The learner's loss becomes "ppo+mask" for the section.  Returns the loss mode to restore (None without masks)."""
+    if actmask is None:
+        return None
+    return actmask.begin(agent.learner, steps if stats is not None else 0)
+
+
+def _actmask_stats(stats, actmask):
+    if stats is not None and actmask is not None:
+        summary = actmask.summary()
+        if summary is not None:
+            stats["actmask"] = summary
+
+
 def apply_suggest(agent, suggest, episode, max_episode):
     """The suggestion coefficient of `episode` (Suggestions.coeff through schedule_value) into the learner's device
     hyper-parameter block, beside apply_demo_mix: a moving coefficient replays the captured graphs as they are.  Returns
@@ -726,6 +762,9 @@ def stats_line(episode, stats):
     if "suggest" in stats:                             # exploration suggestions: marked rows and the KL towards the priors
         from ..suggest import suggest_stats_text
         line += suggest_stats_text(stats)
+    if "actmask" in stats:                             # action masks: masked rows, allowed bins, pressure
+        from ..actmask import actmask_stats_text
+        line += actmask_stats_text(stats)
     if "sil" in stats:                                 # self-imitation: the weights of the section's SIL rows
         from ..selfimit import sil_stats_text
         line += sil_stats_text(stats)
@@ -752,7 +791,7 @@ def _check_sil(sil, demo, suggest, reuse, path_ok=True):
 def learner_section(agent, steer_rollout, throttle_rollout, done, train_cfg, shared_grad_buffers,
                     optimizer=None, traffic_light=None, counter=None, shared_model_list=None, in_process_chief=True,
                     fused_gather=True, losses_on_device=False, step_events=None, stats=None, reward_scaler=None,
-                    demo=None, episode=0, reuse=None, suggest=None, sil=None, smooth=None, curiosity=None):
+                    demo=None, episode=0, reuse=None, suggest=None, sil=None, smooth=None, curiosity=None, actmask=None):
     """train.py:76-110.  Returns (value_loss_list, policy_loss_list, ent_loss_list).
     With `in_process_chief` (one process per GPU) the optimiser step runs right after the gradient
     all-reduce instead of waiting on a separate chief process.  `fused_gather` uses the storage ->
@@ -794,7 +833,10 @@ def learner_section(agent, steer_rollout, throttle_rollout, done, train_cfg, sha
     smoothness term, as in learner_section_multi.  Raises ValueError when a storage's cursor does not stand at T.
     `curiosity` (a cadre_amd.curiosity.Curiosity for one environment; needs fused_gather and a single rank, excludes
     `reward_scaler`, `reuse` and `sil`): the random network distillation bonus, as in learner_section_multi; the two storages
-    are then finished by RolloutStorage.finish_rollouts."""
+    are then finished by RolloutStorage.finish_rollouts.
+    `actmask` (a cadre_amd.actmask.ActionMasks; needs fused_gather, excludes `demo`, `suggest`, `sil`, `smooth` and `reuse`):
+    action masks, as in learner_section_multi."""
+    _check_actmask(actmask, demo, suggest, reuse, sil, smooth, fused_gather)
     _check_smooth(smooth, demo, suggest, reuse, sil, fused_gather)
     _check_curiosity(curiosity, reward_scaler, reuse, sil, shared_grad_buffers, fused_gather)
     if demo is not None and not fused_gather:
@@ -819,7 +861,7 @@ def learner_section(agent, steer_rollout, throttle_rollout, done, train_cfg, sha
         out = _learner_section(agent, steer_rollout, throttle_rollout, done, train_cfg, shared_grad_buffers, optimizer,
                                traffic_light, counter, shared_model_list, in_process_chief, fused_gather, losses_on_device,
                                step_events, use_adv_norm, sec, lr, reward_scaler, cons, demo, episode, reuse, suggest,
-                               stats, sil, smooth, curiosity)
+                               stats, sil, smooth, curiosity, actmask)
     finally:
         if sec is not None:
             agent.learner.set_update_modes()
@@ -831,6 +873,7 @@ def learner_section(agent, steer_rollout, throttle_rollout, done, train_cfg, sha
         _scale_stats(stats, reward_scaler)
         _reuse_stats(stats, reuse)
         _suggest_stats(stats, suggest)
+        _actmask_stats(stats, actmask)
         _sil_stats(stats, sil)
         _smooth_stats(stats, smooth)
         _curiosity_stats(stats, curiosity)
@@ -840,6 +883,7 @@ def learner_section(agent, steer_rollout, throttle_rollout, done, train_cfg, sha
     _scale_stats(stats, reward_scaler)
     _reuse_stats(stats, reuse)
     _suggest_stats(stats, suggest)
+    _actmask_stats(stats, actmask)
     _sil_stats(stats, sil)
     _smooth_stats(stats, smooth)
     _curiosity_stats(stats, curiosity)
@@ -852,7 +896,7 @@ def learner_section(agent, steer_rollout, throttle_rollout, done, train_cfg, sha
 def _learner_section(agent, steer_rollout, throttle_rollout, done, train_cfg, shared_grad_buffers, optimizer, traffic_light,
                      counter, shared_model_list, in_process_chief, fused_gather, losses_on_device, step_events, use_adv_norm,
                      sec, lr, reward_scaler=None, cons=False, demo=None, episode=0, reuse=None, suggest=None, stats=None,
-                     sil=None, smooth=None, curiosity=None):
+                     sil=None, smooth=None, curiosity=None, actmask=None):
     if smooth is not None:                           # (the cursor check comes before any launch of the section)
         smooth.begin_section([(steer_rollout, throttle_rollout)],
                              train_cfg["ppo_epoch"] * _steps_per_epoch(steer_rollout) if stats is not None else 0)
@@ -876,18 +920,21 @@ def _learner_section(agent, steer_rollout, throttle_rollout, done, train_cfg, sh
                               train_cfg["ppo_epoch"] * _steps_per_epoch(steer_rollout))
     if sil is not None:
         sil.begin_section(train_cfg["ppo_epoch"] * _steps_per_epoch(steer_rollout) if stats is not None else 0)
+    am_prev = _actmask_begin(agent, actmask, stats, train_cfg["ppo_epoch"] * _steps_per_epoch(steer_rollout))
     try:
         return _learner_steps(agent, steer_rollout, throttle_rollout, steer_adv, throttle_adv, train_cfg, shared_grad_buffers,
                               optimizer, traffic_light, counter, shared_model_list, in_process_chief, fused_gather,
-                              losses_on_device, step_events, sec, lr, demo, episode, reuse, suggest, sil, smooth)
+                              losses_on_device, step_events, sec, lr, demo, episode, reuse, suggest, sil, smooth, actmask)
     finally:
         if suggest is not None:
             agent.learner.loss_mode = sug_prev
+        if actmask is not None:
+            agent.learner.loss_mode = am_prev
 
 
 def _learner_steps(agent, steer_rollout, throttle_rollout, steer_adv, throttle_adv, train_cfg, shared_grad_buffers, optimizer,
                    traffic_light, counter, shared_model_list, in_process_chief, fused_gather, losses_on_device, step_events, sec,
-                   lr, demo, episode, reuse, suggest, sil=None, smooth=None):
+                   lr, demo, episode, reuse, suggest, sil=None, smooth=None, actmask=None):
     dev_losses = []
     vl, pl, el = [], [], []
     n_step = 0
@@ -912,7 +959,8 @@ def _learner_steps(agent, steer_rollout, throttle_rollout, steer_adv, throttle_a
                 dev_losses.append(agent.update_policy_from_storages(
                     live + stale, sync=False, mlp_grads_ready=hook,
                     stats_row=row, **_demo_kw(demo, a.numel(), episode, n_step, sec),
-                    **_sil_kw(sil, a.numel(), episode, epoch, j), **_smooth_kw(smooth, live)))
+                    **_sil_kw(sil, a.numel(), episode, epoch, j), **_smooth_kw(smooth, live),
+                    **({} if actmask is None else dict(actmask=actmask))))
                 if suggest is not None:
                     suggest.collect(agent.learner)
                 if sil is not None:
@@ -983,6 +1031,7 @@ def train(rank, train_cfg, agent_cfg, env_cfg, rollout_cfg, traffic_light=None, 
         if ck_resume is not None:                # (the environment is the caller's: it restarts through reset())
             first_episode = ck.resume(ck_resume)
     suggest = suggestions(agent, train_cfg, True, ck_interval, ck_resume)      # (refusals first: before anything is loaded)
+    actmask = action_masks(agent, train_cfg, True, ck_interval, ck_resume)
     demo = demo_mixer(agent, train_cfg, rollout_cfg, rank)          # (before the warm start, which shares its DemoSet)
     _pretrain(agent, train_cfg, rollout_cfg, shared_grad_buffers, rank, logger, ck_resume, shared_model_list, traffic_light)
     aux = _aux_runner(agent, train_cfg, shared_grad_buffers, rank, traffic_light is None, ck_interval, first_episode,
@@ -993,19 +1042,24 @@ def train(rank, train_cfg, agent_cfg, env_cfg, rollout_cfg, traffic_light=None, 
     smooth = smoothness(agent, train_cfg)
     obs = env.reset()
     done = False
+    info = None                                  # (the action-mask rule sees the last step's info; None after a reset)
     log_stats = bool(_get(train_cfg, "log_stats", False))
     for episode in range(first_episode, train_cfg.max_episode):
         _rewind(smooth, [(steer_rollout, throttle_rollout)])
         for _ in range(num_steps):
             command = obs["command"]
             raw = dict(obs, rgb=obs["rgb"].copy(), route_fig=obs["route_fig"].copy()) if recorder is not None else None
-            feat, action, alp, values, hidden = agent.act(obs)
+            words = None if actmask is None else actmask.words(obs, info)      # (key absent: today's call)
+            feat, action, alp, values, hidden = agent.act(obs, **({} if words is None else dict(allowed=words)))
             obs, reward, done, info = env.step(agent.convert_action(action))
             ad = info["action_done"]
             if recorder is not None:            # cadre_amd.replay.RolloutRecorder
                 recorder.step(raw, action, alp, values, reward, ad)
             tl = _time_limit_pair(info.get("time_limit", False))        # (key absent: no flag is ever written)
             ev = ({}, {}) if suggest is None else tuple(dict(event=c) for c in suggest.codes(info))   # (key absent: today's call)
+            if words is not None:
+                nS, nT = agent.arena.n_out
+                ev = (dict(ev[0], allowed=words[0], allowed_bins=nS), dict(ev[1], allowed=words[1], allowed_bins=nT))
             steer_rollout.insert(feat, action[0], alp[0], values[0], reward[0],
                                  torch.tensor([[0.0] if ad[0] else [1.0]]), hidden, command, time_limit=tl[0],
                                  **ev[0])
@@ -1013,7 +1067,7 @@ def train(rank, train_cfg, agent_cfg, env_cfg, rollout_cfg, traffic_light=None, 
                                     torch.tensor([[0.0] if ad[1] else [1.0]]), hidden, command, time_limit=tl[1],
                                     **ev[1])
             if done:
-                obs = env.reset()
+                obs, info = env.reset(), None
         if recorder is not None:
             recorder.end_episode()
         stats = {} if log_stats else None
@@ -1030,6 +1084,7 @@ def train(rank, train_cfg, agent_cfg, env_cfg, rollout_cfg, traffic_light=None, 
                                      reward_scaler=agent.reward_scaler, demo=demo, episode=episode,
                                      **({} if reuse is None else dict(reuse=reuse.window_for([(steer_rollout, throttle_rollout)]))),
                                      **({} if suggest is None else dict(suggest=suggest)),
+                                     **({} if actmask is None else dict(actmask=actmask)),
                                      **({} if sil is None else dict(sil=sil.buffer_for([(steer_rollout, throttle_rollout)]))),
                                      **({} if smooth is None else dict(smooth=smooth)),
                                      **({} if cur is None else dict(curiosity=cur)))
@@ -1064,7 +1119,7 @@ def train(rank, train_cfg, agent_cfg, env_cfg, rollout_cfg, traffic_light=None, 
 # ----------------------------------------------------------------------------- N environments in one process
 def learner_section_multi(agent, rollouts, dones, train_cfg, shared_grad_buffers, optimizer=None, losses_on_device=False,
                           stats=None, reward_scaler=None, demo=None, episode=0, reuse=None, suggest=None, sil=None,
-                          smooth=None, curiosity=None):
+                          smooth=None, curiosity=None, actmask=None):
     """train.py:76-110 for N workers that share one agent (`num_processes = N` on one GPU, chief.py:13-21 semantics):
     rollouts = [(steer_rollout, throttle_rollout), ...] per worker, dones[i] = worker i's last `done`.  Bootstrap values
     of all workers in one pass (get_values), GAE + advantage normalisation per storage, then for each ppo_epoch and
@@ -1114,7 +1169,14 @@ def learner_section_multi(agent, rollouts, dones, train_cfg, shared_grad_buffers
     the random network distillation bonus.  Before the storages are finished curiosity.begin_section(rollouts) scores the
     section's rows and writes every storage's `rewards_mixed`, which finish_rollouts(intrinsic=) hands to the GAE launch in
     place of `rewards`; behind the PPO steps curiosity.update() runs the predictor's steps.  `stats` gains "curiosity" (mean_e,
-    max_e, sigma, beta, mean_abs_bonus, mean_abs_ext, steps, loss_before, loss_after; one more small device-to-host copy)."""
+    max_e, sigma, beta, mean_abs_bonus, mean_abs_ext, steps, loss_before, loss_after; one more small device-to-host copy).
+    `actmask` (a cadre_amd.actmask.ActionMasks; excludes `demo`, `suggest`, `sil`, `smooth` and `reuse`, whose kernels do not read
+    the mask): action masks.  The learner's loss becomes "ppo+mask" for the section and every step carries the `allowed` words
+    of its rows (what insert_batch(allowed=) stored beside them) into the update's layout (cadre_allowed_rows) before the
+    update, whose loss launch is cadre_ppo_am_loss.  The loss is per rank and nothing new is exchanged.  `stats` gains
+    "actmask" (masked_share, allowed_bins, pressure, forced_rows as (steer, throttle) pairs; one more small device-to-host
+    copy)."""
+    _check_actmask(actmask, demo, suggest, reuse, sil, smooth)
     _check_smooth(smooth, demo, suggest, reuse, sil)
     _check_curiosity(curiosity, reward_scaler, reuse, sil, shared_grad_buffers)
     if smooth is not None:                           # (the cursor check comes before any launch of the section)
@@ -1146,10 +1208,11 @@ def learner_section_multi(agent, rollouts, dones, train_cfg, shared_grad_buffers
     if sec is not None:
         agent.learner.set_update_modes(stats=True, target_kl=tkl, consensus=cons)
     dev_losses = []
-    sug_prev = None
+    sug_prev = am_prev = None
     try:
         sug_prev = _suggest_begin(agent, suggest, [x for pair in rollouts for x in pair], stats,
                                   train_cfg["ppo_epoch"] * _steps_per_epoch(rollouts[0][0]))
+        am_prev = _actmask_begin(agent, actmask, stats, train_cfg["ppo_epoch"] * _steps_per_epoch(rollouts[0][0]))
         if sil is not None:
             sil.begin_section(train_cfg["ppo_epoch"] * _steps_per_epoch(rollouts[0][0]) if stats is not None else 0)
         for epoch in range(train_cfg["ppo_epoch"]):
@@ -1162,7 +1225,8 @@ def learner_section_multi(agent, rollouts, dones, train_cfg, shared_grad_buffers
                 dev_losses.append(agent.update_policy_from_storages(
                     batches, sync=False, stats_row=None if sec is None else sec.next_row(),
                     **_demo_kw(demo, batches[0][1].numel(), episode, len(dev_losses), sec),
-                    **_sil_kw(sil, batches[0][1].numel(), episode, epoch, j), **smooth_kw))
+                    **_sil_kw(sil, batches[0][1].numel(), episode, epoch, j), **smooth_kw,
+                    **({} if actmask is None else dict(actmask=actmask))))
                 if suggest is not None:
                     suggest.collect(agent.learner)
                 if sil is not None:
@@ -1174,6 +1238,8 @@ def learner_section_multi(agent, rollouts, dones, train_cfg, shared_grad_buffers
             agent.learner.set_update_modes()
         if sug_prev is not None:
             agent.learner.loss_mode = sug_prev
+        if am_prev is not None:
+            agent.learner.loss_mode = am_prev
     _curiosity_end(stats, curiosity)
     losses = torch.stack(dev_losses)
     if sec is not None and not losses_on_device:
@@ -1181,6 +1247,7 @@ def learner_section_multi(agent, rollouts, dones, train_cfg, shared_grad_buffers
         _scale_stats(stats, reward_scaler)
         _reuse_stats(stats, reuse)
         _suggest_stats(stats, suggest)
+        _actmask_stats(stats, actmask)
         _sil_stats(stats, sil)
         _smooth_stats(stats, smooth)
         _curiosity_stats(stats, curiosity)
@@ -1190,6 +1257,7 @@ def learner_section_multi(agent, rollouts, dones, train_cfg, shared_grad_buffers
         _scale_stats(stats, reward_scaler)
         _reuse_stats(stats, reuse)
         _suggest_stats(stats, suggest)
+        _actmask_stats(stats, actmask)
         _sil_stats(stats, sil)
         _smooth_stats(stats, smooth)
         _curiosity_stats(stats, curiosity)
@@ -1270,6 +1338,7 @@ def train_vec(rank, train_cfg, agent_cfg, env_cfg, rollout_cfg, num_envs, env_cl
         if ck_resume is not None:                # (the environments are the caller's: they restart through reset())
             first_episode = ck.resume(ck_resume)
     suggest = suggestions(agent, train_cfg, True, ck_interval, ck_resume)      # (refusals first: before anything is loaded)
+    actmask = action_masks(agent, train_cfg, True, ck_interval, ck_resume)
     demo = demo_mixer(agent, train_cfg, rollout_cfg, rank)          # (before the warm start, which shares its DemoSet)
     _pretrain(agent, train_cfg, rollout_cfg, shared_grad_buffers, rank, logger, ck_resume)
     aux = _aux_runner(agent, train_cfg, shared_grad_buffers, rank, True, ck_interval, first_episode)
@@ -1278,6 +1347,7 @@ def train_vec(rank, train_cfg, agent_cfg, env_cfg, rollout_cfg, num_envs, env_cl
     smooth = smoothness(agent, train_cfg)
     obs = [env.reset() for env in envs]
     dones = [False] * num_envs
+    infos = [None] * num_envs                    # (the action-mask rule sees the last step's info; None after a reset)
     log_stats = bool(_get(train_cfg, "log_stats", False))
     state = lambda: dict(agent=agent, envs=envs, rollouts=rollouts, reward_scaler=agent.reward_scaler)
     if callback is not None:
@@ -1286,10 +1356,12 @@ def train_vec(rank, train_cfg, agent_cfg, env_cfg, rollout_cfg, num_envs, env_cl
         _rewind(smooth, rollouts)
         for _ in range(num_steps):
             commands = [o["command"] for o in obs]
-            outs = agent.act_batch(obs)
+            words = None if actmask is None else [actmask.words(o, f) for o, f in zip(obs, infos)]
+            outs = agent.act_batch(obs, **({} if words is None else dict(allowed=words)))      # (key absent: today's call)
             rewards, masks, tls, evs = [], [], [], []
             for i, (env, out) in enumerate(zip(envs, outs)):
                 obs[i], reward, dones[i], info = env.step(agent.convert_action(out[1]))
+                infos[i] = info
                 ad = info["action_done"]
                 rewards.append(reward)
                 masks.append([0.0 if ad[0] else 1.0, 0.0 if ad[1] else 1.0])
@@ -1299,10 +1371,11 @@ def train_vec(rank, train_cfg, agent_cfg, env_cfg, rollout_cfg, num_envs, env_cl
             RolloutStorage.insert_batch(rollouts, outs, rewards, masks, commands,
                                         time_limits=None if all(f is None for f in tls) else
                                         [_time_limit_pair(False if f is None else f) for f in tls],
-                                        **({} if suggest is None else dict(events=evs)))
+                                        **({} if suggest is None else dict(events=evs)),
+                                        **({} if words is None else dict(allowed=outs.allowed)))
             for i, env in enumerate(envs):
                 if dones[i]:
-                    obs[i] = env.reset()
+                    obs[i], infos[i] = env.reset(), None
         if callback is not None:
             callback("rollout", episode=episode, dones=list(dones), **state())
         stats = {} if log_stats else None
@@ -1316,6 +1389,7 @@ def train_vec(rank, train_cfg, agent_cfg, env_cfg, rollout_cfg, num_envs, env_cl
                                            stats=stats, reward_scaler=agent.reward_scaler, demo=demo, episode=episode,
                                            **({} if reuse is None else dict(reuse=reuse.window_for(rollouts))),
                                            **({} if suggest is None else dict(suggest=suggest)),
+                                           **({} if actmask is None else dict(actmask=actmask)),
                                            **({} if sil is None else dict(sil=sil.buffer_for(rollouts))),
                                            **({} if smooth is None else dict(smooth=smooth)),
                                            **({} if cur is None else dict(curiosity=cur)))

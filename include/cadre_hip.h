@@ -1281,6 +1281,54 @@ int cadre_rnd_backward(const float* xh, const float* h1, const float* h2, const 
                        int32_t D, int32_t H, int32_t E, const float* predictor, double* state, int32_t thresh, float* grads,
                        float* loss, float* scratch, void* stream);
 
+/* ---------------------------------------------------------------- action masks (opt-in, csrc/actmask.h, csrc/actmask.hip)
+ * Invalid-action masking (Huang & Ontañón 2020) for the two categorical / ordinal heads.  A row of a head carries one 64-bit
+ * word `allowed` (int64 tensors, read as uint64): bit k set means bin k may be chosen.  The mask acts in BIN space, after the
+ * ordinal transform where the head is ordinal: with on = lane < K and x the logit of bin `lane`,
+ *   on_m = on && bit(lane)      x = on_m ? x : -inf
+ * and the two softmax passes, the entropy, the probabilities and d total / d logit use on_m where the unmasked kernels use on
+ * (ord_backward receives the masked gradient and the unmasked on).  A word with no bit set among the head's K bins means
+ * "unmasked": all K bins allowed.  With every bit of the K bins set (or none) every output is bit-identical to the entry
+ * point that is extended.  `ord` is required as in the `_ord` entry points (a marker table selects the categorical head).
+ *
+ * cadre_sample_am / cadre_sample_rows_am: cadre_sample_ord / cadre_sample_rows_ord with allowed int64 [R] / [N][2]
+ * (environment order): argmax(p / q) over the allowed bins, lowest index on ties; q is read for all K bins; logp is the
+ * masked log-probability of the chosen bin.
+ * cadre_categorical_eval_am: cadre_categorical_eval_ord under allowed int64 [R]; the given action's bit is OR-ed in first.
+ * cadre_allowed_note: allowed[k][slots[k]] = words[k] for n storages in one launch; table: device array of n pointers to the
+ * storages' int64 [T + 1] tensors (0: skipped), 0 <= slots[k] <= T.
+ * cadre_allowed_rows: the words of a minibatch in the layout of the update, out int64 [2][B]: source zi = 2 * worker + head of
+ * src_table (n_src pointers to int64 [T + 1], 0: a storage without words, its rows get 0 = unmasked), row b of the worker is
+ * idx[zi * Bw + b] (0 <= idx < T) and goes to out[head * B + pos[head * B + worker * Bw + b]] (pos NULL: identity).
+ * cadre_ppo_am_loss: the argument list and behaviour of cadre_ppo_loss_ord (grid, scratch protocol, poison, stats row,
+ * kl_rule.h gate) plus allowed int64 [2][B] in the layout of the sample arrays.  In the loss the taken action is allowed by
+ * definition: after the "empty means all" rule, m |= 1 << a, so foreign data cannot produce -inf log-probabilities.
+ * am_stats (may be NULL) float [2][am_F], am_F >= CADRE_AM_STATS_FIELDS, per head with every mean taken over the head's counted
+ * rows (a command in range; zeros for a head without one):
+ *   0 share of rows with a proper mask (a bin of K forbidden)   1 mean number of allowed bins
+ *   2 mean pressure 1 - exp(lse_masked - lse_unmasked), the mass the unmasked head would put on forbidden bins
+ *   3 rows whose action bit had to be OR-ed in (a count)
+ * am_scratch (needed with am_stats): 10 * ceil(B / 16) floats of per-workgroup partials, combined by the last arriving
+ * workgroup in workgroup order (no float atomics: two launches on the same inputs give the same bits). */
+#define CADRE_AM_STATS_FIELDS 4
+int cadre_sample_am(const float* logits, int64_t ldl, const float* q, int64_t ldq, int32_t R, int32_t n_out, int64_t* action,
+                    float* logp, const int32_t* ord, const int64_t* allowed, void* stream);
+int cadre_sample_rows_am(const float* O3, int64_t ldo, int64_t z_str, const int32_t* pos, const int32_t* cmd, int32_t N,
+                         int32_t C, const float* q, int32_t K_steer, int32_t K_throttle, int64_t* action, float* logp,
+                         float* value, const int32_t* ord, const int64_t* allowed, void* stream);
+int cadre_categorical_eval_am(const float* logits, int64_t ldl, const int64_t* actions, int32_t R, int32_t n_out, float* logp,
+                              float* entropy, const int32_t* ord, const int64_t* allowed, void* stream);
+int cadre_allowed_note(const void* table, const int32_t* slots, const int64_t* words, int32_t n, int32_t T, void* stream);
+int cadre_allowed_rows(const void* src_table, int32_t n_src, const int64_t* idx, int32_t Bw, int32_t T, const int32_t* pos,
+                       int32_t B, int64_t* out, void* stream);
+int cadre_ppo_am_loss(const float* logits, int64_t ldl, int64_t l_ns, const float* values, int64_t ldv, int64_t v_ns,
+                      const int64_t* actions, const int32_t* commands, const float* old_values, const float* returns,
+                      const float* old_logp, const float* adv, int32_t B, int32_t C, int32_t n_out_steer,
+                      int32_t n_out_throttle, double* hp, float clip, float value_coeff, float clip_coeff, float ent_coeff,
+                      float inv_b, float* losses, float* dlogits, float* dvalues, float* scratch, const int32_t* poison,
+                      float* stats_row, int32_t F, float* stats_scratch, float target_kl, int32_t* stop, const int32_t* ord,
+                      const int64_t* allowed, float* am_stats, int32_t am_F, float* am_scratch, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
