@@ -157,10 +157,9 @@ class ActionMasks(object):
 
     # -- one learner section
     def begin(self, learner, steps=0):
-        """Switch the learner's loss for the section; `steps` > 0: collect the mask statistics of that many steps.  Returns the loss
-        mode to restore."""
-        prev = learner.loss_mode
-        learner.set_loss("ppo+mask")
+        """Switch the learner's loss for the section; `steps` > 0: collect the mask statistics of that many steps.  Returns what
+        learner.loss_restore takes."""
+        prev = learner.loss_begin("ppo+mask")
         self._n = 0
         if steps:
             if self._rows is None or self._rows.shape[0] < steps:

@@ -283,8 +283,7 @@ def pretrain(agent, demo, optimizer_or_shared, epochs, minibatch, lr, max_grad_n
     betas, eps = _optimizer_hyper(agent, optimizer_or_shared)
     lrn, dev, F = agent.learner, agent.arena.device, hip.BC_STATS_FIELDS
     emit = None if log is None else (log.log if hasattr(log, "log") else log)
-    prev = (lrn.loss_mode,) + lrn._bc
-    lrn.set_loss("bc", label_smoothing=label_smoothing, bc_coeff=bc_coeff)
+    prev = lrn.loss_begin("bc", label_smoothing=label_smoothing, bc_coeff=bc_coeff)
     records = []
     try:
         for epoch in range(int(epochs)):
@@ -310,7 +309,7 @@ def pretrain(agent, demo, optimizer_or_shared, epochs, minibatch, lr, max_grad_n
                     line += ", validation nll: {:.4f}/{:.4f}, accuracy: {:.4f}/{:.4f}".format(*(rec["val_nll"] + rec["val_accuracy"]))
                 emit(line)
     finally:
-        lrn.loss_mode, lrn._bc = prev[0], prev[1:]
+        lrn.loss_restore(prev)
         if reset_optimizer:
             reset_adam(agent)
     return records

@@ -11,6 +11,8 @@ would apply) and writes straight into the flat gradient arena.  No autograd grap
 per-parameter tensors, nothing on the host between launches — the whole update is 24 launches
 on one stream, replayed as a hipGraph.
 """
+import collections
+import contextlib
 import os
 
 import numpy as np
@@ -19,6 +21,80 @@ import torch
 from . import hip
 
 _UPDATE_PARTS = ("all", "front", "mid", "back")
+
+# One record per loss of the update step (PPOLearnerHIP.set_loss); everything the host does per mode is read from here.
+#   launch       the method that enqueues the loss where the PPO loss stands; its docstring describes the mode
+#   tag          first element of the mode's entry in the hipGraph keys (_mode_key); None: no entry
+#   state        the attribute that holds the mode's scalars as a tuple, in the order of `scalars`
+#   scalars      (set_loss keyword, field of the device-hyper block or None) each.  A scalar without a field goes by value always and
+#                is part of the key always; one with a field lives in the block in device-hyper mode (set_hyper moves it, the key
+#                leaves it out) and None keeps its current value
+#   rows         the attribute of the PPO / other row split (set by "set" + rows); strict: 0 < B_ppo < B instead of 0 <= B_ppo <= B
+#   table        (attribute, its part of the key while unset, the call that sets it): a tensor [2][R][64] or a (tensor, extras) pair
+#                whose address is baked into captured graphs, so the key holds the address, then R or the extras
+#   check        a refusal of set_loss and update (the mode runs outside the learner section)
+#   own_stats    (workspace key, fields): the mode has no PPO diagnostics; update(stats_row=) copies these instead
+#   last_stats   (attribute, workspace key): the statistics tensor of the step that ran last, for the section object
+#   reads_allowed / one_geometry   the launch reads the rows' `allowed` words / the storages of a step must share one geometry
+class LossMode(collections.namedtuple(
+        "LossMode", "launch tag state scalars rows strict table check own_stats last_stats reads_allowed one_geometry",
+        defaults=(None, None, (), None, False, None, None, None, None, False, False))):
+    __slots__ = ()
+    ppo = property(lambda m: m.own_stats is None, doc="the loss has the PPO ratio (it reads old_logp) and the PPO diagnostics")
+
+
+LOSS_MODES = {
+    "ppo": LossMode("_ppo_launch"),
+    "bc": LossMode("_bc_launch", "bc", "_bc", (("label_smoothing", None), ("bc_coeff", None)), check="_check_bc_modes",
+                   own_stats=("bc_stats", hip.BC_STATS_FIELDS)),
+    "ppo+demo": LossMode("_demo_launch", "demo", "_demo", (("label_smoothing", None), ("demo_coeff", hip.HP_DEMO_COEFF),
+                                                          ("demo_value_coeff", hip.HP_DEMO_VALUE_COEFF)), rows="_demo_rows"),
+    "aux": LossMode("_aux_launch", "aux", "_aux", (("beta_clone", None), ("aux_value_coeff", None)),
+                    table=("_aux_table", (None, 0), "set_aux_table(table)"), check="_check_aux_modes",
+                    own_stats=("aux_stats", hip.AUX_STATS_FIELDS)),
+    "ppo+suggest": LossMode("_sug_launch", "suggest", "_sug", (("suggest_coeff", hip.HP_SUGGEST_COEFF),),
+                            table=("_sug_tables", (None, 0), "set_suggest_tables(prior, Z)"),
+                            last_stats=("_last_sug_stats", "sug_stats"), one_geometry=True),
+    "ppo+sil": LossMode("_sil_launch", "sil", "_sil", (("sil_coeff", hip.HP_SIL_COEFF), ("sil_value_coeff", hip.HP_SIL_VALUE_COEFF)),
+                        rows="_sil_rows"),
+    "ppo+smooth": LossMode("_smooth_launch", "smooth", "_smooth", (("smooth_coeff", hip.HP_SMOOTH_COEFF),), rows="_smooth_rows",
+                           strict=True, table=("_smooth_tables", (None,), "set_smooth_tables(ctrl, head_scale)"), one_geometry=True),
+    "ppo+mask": LossMode("_am_launch", "mask", last_stats=("_last_am_stats", "am_stats"), reads_allowed=True, one_geometry=True),
+}
+# the loss coefficients that can live in the block: keyword -> (state attribute, position in it, block field)
+_HP_LOSS = {k: (m.state, i, field) for m in LOSS_MODES.values() for i, (k, field) in enumerate(m.scalars) if field is not None}
+_KEEP = object()
+
+
+def _loss_record(mode):
+    """The record of a loss mode by name."""
+    if mode not in LOSS_MODES:
+        raise ValueError("set_loss: mode %r (known: %s)" % (mode, ", ".join(repr(k) for k in LOSS_MODES)))
+    return LOSS_MODES[mode]
+
+
+def _loss_scalars(m, given, current):
+    """The scalars of mode `m` from set_loss's keywords, as the tuple its state attribute holds.  label_smoothing: in [0, 1).  Every
+    other one is a coefficient: a finite number, no bool; None keeps the current value of a coefficient that can live in the block."""
+    bad = ValueError("set_loss: " + ", ".join("%s=%r" % (k, given[k]) for k, _ in m.scalars if k != "label_smoothing"))
+    out = []
+    for (k, field), cur in zip(m.scalars, current):
+        v = given[k]
+        if k == "label_smoothing":
+            v = float(v)
+            if not 0.0 <= v < 1.0:
+                raise ValueError("set_loss: label_smoothing must be in [0, 1) (got %r)" % (given[k],))
+        else:
+            if isinstance(v, bool):
+                raise bad
+            try:
+                v = cur if (v is None and field is not None) else float(v)
+            except (TypeError, ValueError):
+                raise bad
+            if not np.isfinite(v):
+                raise bad
+        out.append(v)
+    return tuple(out)
 
 
 def _hyper_property(attr, field):
@@ -47,6 +123,8 @@ class PPOLearnerHIP:
     vc = _hyper_property("_vc", "value_coeff")
     cc = _hyper_property("_cc", "clip_coeff")
     ec = _hyper_property("_ec", "ent_coeff")
+    _sug_coeff = property(lambda self: self._sug[0])
+    _smooth_coeff = property(lambda self: self._smooth[0])
 
     def sorted_rows(self, B):
         """Row-sorted update (rows of a minibatch grouped by command; every kernel of the step then works on exactly
@@ -116,15 +194,15 @@ class PPOLearnerHIP:
         self._aux = (1.0, 1.0)     # (beta_clone, aux_value_coeff)
         self._aux_table = None     # device float32 [2][R][64]; its address and R are part of the hipGraph keys
         # "ppo+suggest": cadre_ppo_sug_loss — the PPO loss plus KL(pi || prior of the row's terminal event) on marked rows
-        self._sug_coeff = 0.0
-        self._sug_tables = None    # (prior: device float32 [2][Z + 1][64], Z); the address and Z are part of the hipGraph keys
+        self._sug = (0.0,)         # (suggest_coeff,)
+        self._sug_tables = None   # (prior: device float32 [2][Z + 1][64], Z); the address and Z are part of the hipGraph keys
         self._sug_ord = None       # the rank table of two categorical heads (the entry point wants one), when the arena has none
         self._last_sug_stats = None  # workspace(B)["sug_stats"] of the "ppo+suggest" update that ran last
         # "ppo+sil": cadre_ppo_sil_loss — PPO rows and self-imitation rows (the agent's own past rollouts) in one minibatch
         self._sil = (0.0, 0.0)     # (sil_coeff, sil_value_coeff)
         self._sil_rows = None      # B_ppo: the leading unsorted rows of the minibatch that are PPO rows (set_sil_rows)
         # "ppo+smooth": cadre_ppo_smooth_loss — PPO rows and their successor rows in one minibatch, coupled in pairs
-        self._smooth_coeff = 0.0
+        self._smooth = (0.0,)      # (smooth_coeff,)
         self._smooth_rows = None   # B_ppo: the leading unsorted rows of the minibatch that are PPO rows (set_smooth_rows)
         self._smooth_tables = None  # (ctrl: device float32 [2][64], (scale_steer, scale_throttle)); the address is part of the graph keys
         # "ppo+mask": cadre_ppo_am_loss — the PPO loss under the rows' allowed-bin words (workspace(B)["allowed"])
@@ -134,174 +212,157 @@ class PPOLearnerHIP:
     # ------------------------------------------------------------------ loss selection
     def set_loss(self, mode, label_smoothing=0.0, bc_coeff=1.0, demo_coeff=None, demo_value_coeff=None, beta_clone=1.0,
                  aux_value_coeff=1.0, suggest_coeff=None, sil_coeff=None, sil_value_coeff=None, smooth_coeff=None):
-        """"ppo" (default): the clipped-surrogate loss.  "bc": behaviour cloning — cross-entropy against the demonstrated bin
-        (workspace `actions`; -1 = no label for that head) with `label_smoothing` in [0, 1) and weight `bc_coeff`, the critic
-        regressed on workspace `returns`, the learner's own value_coeff / ent_coeff, per-row weights from the `adv` slot;
-        old_values / old_logp are not read.  The imitation statistics of a step (hip.BC_STATS_FIELDS per head) are in
-        workspace(B)["bc_stats"].  By-value scalars only: refused together with the device-hyper block.
+        """"ppo" (default): the clipped-surrogate loss.  Every other mode (LOSS_MODES) is described at its launch: "bc" _bc_launch,
+        "ppo+demo" _demo_launch, "aux" _aux_launch, "ppo+suggest" _sug_launch, "ppo+sil" _sil_launch, "ppo+smooth" _smooth_launch,
+        "ppo+mask" _am_launch.  The keywords are the scalars of the mode that is being selected; those of another mode are not read."""
+        given = dict(locals())
+        m = _loss_record(mode)
+        if m.scalars:
+            vals = _loss_scalars(m, given, getattr(self, m.state))
+            if m.check:
+                getattr(self, m.check)()
+            setattr(self, m.state, vals)
+            block = {k: v for (k, field), v in zip(m.scalars, vals) if field is not None}
+            if block and self._hp_on:
+                self.set_hyper(**block)
+        self.loss_mode = mode
+
+    def loss_begin(self, mode, rows=None, table=_KEEP, **scalars):
+        """This loss until loss_restore(token): set_loss(mode, **scalars) where a None scalar keeps its current value, the row split
+        `rows` of a mode that has one and the table `table` of one that has one.  Returns the token."""
+        m = _loss_record(mode)
+        saved = [(attr, getattr(self, attr)) for attr in (m.rows, m.state if scalars else None, m.table and m.table[0]) if attr]
+        token = (self.loss_mode, m, saved)
+        try:
+            if table is not _KEEP:
+                getattr(self, m.table[2].split("(")[0])(table)
+            cur = dict(zip((k for k, _ in m.scalars), getattr(self, m.state))) if m.scalars else {}
+            self.set_loss(mode, **{k: cur.get(k) if v is None else v for k, v in scalars.items()})
+            if m.rows:
+                self._set_rows(m.rows, rows)
+        except Exception:
+            self.loss_restore(token)
+            raise
+        return token
+
+    def loss_restore(self, token):
+        """Back to what loss_begin found: the mode, the row split and the table always; the scalars when the call gave any — except
+        those of a mode whose coefficients live in the block, in device-hyper mode: values written to the block stay."""
+        mode, m, saved = token
+        self.loss_mode = mode
+        for attr, value in saved:
+            if not (attr == m.state and self._hp_on and any(field is not None for _, field in m.scalars)):
+                setattr(self, attr, value)
+
+    @contextlib.contextmanager
+    def loss_scope(self, mode, **kw):
+        """with learner.loss_scope(mode, ...): loss_begin / loss_restore around one call."""
+        token = self.loss_begin(mode, **kw)
+        try:
+            yield self
+        finally:
+            self.loss_restore(token)
+
+    def _set_rows(self, attr, B_ppo):
+        if B_ppo is not None and int(B_ppo) < 0:
+            raise ValueError("set%s: B_ppo=%r" % (attr, B_ppo))
+        setattr(self, attr, None if B_ppo is None else int(B_ppo))
+
+    def set_demo_rows(self, B_ppo):
+        """"ppo+demo": unsorted rows 0 .. B_ppo - 1 of the next minibatches are PPO rows, the rest demonstration rows."""
+        self._set_rows("_demo_rows", B_ppo)
+
+    def set_sil_rows(self, B_ppo):
+        """"ppo+sil": unsorted rows 0 .. B_ppo - 1 of the next minibatches are PPO rows, the rest SIL rows."""
+        self._set_rows("_sil_rows", B_ppo)
+
+    def set_smooth_rows(self, B_ppo):
+        """"ppo+smooth": unsorted rows 0 .. B_ppo - 1 of the next minibatches are PPO rows, the rest successor rows."""
+        self._set_rows("_smooth_rows", B_ppo)
+
+    def _split(self, B):
+        """B_ppo of the selected mode, checked against the minibatch."""
+        m = LOSS_MODES[self.loss_mode]
+        B_ppo = getattr(self, m.rows)
+        if B_ppo is None or (not 0 < B_ppo < B if m.strict else B_ppo > B):
+            raise hip.CadreHipError("the %r loss needs set%s(B_ppo) with %s (got %r, B = %d)"
+                                    % (self.loss_mode, m.rows, "0 < B_ppo < B" if m.strict else "0 <= B_ppo <= B", B_ppo, B))
+        return B_ppo
+
+    def _table(self):
+        """The table of the selected mode."""
+        attr, _, setter = LOSS_MODES[self.loss_mode].table
+        if getattr(self, attr) is None:
+            raise hip.CadreHipError("the %r loss needs %s first" % (self.loss_mode, setter))
+        return getattr(self, attr)
+
+    # the runs of arguments the loss entry points share (every PPO-family one takes rows, scalars, gradients and the stats tail, in
+    # that order); a launch puts its own between them
+    def _tower_args(self, w, B):
+        """Logits and values of the towers, each with its pitch and net stride."""
+        O3, NP = w["O3"], self.a.NP
+        return (hip.ptr(O3), NP, 2 * B * NP, hip.ptr(O3[1]), NP, 2 * B * NP)
+
+    def _row_args(self, w, B):
+        """The tower outputs, then the six row arrays of the minibatch."""
+        return self._tower_args(w, B) + tuple(hip.ptr(w[k]) for k in ("actions", "commands", "old_values", "returns", "old_logp", "adv"))
+
+    def _scalar_args(self, B, inv_b):
+        """B, C, K0, K1, then the block (NULL: the four scalars that follow count), clip, vc, cc, ec and inv_b."""
+        a = self.a
+        return (B, a.C, a.n_out[0], a.n_out[1], hip.ptr(self._hp) if self._hp_on else None, self.clip, self.vc, self.cc, self.ec, inv_b)
+
+    def _stats_args(self, w, B):
+        """The stats row (NULL: no diagnostics), F, its scratch, target_kl of the launch and the gate's flag."""
+        stats = self._loss_stats()
+        srow, sscr = self._stats_ws(w, B) if stats else (None, None)
+        return (hip.ptr(srow), srow.shape[1] if stats else 0, hip.ptr(sscr), self._loss_tkl(),
+                hip.ptr(self._stop) if (stats and self.target_kl is not None) else None)
+
+    def _grad_args(self, w, *scratch):
+        """dO3 (dlogits, dvalues), the loss scratch, a mode's own scratch tensors and the sync word the launch clears."""
+        dO3 = w["dO3"]
+        return ((hip.ptr(dO3), hip.ptr(dO3[1]), hip.ptr(w["loss_scratch"])) + tuple(hip.ptr(w[k]) for k in scratch)
+                + (hip.ptr(w["sync"][self.a.Z * self.S:]),))
+
+    def _ord(self, marker=False):
+        """The arena's rank table; marker: the table of two categorical heads where the arena has none."""
+        ord_t = getattr(self.a, "ord", None)
+        return self.marker_ord() if (ord_t is None and marker) else ord_t
+
+    def _mix_kinds(self, w, B, B_ppo, sorted_rows):
+        hip.check(hip.lib().cadre_mix_row_kinds(hip.ptr(w["pos"]) if sorted_rows else None, B, B_ppo, hip.ptr(w["row_kind"]),
+                                                hip.stream()), "cadre_mix_row_kinds")
+
+    # ------------------------------------------------------------------ demonstration mixing
+    def _demo_ws(self, w, B):
+        """The static tensors of the "ppo+demo" loss in workspace(B)."""
+        if "row_kind" not in w:
+            dev, nblk = self.a.device, (B + 15) // 16
+            w["row_kind"] = torch.zeros(2, B, dtype=torch.int32, device=dev)
+            w["demo_losses"] = torch.zeros(2, device=dev)
+            w["demo_stats"] = torch.zeros(2, hip.BC_STATS_FIELDS, device=dev)
+            w["demo_scratch"] = torch.zeros(2 * nblk * (2 + hip.BC_STATS_FIELDS), device=dev)
+
+    def _demo_launch(self, w, B, inv_b, sorted_rows):
+        """cadre_mix_row_kinds + cadre_ppo_demo_loss on the tower outputs in workspace(B), in the place of the PPO loss.
         "ppo+demo": the clipped-surrogate loss on the first set_demo_rows() unsorted rows of the minibatch and the imitation
         loss (weight `demo_coeff`, critic weight `demo_value_coeff`, `label_smoothing`, no entropy term, mean over the
         demonstration rows) on the rest, in ONE launch (cadre_ppo_demo_loss).  Diagnostics, the KL gate, the adaptive lr and
         rank consensus work as in "ppo" and see the PPO rows only; a stopped step skips the whole update, the demonstration
         term included.  In device-hyper mode the two demo coefficients live in the block (set_hyper(demo_coeff=, ...)):
         a changed value needs no new graph.  None keeps the current coefficient.  The demo losses / statistics of a step are
-        in workspace(B)["demo_losses"] / ["demo_stats"].
-        "aux": the PPG auxiliary loss (cadre_aux_loss) — aux_value_coeff * 0.5 * mean (v - R)^2 + beta_clone * mean
-        KL(pi_old || pi), pi_old read from the table of set_aux_table() at the rows in workspace(B)["aux_rows"] (int64 [2][B]:
-        the table row of each UNSORTED minibatch row; a static tensor the caller fills before the update).  The learner's own
-        value_coeff / ent_coeff / clip are not used; actions, old_values, old_logp and adv are not read.  The two scalars go
-        by value, yet the mode IS available in device-hyper mode: it reads nothing from the block and changes nothing in it
-        (the optimiser step keeps reading lr / max_grad_norm there; the KL-adaptive controller lives in the PPO loss kernel
-        and does not run).  Refused while set_update_modes(stats / target_kl / consensus) is armed.  The statistics of a step
-        (hip.AUX_STATS_FIELDS per head) are in workspace(B)["aux_stats"].
-        "ppo+suggest": the clipped-surrogate loss plus, on the rows whose kind in workspace(B)["sug_kind"] (int32 [2][B] in
-        workspace order, a static tensor that cadre_suggest_rows fills before the update) is z >= 1, `suggest_coeff` times
-        KL(pi || prior z of the head) from the table of set_suggest_tables(), the mean taken over the minibatch rows
-        (cadre_ppo_sug_loss, ONE launch).  Diagnostics, the KL gate, the adaptive lr and rank consensus work as in "ppo" and
-        see what they see there.  In device-hyper mode the coefficient lives in the block (set_hyper(suggest_coeff=)): a
-        changed value needs no new graph.  None keeps the current coefficient.  The suggestion loss / statistics of a step
-        (hip.SUG_STATS_FIELDS per head) are in workspace(B)["sug_losses"] / ["sug_stats"].
-        "ppo+sil": the clipped-surrogate loss on the first set_sil_rows() unsorted rows of the minibatch and the
-        self-imitation terms on the rest — w = max(R - v, 0) with R from the `returns` column, `sil_coeff` * mean(-lp w) +
-        `sil_value_coeff` * mean(0.5 w^2) over the SIL rows — in ONE launch (cadre_ppo_sil_loss).  Diagnostics, the KL gate,
-        the adaptive lr and rank consensus work as in "ppo" and see the PPO rows only.  In device-hyper mode the two
-        coefficients live in the block (set_hyper(sil_coeff=, sil_value_coeff=)): a changed value needs no new graph.  None
-        keeps the current coefficient.  The SIL losses / statistics / per-row w of a step are in workspace(B)["sil_losses"] /
-        ["sil_stats"] / ["sil_w"] (static tensors, as the kinds in ["row_kind"]).
-        "ppo+smooth": the clipped-surrogate loss on the first set_smooth_rows() unsorted rows of the minibatch, the rest being
-        their successor rows (row t + 1 of the same storages), plus `smooth_coeff` * head_scale * mean over the pair slots of
-        d^2, d the difference of the two rows' mean controls (CAPS's temporal term; set_smooth_tables gives the control tables)
-        — in ONE launch (cadre_ppo_smooth_loss); the gradient goes into both rows of a pair.  Diagnostics, the KL gate, the
-        adaptive lr and rank consensus work as in "ppo" and see the PPO rows only, without the term.  In device-hyper mode
-        the coefficient lives in the block (set_hyper(smooth_coeff=)): a changed value needs no new graph.  None keeps the
-        current coefficient.  The pairs of a step are in workspace(B)["row_kind"] / ["mate"] (cadre_smooth_mates writes them
-        before the step), its smoothness loss / statistics / per-row d in ["smooth_losses"] / ["smooth_stats"] / ["smooth_d"].
-        "ppo+mask": the clipped-surrogate loss under action masks (cadre_ppo_am_loss, ONE launch where the PPO loss stands): a
-        row's word in workspace(B)["allowed"] (int64 [2][B] in workspace order, a static tensor that cadre_allowed_rows fills
-        before the update; bit k set: bin k may be chosen, no bit among the head's bins: unmasked) restricts the softmax, the
-        entropy and the gradient to the allowed bins; with every word unmasked the step is bit-identical to "ppo".  It has no
-        scalar of its own: diagnostics, the KL gate, the adaptive lr, device hyper-parameters, ordinal heads and rank
-        consensus work as in "ppo".  The mask statistics of a step (hip.AM_STATS_FIELDS per head) are in
-        workspace(B)["am_stats"]."""
-        if mode not in ("ppo", "bc", "ppo+demo", "aux", "ppo+suggest", "ppo+sil", "ppo+smooth", "ppo+mask"):
-            raise ValueError("set_loss: mode %r (known: 'ppo', 'bc', 'ppo+demo', 'aux', 'ppo+suggest', 'ppo+sil', 'ppo+smooth', "
-                             "'ppo+mask')" % (mode,))
-        if mode == "ppo+smooth":
-            if isinstance(smooth_coeff, bool):
-                raise ValueError("set_loss: smooth_coeff=%r" % (smooth_coeff,))
-            try:
-                sm = self._smooth_coeff if smooth_coeff is None else float(smooth_coeff)
-            except (TypeError, ValueError):
-                raise ValueError("set_loss: smooth_coeff=%r" % (smooth_coeff,))
-            if not np.isfinite(sm):
-                raise ValueError("set_loss: smooth_coeff=%r" % (smooth_coeff,))
-            self._smooth_coeff = sm
-            if self._hp_on:
-                self.set_hyper(smooth_coeff=sm)
-        if mode == "ppo+sil":
-            if any(isinstance(v, bool) for v in (sil_coeff, sil_value_coeff)):
-                raise ValueError("set_loss: sil_coeff=%r, sil_value_coeff=%r" % (sil_coeff, sil_value_coeff))
-            try:
-                sc = self._sil[0] if sil_coeff is None else float(sil_coeff)
-                svc = self._sil[1] if sil_value_coeff is None else float(sil_value_coeff)
-            except (TypeError, ValueError):
-                raise ValueError("set_loss: sil_coeff=%r, sil_value_coeff=%r" % (sil_coeff, sil_value_coeff))
-            if not (np.isfinite(sc) and np.isfinite(svc)):
-                raise ValueError("set_loss: sil_coeff=%r, sil_value_coeff=%r" % (sil_coeff, sil_value_coeff))
-            self._sil = (sc, svc)
-            if self._hp_on:
-                self.set_hyper(sil_coeff=sc, sil_value_coeff=svc)
-        if mode == "ppo+suggest":
-            if isinstance(suggest_coeff, bool):
-                raise ValueError("set_loss: suggest_coeff=%r" % (suggest_coeff,))
-            try:
-                sc = self._sug_coeff if suggest_coeff is None else float(suggest_coeff)
-            except (TypeError, ValueError):
-                raise ValueError("set_loss: suggest_coeff=%r" % (suggest_coeff,))
-            if not np.isfinite(sc):
-                raise ValueError("set_loss: suggest_coeff=%r" % (suggest_coeff,))
-            self._sug_coeff = sc
-            if self._hp_on:
-                self.set_hyper(suggest_coeff=sc)
-        if mode == "aux":
-            if any(isinstance(v, bool) for v in (beta_clone, aux_value_coeff)):
-                raise ValueError("set_loss: beta_clone=%r, aux_value_coeff=%r" % (beta_clone, aux_value_coeff))
-            try:
-                beta, avc = float(beta_clone), float(aux_value_coeff)
-            except (TypeError, ValueError):
-                raise ValueError("set_loss: beta_clone=%r, aux_value_coeff=%r" % (beta_clone, aux_value_coeff))
-            if not (np.isfinite(beta) and np.isfinite(avc)):
-                raise ValueError("set_loss: beta_clone=%r, aux_value_coeff=%r" % (beta_clone, aux_value_coeff))
-            self._check_aux_modes()
-            self._aux = (beta, avc)
-        if mode == "ppo+demo":
-            eps = float(label_smoothing)
-            dc = self._demo[1] if demo_coeff is None else float(demo_coeff)
-            dvc = self._demo[2] if demo_value_coeff is None else float(demo_value_coeff)
-            if not 0.0 <= eps < 1.0:
-                raise ValueError("set_loss: label_smoothing must be in [0, 1) (got %r)" % (label_smoothing,))
-            if not (np.isfinite(dc) and np.isfinite(dvc)):
-                raise ValueError("set_loss: demo_coeff=%r, demo_value_coeff=%r" % (demo_coeff, demo_value_coeff))
-            self._demo = (eps, dc, dvc)
-            if self._hp_on:
-                self.set_hyper(demo_coeff=dc, demo_value_coeff=dvc)
-        if mode == "bc":
-            eps, coeff = float(label_smoothing), float(bc_coeff)
-            if not 0.0 <= eps < 1.0:
-                raise ValueError("set_loss: label_smoothing must be in [0, 1) (got %r)" % (label_smoothing,))
-            if not np.isfinite(coeff):
-                raise ValueError("set_loss: bc_coeff=%r" % (bc_coeff,))
-            self._check_bc_modes()
-            self._bc = (eps, coeff)
-        self.loss_mode = mode
-
-    def set_demo_rows(self, B_ppo):
-        """"ppo+demo": unsorted rows 0 .. B_ppo - 1 of the next minibatches are PPO rows, the rest demonstration rows."""
-        if B_ppo is not None and int(B_ppo) < 0:
-            raise ValueError("set_demo_rows: B_ppo=%r" % (B_ppo,))
-        self._demo_rows = None if B_ppo is None else int(B_ppo)
-
-    def _demo_launch(self, w, B, inv_b, sorted_rows):
-        """cadre_mix_row_kinds + cadre_ppo_demo_loss on the tower outputs in workspace(B), in the place of the PPO loss."""
-        a, S = self.a, self.S
-        L, st = hip.lib(), hip.stream()
-        O3, dO3, NP = w["O3"], w["dO3"], a.NP
-        B_ppo = self._demo_rows
-        if B_ppo is None or B_ppo > B:
-            raise hip.CadreHipError("the 'ppo+demo' loss needs set_demo_rows(B_ppo) with 0 <= B_ppo <= B (got %r, B = %d)" % (B_ppo, B))
-        if "row_kind" not in w:
-            nblk = (B + 15) // 16
-            w["row_kind"] = torch.zeros(2, B, dtype=torch.int32, device=a.device)
-            w["demo_losses"] = torch.zeros(2, device=a.device)
-            w["demo_stats"] = torch.zeros(2, hip.BC_STATS_FIELDS, device=a.device)
-            w["demo_scratch"] = torch.zeros(2 * nblk * (2 + hip.BC_STATS_FIELDS), device=a.device)
-        hip.check(L.cadre_mix_row_kinds(hip.ptr(w["pos"]) if sorted_rows else None, B, B_ppo, hip.ptr(w["row_kind"]), st),
-                  "cadre_mix_row_kinds")
-        stats = self._loss_stats()
-        srow, sscr = self._stats_ws(w, B) if stats else (None, None)
-        eps, dc, dvc = self._demo
-        inv_bd = 1.0 / (B - B_ppo) if B > B_ppo else 1.0
-        ord_t = getattr(a, "ord", None)
-        hip.check(L.cadre_ppo_demo_loss(hip.ptr(O3), NP, 2 * B * NP, hip.ptr(O3[1]), NP, 2 * B * NP,
-                                        hip.ptr(w["actions"]), hip.ptr(w["commands"]), hip.ptr(w["old_values"]),
-                                        hip.ptr(w["returns"]), hip.ptr(w["old_logp"]), hip.ptr(w["adv"]),
-                                        hip.ptr(w["row_kind"]), B, a.C, a.n_out[0], a.n_out[1],
-                                        hip.ptr(self._hp) if self._hp_on else None, self.clip, self.vc, self.cc, self.ec, inv_b,
-                                        eps, dc, dvc, inv_bd, hip.ptr(w["losses"]), hip.ptr(w["demo_losses"]),
-                                        hip.ptr(dO3), hip.ptr(dO3[1]), hip.ptr(w["loss_scratch"]), hip.ptr(w["demo_scratch"]),
-                                        hip.ptr(w["sync"][a.Z * S:]), hip.ptr(srow), srow.shape[1] if stats else 0,
-                                        hip.ptr(sscr), self._loss_tkl(),
-                                        hip.ptr(self._stop) if (stats and self.target_kl is not None) else None,
-                                        hip.ptr(w["demo_stats"]), hip.BC_STATS_FIELDS, hip.ptr(ord_t), st),
-                  "cadre_ppo_demo_loss")
+        in workspace(B)["demo_losses"] / ["demo_stats"]."""
+        B_ppo = self._split(B)
+        self._demo_ws(w, B)
+        self._mix_kinds(w, B, B_ppo, sorted_rows)
+        p = hip.ptr
+        hip.check(hip.lib().cadre_ppo_demo_loss(
+            *self._row_args(w, B), p(w["row_kind"]), *self._scalar_args(B, inv_b), *self._demo, 1.0 / (B - B_ppo) if B > B_ppo else 1.0,
+            p(w["losses"]), p(w["demo_losses"]), *self._grad_args(w, "demo_scratch"), *self._stats_args(w, B), p(w["demo_stats"]),
+            hip.BC_STATS_FIELDS, p(self._ord()), hip.stream()), "cadre_ppo_demo_loss")
 
     # ------------------------------------------------------------------ self-imitation
-    def set_sil_rows(self, B_ppo):
-        """"ppo+sil": unsorted rows 0 .. B_ppo - 1 of the next minibatches are PPO rows, the rest SIL rows."""
-        if B_ppo is not None and int(B_ppo) < 0:
-            raise ValueError("set_sil_rows: B_ppo=%r" % (B_ppo,))
-        self._sil_rows = None if B_ppo is None else int(B_ppo)
-
     def _sil_ws(self, w, B):
         """The static tensors of the "ppo+sil" loss in workspace(B)."""
         if "sil_w" not in w:
@@ -315,41 +376,24 @@ class PPOLearnerHIP:
         return w["sil_w"]
 
     def _sil_launch(self, w, B, inv_b, sorted_rows):
-        """cadre_mix_row_kinds + cadre_ppo_sil_loss on the tower outputs in workspace(B), in the place of the PPO loss."""
-        a, S = self.a, self.S
-        L, st = hip.lib(), hip.stream()
-        O3, dO3, NP = w["O3"], w["dO3"], a.NP
-        B_ppo = self._sil_rows
-        if B_ppo is None or B_ppo > B:
-            raise hip.CadreHipError("the 'ppo+sil' loss needs set_sil_rows(B_ppo) with 0 <= B_ppo <= B (got %r, B = %d)" % (B_ppo, B))
+        """cadre_mix_row_kinds + cadre_ppo_sil_loss on the tower outputs in workspace(B), in the place of the PPO loss.
+        "ppo+sil": the clipped-surrogate loss on the first set_sil_rows() unsorted rows of the minibatch and the
+        self-imitation terms on the rest — w = max(R - v, 0) with R from the `returns` column, `sil_coeff` * mean(-lp w) +
+        `sil_value_coeff` * mean(0.5 w^2) over the SIL rows — in ONE launch (cadre_ppo_sil_loss).  Diagnostics, the KL gate,
+        the adaptive lr and rank consensus work as in "ppo" and see the PPO rows only.  In device-hyper mode the two
+        coefficients live in the block (set_hyper(sil_coeff=, sil_value_coeff=)): a changed value needs no new graph.  None
+        keeps the current coefficient.  The SIL losses / statistics / per-row w of a step are in workspace(B)["sil_losses"] /
+        ["sil_stats"] / ["sil_w"] (static tensors, as the kinds in ["row_kind"])."""
+        B_ppo = self._split(B)
         self._sil_ws(w, B)
-        hip.check(L.cadre_mix_row_kinds(hip.ptr(w["pos"]) if sorted_rows else None, B, B_ppo, hip.ptr(w["row_kind"]), st),
-                  "cadre_mix_row_kinds")
-        stats = self._loss_stats()
-        srow, sscr = self._stats_ws(w, B) if stats else (None, None)
-        sc, svc = self._sil
-        inv_bs = 1.0 / (B - B_ppo) if B > B_ppo else 1.0
-        ord_t = getattr(a, "ord", None)
-        hip.check(L.cadre_ppo_sil_loss(hip.ptr(O3), NP, 2 * B * NP, hip.ptr(O3[1]), NP, 2 * B * NP,
-                                       hip.ptr(w["actions"]), hip.ptr(w["commands"]), hip.ptr(w["old_values"]),
-                                       hip.ptr(w["returns"]), hip.ptr(w["old_logp"]), hip.ptr(w["adv"]),
-                                       hip.ptr(w["row_kind"]), B, a.C, a.n_out[0], a.n_out[1],
-                                       hip.ptr(self._hp) if self._hp_on else None, self.clip, self.vc, self.cc, self.ec, inv_b,
-                                       sc, svc, inv_bs, hip.ptr(w["losses"]), hip.ptr(w["sil_losses"]), hip.ptr(w["sil_w"]),
-                                       hip.ptr(dO3), hip.ptr(dO3[1]), hip.ptr(w["loss_scratch"]), hip.ptr(w["sil_scratch"]),
-                                       hip.ptr(w["sync"][a.Z * S:]), hip.ptr(srow), srow.shape[1] if stats else 0,
-                                       hip.ptr(sscr), self._loss_tkl(),
-                                       hip.ptr(self._stop) if (stats and self.target_kl is not None) else None,
-                                       hip.ptr(w["sil_stats"]), hip.SIL_STATS_FIELDS, hip.ptr(ord_t), st),
-                  "cadre_ppo_sil_loss")
+        self._mix_kinds(w, B, B_ppo, sorted_rows)
+        p = hip.ptr
+        hip.check(hip.lib().cadre_ppo_sil_loss(
+            *self._row_args(w, B), p(w["row_kind"]), *self._scalar_args(B, inv_b), *self._sil, 1.0 / (B - B_ppo) if B > B_ppo else 1.0,
+            p(w["losses"]), p(w["sil_losses"]), p(w["sil_w"]), *self._grad_args(w, "sil_scratch"), *self._stats_args(w, B),
+            p(w["sil_stats"]), hip.SIL_STATS_FIELDS, p(self._ord()), hip.stream()), "cadre_ppo_sil_loss")
 
     # ------------------------------------------------------------------ temporal smoothness
-    def set_smooth_rows(self, B_ppo):
-        """"ppo+smooth": unsorted rows 0 .. B_ppo - 1 of the next minibatches are PPO rows, the rest successor rows."""
-        if B_ppo is not None and int(B_ppo) < 0:
-            raise ValueError("set_smooth_rows: B_ppo=%r" % (B_ppo,))
-        self._smooth_rows = None if B_ppo is None else int(B_ppo)
-
     def set_smooth_tables(self, ctrl, head_scale=(1.0, 1.0)):
         """The control tables of the "ppo+smooth" loss: device float32 [2][64], contiguous, the control value of bin k of head h
         in [h][k] (cadre_amd.smooth.smooth_tables; None: forget them), and the two head scales (finite, >= 0).  The table's
@@ -382,29 +426,25 @@ class PPOLearnerHIP:
             w["smooth_scratch"] = torch.zeros(2 * nblk * hip.SMOOTH_STATS_FIELDS, device=dev)
         return w["row_kind"], w["mate"]
 
-    def _smooth_launch(self, w, B, inv_b):
-        """cadre_ppo_smooth_loss on the tower outputs in workspace(B), in the place of the PPO loss."""
-        a, S = self.a, self.S
-        O3, dO3, NP = w["O3"], w["dO3"], a.NP
-        B_ppo = self._smooth_rows
-        if B_ppo is None or not 0 < B_ppo < B:
-            raise hip.CadreHipError("the 'ppo+smooth' loss needs set_smooth_rows(B_ppo) with 0 < B_ppo < B (got %r, B = %d)" % (B_ppo, B))
-        if self._smooth_tables is None:
-            raise hip.CadreHipError("the 'ppo+smooth' loss needs set_smooth_tables(ctrl, head_scale) first")
-        ctrl, hs = self._smooth_tables
+    def _smooth_launch(self, w, B, inv_b, sorted_rows=False):
+        """cadre_ppo_smooth_loss on the tower outputs in workspace(B), in the place of the PPO loss.
+        "ppo+smooth": the clipped-surrogate loss on the first set_smooth_rows() unsorted rows of the minibatch, the rest being
+        their successor rows (row t + 1 of the same storages), plus `smooth_coeff` * head_scale * mean over the pair slots of
+        d^2, d the difference of the two rows' mean controls (CAPS's temporal term; set_smooth_tables gives the control tables)
+        — in ONE launch (cadre_ppo_smooth_loss); the gradient goes into both rows of a pair.  Diagnostics, the KL gate, the
+        adaptive lr and rank consensus work as in "ppo" and see the PPO rows only, without the term.  In device-hyper mode
+        the coefficient lives in the block (set_hyper(smooth_coeff=)): a changed value needs no new graph.  None keeps the
+        current coefficient.  The pairs of a step are in workspace(B)["row_kind"] / ["mate"] (cadre_smooth_mates writes them
+        before the step), its smoothness loss / statistics / per-row d in ["smooth_losses"] / ["smooth_stats"] / ["smooth_d"]."""
+        B_ppo = self._split(B)
+        ctrl, hs = self._table()
         self._smooth_ws(w, B)
-        stats = self._loss_stats()
-        srow, sscr = self._stats_ws(w, B) if stats else (None, None)
-        ord_t = getattr(a, "ord", None)
+        p = hip.ptr
         hip.check(hip.lib().cadre_ppo_smooth_loss(
-            hip.ptr(O3), NP, 2 * B * NP, hip.ptr(O3[1]), NP, 2 * B * NP, hip.ptr(w["actions"]), hip.ptr(w["commands"]),
-            hip.ptr(w["old_values"]), hip.ptr(w["returns"]), hip.ptr(w["old_logp"]), hip.ptr(w["adv"]), hip.ptr(w["row_kind"]),
-            hip.ptr(w["mate"]), hip.ptr(ctrl), B, a.C, a.n_out[0], a.n_out[1], hip.ptr(self._hp) if self._hp_on else None,
-            self.clip, self.vc, self.cc, self.ec, inv_b, self._smooth_coeff, hs[0], hs[1], 1.0 / (B - B_ppo), hip.ptr(w["losses"]),
-            hip.ptr(w["smooth_losses"]), hip.ptr(w["smooth_d"]), hip.ptr(dO3), hip.ptr(dO3[1]), hip.ptr(w["loss_scratch"]),
-            hip.ptr(w["smooth_scratch"]), hip.ptr(w["sync"][a.Z * S:]), hip.ptr(srow), srow.shape[1] if stats else 0,
-            hip.ptr(sscr), self._loss_tkl(), hip.ptr(self._stop) if (stats and self.target_kl is not None) else None,
-            hip.ptr(w["smooth_stats"]), hip.SMOOTH_STATS_FIELDS, hip.ptr(ord_t), hip.stream()), "cadre_ppo_smooth_loss")
+            *self._row_args(w, B), p(w["row_kind"]), p(w["mate"]), p(ctrl), *self._scalar_args(B, inv_b), self._smooth_coeff, hs[0],
+            hs[1], 1.0 / (B - B_ppo), p(w["losses"]), p(w["smooth_losses"]), p(w["smooth_d"]), *self._grad_args(w, "smooth_scratch"),
+            *self._stats_args(w, B), p(w["smooth_stats"]), hip.SMOOTH_STATS_FIELDS, p(self._ord()), hip.stream()),
+            "cadre_ppo_smooth_loss")
 
     # ------------------------------------------------------------------ exploration suggestions
     def set_suggest_tables(self, prior, Z=None):
@@ -433,30 +473,22 @@ class PPOLearnerHIP:
             w["sug_scratch"] = torch.zeros(2 * 4 * ((B + 15) // 16), device=dev)
         return w["sug_kind"]
 
-    def _sug_launch(self, w, B, inv_b):
-        """cadre_ppo_sug_loss on the tower outputs in workspace(B), in the place of the PPO loss."""
-        a, S = self.a, self.S
-        O3, dO3, NP = w["O3"], w["dO3"], a.NP
-        if self._sug_tables is None:
-            raise hip.CadreHipError("the 'ppo+suggest' loss needs set_suggest_tables(prior, Z) first")
-        prior, Z = self._sug_tables
+    def _sug_launch(self, w, B, inv_b, sorted_rows=False):
+        """cadre_ppo_sug_loss on the tower outputs in workspace(B), in the place of the PPO loss.
+        "ppo+suggest": the clipped-surrogate loss plus, on the rows whose kind in workspace(B)["sug_kind"] (int32 [2][B] in
+        workspace order, a static tensor that cadre_suggest_rows fills before the update) is z >= 1, `suggest_coeff` times
+        KL(pi || prior z of the head) from the table of set_suggest_tables(), the mean taken over the minibatch rows
+        (cadre_ppo_sug_loss, ONE launch).  Diagnostics, the KL gate, the adaptive lr and rank consensus work as in "ppo" and
+        see what they see there.  In device-hyper mode the coefficient lives in the block (set_hyper(suggest_coeff=)): a
+        changed value needs no new graph.  None keeps the current coefficient.  The suggestion loss / statistics of a step
+        (hip.SUG_STATS_FIELDS per head) are in workspace(B)["sug_losses"] / ["sug_stats"]."""
+        prior, Z = self._table()
         self._sug_ws(w, B)
-        ord_t = getattr(a, "ord", None)
-        if ord_t is None:
-            if self._sug_ord is None:
-                self._sug_ord = torch.full((2, 64), -1, dtype=torch.int32, device=a.device)
-            ord_t = self._sug_ord
-        stats = self._loss_stats()
-        srow, sscr = self._stats_ws(w, B) if stats else (None, None)
+        p = hip.ptr
         hip.check(hip.lib().cadre_ppo_sug_loss(
-            hip.ptr(O3), NP, 2 * B * NP, hip.ptr(O3[1]), NP, 2 * B * NP, hip.ptr(w["actions"]), hip.ptr(w["commands"]),
-            hip.ptr(w["old_values"]), hip.ptr(w["returns"]), hip.ptr(w["old_logp"]), hip.ptr(w["adv"]), hip.ptr(w["sug_kind"]),
-            hip.ptr(prior), Z, B, a.C, a.n_out[0], a.n_out[1], hip.ptr(self._hp) if self._hp_on else None, self.clip, self.vc,
-            self.cc, self.ec, inv_b, self._sug_coeff, hip.ptr(w["losses"]), hip.ptr(w["sug_losses"]), hip.ptr(dO3),
-            hip.ptr(dO3[1]), hip.ptr(w["loss_scratch"]), hip.ptr(w["sug_scratch"]), hip.ptr(w["sync"][a.Z * S:]), hip.ptr(srow),
-            srow.shape[1] if stats else 0, hip.ptr(sscr), self._loss_tkl(),
-            hip.ptr(self._stop) if (stats and self.target_kl is not None) else None, hip.ptr(w["sug_stats"]),
-            hip.SUG_STATS_FIELDS, hip.ptr(ord_t), hip.stream()), "cadre_ppo_sug_loss")
+            *self._row_args(w, B), p(w["sug_kind"]), p(prior), Z, *self._scalar_args(B, inv_b), self._sug_coeff, p(w["losses"]),
+            p(w["sug_losses"]), *self._grad_args(w, "sug_scratch"), *self._stats_args(w, B), p(w["sug_stats"]), hip.SUG_STATS_FIELDS,
+            p(self._ord(marker=True)), hip.stream()), "cadre_ppo_sug_loss")
 
     # ------------------------------------------------------------------ action masks
     def _am_ws(self, w, B):
@@ -475,24 +507,21 @@ class PPOLearnerHIP:
             self._sug_ord = torch.full((2, 64), -1, dtype=torch.int32, device=self.a.device)
         return self._sug_ord
 
-    def _am_launch(self, w, B, inv_b):
-        """cadre_ppo_am_loss on the tower outputs in workspace(B), in the place of the PPO loss."""
-        a, S = self.a, self.S
-        O3, dO3, NP = w["O3"], w["dO3"], a.NP
+    def _am_launch(self, w, B, inv_b, sorted_rows=False):
+        """cadre_ppo_am_loss on the tower outputs in workspace(B), in the place of the PPO loss.
+        "ppo+mask": the clipped-surrogate loss under action masks (cadre_ppo_am_loss, ONE launch where the PPO loss stands): a
+        row's word in workspace(B)["allowed"] (int64 [2][B] in workspace order, a static tensor that cadre_allowed_rows fills
+        before the update; bit k set: bin k may be chosen, no bit among the head's bins: unmasked) restricts the softmax, the
+        entropy and the gradient to the allowed bins; with every word unmasked the step is bit-identical to "ppo".  It has no
+        scalar of its own: diagnostics, the KL gate, the adaptive lr, device hyper-parameters, ordinal heads and rank
+        consensus work as in "ppo".  The mask statistics of a step (hip.AM_STATS_FIELDS per head) are in
+        workspace(B)["am_stats"]."""
         self._am_ws(w, B)
-        ord_t = getattr(a, "ord", None)
-        if ord_t is None:
-            ord_t = self.marker_ord()
-        stats = self._loss_stats()
-        srow, sscr = self._stats_ws(w, B) if stats else (None, None)
+        p = hip.ptr
         hip.check(hip.lib().cadre_ppo_am_loss(
-            hip.ptr(O3), NP, 2 * B * NP, hip.ptr(O3[1]), NP, 2 * B * NP, hip.ptr(w["actions"]), hip.ptr(w["commands"]),
-            hip.ptr(w["old_values"]), hip.ptr(w["returns"]), hip.ptr(w["old_logp"]), hip.ptr(w["adv"]), B, a.C, a.n_out[0],
-            a.n_out[1], hip.ptr(self._hp) if self._hp_on else None, self.clip, self.vc, self.cc, self.ec, inv_b,
-            hip.ptr(w["losses"]), hip.ptr(dO3), hip.ptr(dO3[1]), hip.ptr(w["loss_scratch"]), hip.ptr(w["sync"][a.Z * S:]),
-            hip.ptr(srow), srow.shape[1] if stats else 0, hip.ptr(sscr), self._loss_tkl(),
-            hip.ptr(self._stop) if (stats and self.target_kl is not None) else None, hip.ptr(ord_t), hip.ptr(w["allowed"]),
-            hip.ptr(w["am_stats"]), hip.AM_STATS_FIELDS, hip.ptr(w["am_scratch"]), hip.stream()), "cadre_ppo_am_loss")
+            *self._row_args(w, B), *self._scalar_args(B, inv_b), p(w["losses"]), *self._grad_args(w), *self._stats_args(w, B),
+            p(self._ord(marker=True)), p(w["allowed"]), p(w["am_stats"]), hip.AM_STATS_FIELDS, p(w["am_scratch"]), hip.stream()),
+            "cadre_ppo_am_loss")
 
     # ------------------------------------------------------------------ PPG auxiliary phase
     def set_aux_table(self, table):
@@ -512,8 +541,7 @@ class PPOLearnerHIP:
                                     "the learner section (call set_update_modes() first)")
 
     def _aux_args(self, w, B, sorted_rows):
-        if self._aux_table is None:
-            raise hip.CadreHipError("the 'aux' loss needs set_aux_table(table) first")
+        self._table()
         if "aux_rows" not in w:
             w["aux_rows"] = torch.zeros(2, B, dtype=torch.int64, device=self.a.device)
             w["aux_stats"] = torch.zeros(2, hip.AUX_STATS_FIELDS, device=self.a.device)
@@ -522,18 +550,21 @@ class PPOLearnerHIP:
 
     def _aux_launch(self, w, B, inv_b, sorted_rows):
         """cadre_aux_loss on the tower outputs in workspace(B): losses[3], the stats row aux_stats [2][AUX_STATS_FIELDS] and
-        dO3 (dlogits and dvalues)."""
-        a, S = self.a, self.S
-        O3, dO3, NP = w["O3"], w["dO3"], a.NP
+        dO3 (dlogits and dvalues).
+        "aux": the PPG auxiliary loss (cadre_aux_loss) — aux_value_coeff * 0.5 * mean (v - R)^2 + beta_clone * mean
+        KL(pi_old || pi), pi_old read from the table of set_aux_table() at the rows in workspace(B)["aux_rows"] (int64 [2][B]:
+        the table row of each UNSORTED minibatch row; a static tensor the caller fills before the update).  The learner's own
+        value_coeff / ent_coeff / clip are not used; actions, old_values, old_logp and adv are not read.  The two scalars go
+        by value, yet the mode IS available in device-hyper mode: it reads nothing from the block and changes nothing in it
+        (the optimiser step keeps reading lr / max_grad_norm there; the KL-adaptive controller lives in the PPO loss kernel
+        and does not run).  Refused while set_update_modes(stats / target_kl / consensus) is armed.  The statistics of a step
+        (hip.AUX_STATS_FIELDS per head) are in workspace(B)["aux_stats"]."""
+        a, p = self.a, hip.ptr
         pos, rows, table, R = self._aux_args(w, B, sorted_rows)
-        beta, avc = self._aux
-        ord_t = getattr(a, "ord", None)
-        hip.check(hip.lib().cadre_aux_loss(hip.ptr(O3), NP, 2 * B * NP, hip.ptr(O3[1]), NP, 2 * B * NP, hip.ptr(w["commands"]),
-                                           hip.ptr(w["returns"]), pos, rows, table, R, B, a.C, a.n_out[0], a.n_out[1], beta,
-                                           avc, inv_b, hip.ptr(w["losses"]), hip.ptr(dO3), hip.ptr(dO3[1]),
-                                           hip.ptr(w["loss_scratch"]), hip.ptr(w["sync"][a.Z * S:]), hip.ptr(w["aux_stats"]),
-                                           hip.AUX_STATS_FIELDS, hip.ptr(w["aux_scratch"]), hip.ptr(ord_t), hip.stream()),
-                  "cadre_aux_loss")
+        hip.check(hip.lib().cadre_aux_loss(
+            *self._tower_args(w, B), p(w["commands"]), p(w["returns"]), pos, rows, table, R, B, a.C, a.n_out[0], a.n_out[1],
+            *self._aux, inv_b, p(w["losses"]), *self._grad_args(w), p(w["aux_stats"]), hip.AUX_STATS_FIELDS, p(w["aux_scratch"]),
+            p(self._ord()), hip.stream()), "cadre_aux_loss")
 
     def aux_record(self, B, sorted_rows=False):
         """Forward only on the packed minibatch in workspace(B) (eagerly, no captured graph: the record pass runs once per
@@ -586,23 +617,23 @@ class PPOLearnerHIP:
             raise hip.CadreHipError("the imitation loss has no PPO diagnostics, KL gate or rank consensus: call "
                                     "set_update_modes() first")
 
-    def _bc_launch(self, w, B, inv_b, grad=True):
+    def _bc_launch(self, w, B, inv_b, sorted_rows=False, grad=True):
         """cadre_bc_loss on the tower outputs in workspace(B): losses[3], the stats row bc_stats [2][BC_STATS_FIELDS] and,
-        with `grad`, dO3 (dlogits and dvalues).  grad=False is the evaluation form."""
-        a, S = self.a, self.S
-        O3, dO3, NP = w["O3"], w["dO3"], a.NP
+        with `grad`, dO3 (dlogits and dvalues).  grad=False is the evaluation form.
+        "bc": behaviour cloning — cross-entropy against the demonstrated bin
+        (workspace `actions`; -1 = no label for that head) with `label_smoothing` in [0, 1) and weight `bc_coeff`, the critic
+        regressed on workspace `returns`, the learner's own value_coeff / ent_coeff, per-row weights from the `adv` slot;
+        old_values / old_logp are not read.  The imitation statistics of a step (hip.BC_STATS_FIELDS per head) are in
+        workspace(B)["bc_stats"].  By-value scalars only: refused together with the device-hyper block."""
+        a, p = self.a, hip.ptr
         if "bc_stats" not in w:
             w["bc_stats"] = torch.zeros(2, hip.BC_STATS_FIELDS, device=a.device)
             w["bc_scratch"] = torch.zeros(2 * hip.BC_STATS_FIELDS * ((B + 15) // 16), device=a.device)
-        eps, coeff = self._bc
-        ord_t = getattr(a, "ord", None)
-        hip.check(hip.lib().cadre_bc_loss(hip.ptr(O3), NP, 2 * B * NP, hip.ptr(O3[1]), NP, 2 * B * NP,
-                                          hip.ptr(w["actions"]), hip.ptr(w["commands"]), hip.ptr(w["returns"]), hip.ptr(w["adv"]),
-                                          B, a.C, a.n_out[0], a.n_out[1], eps, coeff, self.vc, self.ec, inv_b,
-                                          hip.ptr(w["losses"]), hip.ptr(dO3) if grad else None, hip.ptr(dO3[1]) if grad else None,
-                                          hip.ptr(w["loss_scratch"]), hip.ptr(w["sync"][a.Z * S:]), hip.ptr(w["bc_stats"]),
-                                          hip.BC_STATS_FIELDS, hip.ptr(w["bc_scratch"]), hip.ptr(ord_t), hip.stream()),
-                  "cadre_bc_loss")
+        dl, dv, scratch, sync = self._grad_args(w)
+        hip.check(hip.lib().cadre_bc_loss(
+            *self._tower_args(w, B), p(w["actions"]), p(w["commands"]), p(w["returns"]), p(w["adv"]), B, a.C, a.n_out[0], a.n_out[1],
+            *self._bc, self.vc, self.ec, inv_b, p(w["losses"]), dl if grad else None, dv if grad else None, scratch, sync,
+            p(w["bc_stats"]), hip.BC_STATS_FIELDS, p(w["bc_scratch"]), p(self._ord()), hip.stream()), "cadre_bc_loss")
 
     def bc_evaluate(self, B, inv_b, sorted_rows=False, stats_row=None):
         """Forward + the evaluation form of the imitation loss on the packed minibatch in workspace(B): no gradient is
@@ -689,35 +720,27 @@ class PPOLearnerHIP:
         key = key + ((("hp",),) if self._hp_on else ())
         key = key + ((("ord",),) if getattr(self.a, "ord", None) is not None else ())
         key = key + ((("consensus",),) if self.consensus else ())
-        # the imitation loss is a mode (("bc", label_smoothing, bc_coeff)): its graphs hold cadre_bc_loss and its scalars
-        key = key + ((("bc",) + self._bc,) if self.loss_mode == "bc" else ())
-        # the mixed loss is a mode: label_smoothing and B_ppo are by value always, the two coefficients unless they live in the
-        # block (device-hyper mode: a decaying coefficient replays one graph)
-        if self.loss_mode == "ppo+demo":
-            key = key + ((("demo", self._demo[0], self._demo_rows) + (() if self._hp_on else self._demo[1:])),)
-        # the auxiliary loss is a mode: both scalars by value, and the table's address and row count, which the graph holds
-        if self.loss_mode == "aux":
-            t = self._aux_table
-            key = key + ((("aux",) + self._aux + ((None, 0) if t is None else (t.data_ptr(), t.shape[1]))),)
-        # the suggestion loss is a mode: the prior table's address and Z, which the graph holds, and the coefficient unless it
-        # lives in the block
-        if self.loss_mode == "ppo+suggest":
-            t = self._sug_tables
-            key = key + ((("suggest",) + ((None, 0) if t is None else (t[0].data_ptr(), t[1])) +
-                          (() if self._hp_on else (self._sug_coeff,))),)
-        # the self-imitation loss is a mode: B_ppo by value always, the two coefficients unless they live in the block
-        if self.loss_mode == "ppo+sil":
-            key = key + ((("sil", self._sil_rows) + (() if self._hp_on else self._sil)),)
-        # the smoothness loss is a mode: B_ppo, the control table's address and the head scales by value always, the coefficient
-        # unless it lives in the block
-        if self.loss_mode == "ppo+smooth":
-            t = self._smooth_tables
-            key = key + ((("smooth", self._smooth_rows) + ((None,) if t is None else (t[0].data_ptr(),) + t[1]) +
-                          (() if self._hp_on else (self._smooth_coeff,))),)
-        # the masked loss is a mode without values: its graphs hold cadre_ppo_am_loss and the workspace's static tensors
-        if self.loss_mode == "ppo+mask":
-            key = key + (("mask",),)
-        return key
+        # a loss other than "ppo" is a mode: its graphs hold its launch and whatever that takes by value.  From its record: the
+        # tag; the scalars that go by value always (label_smoothing, the imitation and auxiliary coefficients); B_ppo; the table's
+        # address and R / Z / the head scales, which the graph holds; then the coefficients that can live in the block — unless
+        # they do (device-hyper mode: a decaying coefficient replays one graph).  A mode without values is its tag alone
+        m = LOSS_MODES[self.loss_mode]
+        if m.tag is None:
+            return key
+        vals = getattr(self, m.state) if m.scalars else ()
+        part = (m.tag,) + tuple(v for (_, field), v in zip(m.scalars, vals) if field is None)
+        part += (getattr(self, m.rows),) if m.rows else ()
+        if m.table:
+            t = getattr(self, m.table[0])
+            if t is None:
+                part += m.table[1]
+            elif isinstance(t, tuple):
+                part += (t[0].data_ptr(),) + (t[1] if isinstance(t[1], tuple) else (t[1],))
+            else:
+                part += (t.data_ptr(), t.shape[1])
+        if not self._hp_on:
+            part += tuple(v for (_, field), v in zip(m.scalars, vals) if field is not None)
+        return key + (part,)
 
     # ------------------------------------------------------------------ device-resident hyper-parameters
     def _drop_update_graphs(self, hp=False):
@@ -764,10 +787,8 @@ class PPOLearnerHIP:
         m = self._hp_host
         m[hip.HP["clip"]], m[hip.HP["value_coeff"]] = self._clip, self._vc
         m[hip.HP["clip_coeff"]], m[hip.HP["ent_coeff"]] = self._cc, self._ec
-        m[hip.HP_DEMO_COEFF], m[hip.HP_DEMO_VALUE_COEFF] = self._demo[1], self._demo[2]
-        m[hip.HP_SUGGEST_COEFF] = self._sug_coeff
-        m[hip.HP_SIL_COEFF], m[hip.HP_SIL_VALUE_COEFF] = self._sil
-        m[hip.HP_SMOOTH_COEFF] = self._smooth_coeff
+        for state, i, field in _HP_LOSS.values():
+            m[field] = getattr(self, state)[i]
         if np.isnan(m[hip.HP["lr"]]):
             m[hip.HP["lr"]] = 3e-4
         self._hp_on = True
@@ -797,10 +818,8 @@ class PPOLearnerHIP:
 
     @staticmethod
     def _hp_index(name):
-        """Block index of a named field: hip.HP_INDEX, or one of the fields a single loss kernel reads."""
-        own = dict(suggest_coeff=hip.HP_SUGGEST_COEFF, sil_coeff=hip.HP_SIL_COEFF, sil_value_coeff=hip.HP_SIL_VALUE_COEFF,
-                   smooth_coeff=hip.HP_SMOOTH_COEFF)
-        return own[name] if name in own else hip.HP_INDEX[name]
+        """Block index of a named field: a loss coefficient's from its mode's record, every other from hip.HP."""
+        return _HP_LOSS[name][2] if name in _HP_LOSS else hip.HP[name]
 
     def _need_hp(self, what):
         if not self._hp_on:
@@ -816,11 +835,8 @@ class PPOLearnerHIP:
         suggest_coeff: the coefficient of the "ppo+suggest" loss (read by cadre_ppo_sug_loss only).
         sil_coeff / sil_value_coeff: the two coefficients of the "ppo+sil" loss (read by cadre_ppo_sil_loss only).
         smooth_coeff: the coefficient of the "ppo+smooth" loss (read by cadre_ppo_smooth_loss only)."""
+        new = {k: v for k, v in locals().items() if k != "self"}
         self._need_hp("set_hyper")
-        new = dict(lr=lr, clip=clip, ent_coeff=ent_coeff, value_coeff=value_coeff, clip_coeff=clip_coeff,
-                   max_grad_norm=max_grad_norm, demo_coeff=demo_coeff, demo_value_coeff=demo_value_coeff,
-                   suggest_coeff=suggest_coeff, sil_coeff=sil_coeff, sil_value_coeff=sil_value_coeff,
-                   smooth_coeff=smooth_coeff)
         idx = []
         for name, v in new.items():
             if v is None:
@@ -836,10 +852,9 @@ class PPOLearnerHIP:
         m = self._hp_host
         self._clip, self._vc = float(m[hip.HP["clip"]]), float(m[hip.HP["value_coeff"]])
         self._cc, self._ec = float(m[hip.HP["clip_coeff"]]), float(m[hip.HP["ent_coeff"]])
-        self._demo = (self._demo[0], float(m[hip.HP_DEMO_COEFF]), float(m[hip.HP_DEMO_VALUE_COEFF]))
-        self._sug_coeff = float(m[hip.HP_SUGGEST_COEFF])
-        self._sil = (float(m[hip.HP_SIL_COEFF]), float(m[hip.HP_SIL_VALUE_COEFF]))
-        self._smooth_coeff = float(m[hip.HP_SMOOTH_COEFF])
+        for state, i, field in _HP_LOSS.values():
+            vals = getattr(self, state)
+            setattr(self, state, vals[:i] + (float(m[field]),) + vals[i + 1:])
         if any(hip.HP["clip"] <= i <= hip.HP["ent_coeff"] for i in idx):
             self._hp_moved = True
         if idx:
@@ -1064,17 +1079,14 @@ class PPOLearnerHIP:
         [2][>= hip.BC_STATS_FIELDS]) receives the imitation statistics of the demonstration rows; `stats_row` keeps its
         meaning there (the diagnostics of the PPO rows)."""
         a = self.a
-        bc = self.loss_mode == "bc"
+        m = LOSS_MODES[self.loss_mode]
         if demo_stats_row is not None and self.loss_mode != "ppo+demo":
             raise hip.CadreHipError("update(demo_stats_row=...) needs set_loss('ppo+demo')")
-        if bc:
-            self._check_bc_modes()
-        aux = self.loss_mode == "aux"
-        if aux:
-            self._check_aux_modes()
-            if self._aux_table is None:
-                raise hip.CadreHipError("the 'aux' loss needs set_aux_table(table) first")
-        if stats_row is not None and not bc and not aux and not self._loss_stats():
+        if m.check:
+            getattr(self, m.check)()
+        if self.loss_mode == "aux":                      # (the record pass shares the refusal: before anything is enqueued)
+            self._table()
+        if stats_row is not None and m.ppo and not self._loss_stats():
             raise hip.CadreHipError("update(stats_row=...) needs set_update_modes(stats=True) (or a target_kl)")
         # The packed W_hh copies are current iff this learner's own fused optimiser step produced the parameters that are
         # in the arena now (a chief in another process, a broadcast or a checkpoint load change them behind our back: then
@@ -1102,19 +1114,14 @@ class PPOLearnerHIP:
         w = self.workspace(B)
         if demo_stats_row is not None:
             demo_stats_row[:, :hip.BC_STATS_FIELDS].copy_(w["demo_stats"])
-        if self.loss_mode == "bc":            # the imitation statistics; no gradient norms follow
+        m = LOSS_MODES[self.loss_mode]
+        if m.own_stats:                       # the mode's own statistics (imitation, auxiliary); no gradient norms follow
             if stats_row is not None:
-                stats_row[:, :hip.BC_STATS_FIELDS].copy_(w["bc_stats"])
-            return w["losses"]
-        if self.loss_mode == "aux":           # the auxiliary statistics; no gradient norms follow
-            if stats_row is not None:
-                stats_row[:, :hip.AUX_STATS_FIELDS].copy_(w["aux_stats"])
+                stats_row[:, :m.own_stats[1]].copy_(w[m.own_stats[0]])
             return w["losses"]
         self._last_stats = w.get("stats")
-        if self.loss_mode == "ppo+suggest":
-            self._last_sug_stats = w.get("sug_stats")
-        if self.loss_mode == "ppo+mask":
-            self._last_am_stats = w.get("am_stats")
+        if m.last_stats:
+            setattr(self, m.last_stats[0], w.get(m.last_stats[1]))
         if stats_row is not None:
             stats_row.copy_(w["stats"])
             self._norm_row = stats_row
@@ -1173,26 +1180,22 @@ class PPOLearnerHIP:
                 gc.enable()
         return g
 
-    def _ppo_launch(self, w, B, inv_b, ord_t):
+    def _ppo_launch(self, w, B, inv_b, sorted_rows=False):
         """The PPO-loss launch of the plain, stats, device-hyper and ordinal modes: entry point and arguments from the flags.
         cadre_ppo_loss[_stats][_hp] take the block OR the four scalars, and the stats arguments only as `_stats`;
         cadre_ppo_loss_ord takes all of them (hp NULL = by-value scalars, stats row NULL = no diagnostics) and the rank table."""
-        a, S = self.a, self.S
-        Z, NP, O3, dO3 = a.Z, a.NP, w["O3"], w["dO3"]
-        hp, stats, ordinal = self._hp_on, self._loss_stats(), ord_t is not None
+        hp, stats, ord_t = self._hp_on, self._loss_stats(), self._ord()
+        ordinal = ord_t is not None
         name = "cadre_ppo_loss_ord" if ordinal else "cadre_ppo_loss%s%s" % ("_stats" if stats else "", "_hp" if hp else "")
-        srow, sscr = self._stats_ws(w, B) if stats else (None, None)
-        args = (hip.ptr(O3), NP, 2 * B * NP, hip.ptr(O3[1]), NP, 2 * B * NP,
-                hip.ptr(w["actions"]), hip.ptr(w["commands"]), hip.ptr(w["old_values"]),
-                hip.ptr(w["returns"]), hip.ptr(w["old_logp"]), hip.ptr(w["adv"]), B, a.C, a.n_out[0], a.n_out[1])
+        scal = self._scalar_args(B, inv_b)               # (B, C, K0, K1 | block | clip, vc, cc, ec | inv_b)
+        args = self._row_args(w, B) + scal[:4]
         if hp or ordinal:
-            args += (hip.ptr(self._hp) if hp else None,)
+            args += scal[4:5]
         if ordinal or not hp:
-            args += (self.clip, self.vc, self.cc, self.ec)
-        args += (inv_b, hip.ptr(w["losses"]), hip.ptr(dO3), hip.ptr(dO3[1]), hip.ptr(w["loss_scratch"]), hip.ptr(w["sync"][Z * S:]))
+            args += scal[5:9]
+        args += (inv_b, hip.ptr(w["losses"])) + self._grad_args(w)
         if stats or ordinal:
-            args += (hip.ptr(srow), srow.shape[1] if stats else 0, hip.ptr(sscr), self._loss_tkl(),
-                     hip.ptr(self._stop) if (stats and self.target_kl is not None) else None)
+            args += self._stats_args(w, B)
         if ordinal:
             args += (hip.ptr(ord_t),)
         hip.check(getattr(hip.lib(), name)(*args, hip.stream()), name)
@@ -1216,23 +1219,8 @@ class PPOLearnerHIP:
         O3, dO3 = w["O3"], w["dO3"]
         if front:
             self._forward(w, B, (0, 1, Z), C, seg=seg, fused_mlp=True)
-        ord_t = getattr(a, "ord", None)                 # ordinal policy heads: the rank table (static, like every pointer here)
-        if front and self.loss_mode == "bc":
-            self._bc_launch(w, B, inv_b)                # the imitation loss writes losses, dO3: the rest is indifferent
-        elif front and self.loss_mode == "ppo+demo":
-            self._demo_launch(w, B, inv_b, sorted_rows)  # PPO rows + demonstration rows: two launches, the rest is indifferent
-        elif front and self.loss_mode == "aux":
-            self._aux_launch(w, B, inv_b, sorted_rows)  # critic + KL clone against the recorded table: the rest is indifferent
-        elif front and self.loss_mode == "ppo+sil":
-            self._sil_launch(w, B, inv_b, sorted_rows)   # PPO rows + self-imitation rows: two launches, the rest is indifferent
-        elif front and self.loss_mode == "ppo+smooth":
-            self._smooth_launch(w, B, inv_b)            # PPO rows + their successor rows, coupled in pairs: the rest is indifferent
-        elif front and self.loss_mode == "ppo+suggest":
-            self._sug_launch(w, B, inv_b)               # PPO + the event priors on marked rows: the rest is indifferent
-        elif front and self.loss_mode == "ppo+mask":
-            self._am_launch(w, B, inv_b)                # PPO under the rows' allowed-bin words: the rest is indifferent
-        elif front:
-            self._ppo_launch(w, B, inv_b, ord_t)
+        if front:   # the selected loss writes losses and dO3 (one launch, two with a row split to place): the rest is indifferent
+            getattr(self, LOSS_MODES[self.loss_mode].launch)(w, B, inv_b, sorted_rows)
         # ---------------- backward: MLP towers (16 = 2Z batched)
         Gr = a.grads
         pP, gP = a.params[a.P0:], Gr[a.P0:]

@@ -8,7 +8,7 @@ import numpy as np
 import torch
 
 from .. import hip
-from ..learner import PPOLearnerHIP
+from ..learner import LOSS_MODES, PPOLearnerHIP
 from .models import LSTM, Model, _cfg, arena_of, create_model, get_vae_output, ordinal_rank, resolve_ordinal  # noqa: F401
 
 
@@ -624,18 +624,14 @@ class CadreAgent(object):
                 raise ValueError("update_policy_from_storages: actmask excludes demo, sil, smooth and evaluate (their kernels do "
                                  "not read the rows' allowed-bin words yet)")
             lrn = self.learner
-            prev = lrn.loss_mode
-            if prev not in ("ppo", "ppo+mask"):
+            if lrn.loss_mode not in ("ppo", "ppo+mask"):
                 raise ValueError("update_policy_from_storages: actmask with the learner's loss set to %r (its kernel does not "
-                                 "read the rows' allowed-bin words yet)" % (prev,))
-            lrn.set_loss("ppo+mask")
-            try:
+                                 "read the rows' allowed-bin words yet)" % (lrn.loss_mode,))
+            with lrn.loss_scope("ppo+mask"):
                 out = self._update_from_storages(batches, sync, mlp_grads_ready, stats_row, False)
                 if hasattr(actmask, "step"):
                     actmask.step(lrn)
                 return out
-            finally:
-                lrn.loss_mode = prev
         if smooth is not None:
             if evaluate or demo or sil:
                 raise ValueError("update_policy_from_storages: successor rows have no evaluation form and exclude demo and sil "
@@ -651,19 +647,16 @@ class CadreAgent(object):
                     raise ValueError("update_policy_from_storages: successor entry %d does not carry the storages and advantages "
                                      "of worker %d" % (k, (rotation + k) % nW))
             lrn = self.learner
-            prev = (lrn.loss_mode, lrn._smooth_rows)
-            lrn.set_loss("ppo+smooth")
-            lrn.set_smooth_rows(nW * batches[0][1].numel())
-            self._smooth_step = (nW, E, rotation)
-            try:
-                out = self._update_from_storages(list(batches) + list(entries), sync, mlp_grads_ready, stats_row, False)
-                if smooth_stats_row is not None:
-                    B = (nW + E) * batches[0][1].numel()
-                    smooth_stats_row[:, :hip.SMOOTH_STATS_FIELDS].copy_(lrn.workspace(B)["smooth_stats"])
-                return out
-            finally:
-                lrn.loss_mode, lrn._smooth_rows = prev
-                self._smooth_step = None
+            with lrn.loss_scope("ppo+smooth", rows=nW * batches[0][1].numel()):
+                self._smooth_step = (nW, E, rotation)
+                try:
+                    out = self._update_from_storages(list(batches) + list(entries), sync, mlp_grads_ready, stats_row, False)
+                    if smooth_stats_row is not None:
+                        B = (nW + E) * batches[0][1].numel()
+                        smooth_stats_row[:, :hip.SMOOTH_STATS_FIELDS].copy_(lrn.workspace(B)["smooth_stats"])
+                    return out
+                finally:
+                    self._smooth_step = None
         if smooth_stats_row is not None:
             raise ValueError("update_policy_from_storages: smooth_stats_row without smooth entries")
         if sil:
@@ -671,42 +664,29 @@ class CadreAgent(object):
                 raise ValueError("update_policy_from_storages: sil rows have no evaluation form and exclude demo rows "
                                  "(a row carries one kind array)")
             lrn = self.learner
-            prev = (lrn.loss_mode, lrn._sil_rows)
-            lrn.set_loss("ppo+sil")
-            lrn.set_sil_rows(len(batches) * batches[0][1].numel())
-            try:
+            with lrn.loss_scope("ppo+sil", rows=len(batches) * batches[0][1].numel()):
                 out = self._update_from_storages(list(batches) + list(sil), sync, mlp_grads_ready, stats_row, False)
                 if sil_stats_row is not None:
                     B = (len(batches) + len(sil)) * batches[0][1].numel()
                     sil_stats_row[:, :hip.SIL_STATS_FIELDS].copy_(lrn.workspace(B)["sil_stats"])
                 return out
-            finally:
-                lrn.loss_mode, lrn._sil_rows = prev
         if sil_stats_row is not None:
             raise ValueError("update_policy_from_storages: sil_stats_row without sil entries")
         if demo:
             if evaluate:
                 raise ValueError("update_policy_from_storages: demo rows have no evaluation form here (imitate_from_storages(evaluate=True))")
-            lrn = self.learner
-            prev = (lrn.loss_mode, lrn._demo, lrn._demo_rows)
-            n_ppo = len(batches) * batches[0][1].numel()
-            lrn.set_loss("ppo+demo", lrn._demo[0] if demo_label_smoothing is None else demo_label_smoothing,
-                         demo_coeff=demo_coeff, demo_value_coeff=demo_value_coeff)
-            lrn.set_demo_rows(n_ppo)
-            try:
+            with self.learner.loss_scope("ppo+demo", rows=len(batches) * batches[0][1].numel(), label_smoothing=demo_label_smoothing,
+                                         demo_coeff=demo_coeff, demo_value_coeff=demo_value_coeff):
                 return self._update_from_storages(list(batches) + list(demo), sync, mlp_grads_ready, stats_row, False,
                                                   demo_stats_row)
-            finally:
-                lrn.loss_mode, lrn._demo_rows = prev[0], prev[2]
-                if not lrn.device_hyper:
-                    lrn._demo = prev[1]
         if demo_stats_row is not None:
             raise ValueError("update_policy_from_storages: demo_stats_row without demo entries")
         return self._update_from_storages(batches, sync, mlp_grads_ready, stats_row, evaluate)
 
     def _update_from_storages(self, batches, sync, mlp_grads_ready, stats_row, evaluate, demo_stats_row=None, record=None):
         nW = len(batches)
-        if (record is None and not evaluate and self.learner.loss_mode in ("ppo", "ppo+demo", "ppo+suggest", "ppo+sil", "ppo+smooth")
+        mode = LOSS_MODES[self.learner.loss_mode]
+        if (record is None and not evaluate and mode.ppo and not mode.reads_allowed
                 and any(getattr(b[k], "allowed", None) is not None for b in batches for k in (0, 3))):
             raise ValueError("update_policy_from_storages: a storage of this step carries `allowed` words (its actions were sampled "
                              "under action masks) but the loss is %r, which does not read them: old_logp would belong to another "
@@ -744,7 +724,7 @@ class CadreAgent(object):
         if any((st_._ldo, st_.seq_length, st_._ldh) != geo for b in batches for st_ in (b[0], b[3])):
             # storages of different geometry (feature pitch / window length): one gather launch per storage with its
             # own strides (cadre_gather_minibatch) — the one-launch table below assumes a single geometry
-            if self.learner.loss_mode in ("ppo+suggest", "ppo+smooth", "ppo+mask"):
+            if mode.one_geometry:
                 raise ValueError("the %r loss needs storages of one geometry: the kinds of the minibatch are placed "
                                  "by one launch beside the one-launch gather" % (self.learner.loss_mode,))
             self._gather_entry = "cadre_gather_minibatch_ft" if ft else "cadre_gather_minibatch"
@@ -923,29 +903,10 @@ class CadreAgent(object):
         `label_smoothing` / `bc_coeff`: None keeps the learner's current imitation settings.  `stats_row`: device float32
         [2][>= hip.BC_STATS_FIELDS] that receives the step's imitation statistics (accuracy, NLL, entropy, |v - R|, weight
         sum, rows counted).  `evaluate`: the evaluation form — losses and statistics only, no gradient, nothing moves."""
-        lrn = self.learner
-        prev = (lrn.loss_mode,) + lrn._bc
-        eps, coeff = lrn._bc
-        lrn.set_loss("bc", eps if label_smoothing is None else label_smoothing, coeff if bc_coeff is None else bc_coeff)
-        try:
+        with self.learner.loss_scope("bc", label_smoothing=label_smoothing, bc_coeff=bc_coeff):
             return self.update_policy_from_storages(batches, sync=sync, stats_row=stats_row, evaluate=bool(evaluate))
-        finally:
-            lrn.loss_mode, lrn._bc = prev[0], prev[1:]
 
     # ------------------------------------------------------------------ PPG auxiliary phase (cadre_amd.phasic)
-    def _aux_mode(self, table, beta_clone=None, value_coeff=None):
-        """Switch the learner to the auxiliary loss on `table`; returns what `finally` needs to put the old mode back."""
-        lrn = self.learner
-        prev = (lrn.loss_mode, lrn._aux, lrn._aux_table)
-        try:
-            lrn.set_aux_table(table)
-            lrn.set_loss("aux", beta_clone=lrn._aux[0] if beta_clone is None else beta_clone,
-                         aux_value_coeff=lrn._aux[1] if value_coeff is None else value_coeff)
-        except Exception:
-            lrn.loss_mode, lrn._aux, lrn._aux_table = prev
-            raise
-        return prev
-
     @staticmethod
     def _aux_entry(entry):
         if len(entry) != 1:
@@ -960,12 +921,8 @@ class CadreAgent(object):
         device float32 [2][R][64] with R >= every index + 1 (AuxBuffer.table).  Nothing moves; the loss mode that was
         selected before is restored on exit."""
         batches = self._aux_entry(entry)
-        prev = self._aux_mode(table)
-        lrn = self.learner
-        try:
+        with self.learner.loss_scope("aux", table=table, beta_clone=None, aux_value_coeff=None):
             return self._update_from_storages(batches, False, None, None, True)
-        finally:
-            lrn.loss_mode, lrn._aux, lrn._aux_table = prev
 
     def aux_from_storages(self, entry, table, stats_row=None, sync=True, beta_clone=None, value_coeff=None):
         """One step of the auxiliary phase on the ONE entry `entry` (as in aux_record_from_storages): the update's launch
@@ -975,12 +932,8 @@ class CadreAgent(object):
         None keeps the learner's current settings.  `stats_row`: device float32 [2][>= hip.AUX_STATS_FIELDS] that receives
         the step's statistics (mean KL, max KL, |v - R|, entropy, (v - R)^2, rows counted).  Returns (value term, KL term, 0)."""
         batches = self._aux_entry(entry)
-        prev = self._aux_mode(table, beta_clone, value_coeff)
-        lrn = self.learner
-        try:
+        with self.learner.loss_scope("aux", table=table, beta_clone=beta_clone, aux_value_coeff=value_coeff):
             return self._update_from_storages(batches, sync, None, stats_row, False)
-        finally:
-            lrn.loss_mode, lrn._aux, lrn._aux_table = prev
 
     # ------------------------------------------------------------------ sample reuse (cadre_amd.reuse)
     def reuse_record_from_storages(self, entry, logp_now, value_now):

@@ -378,8 +378,15 @@ def _check_actmask(actmask, demo, suggest, reuse, sil, smooth, fused_gather=True
                           sample_reuse=reuse)
 
 
+def _loss_end(agent, *tokens):
+    """The learner's loss as it was before _suggest_begin / _actmask_begin switched it (None: that one did not)."""
+    for token in tokens:
+        if token is not None:
+            agent.learner.loss_restore(token)
+
+
 def _actmask_begin(agent, actmask, stats, steps):
-    """The learner's loss becomes "ppo+mask" for the section.  Returns the loss mode to restore (None without masks)."""
+    """The learner's loss becomes "ppo+mask" for the section.  Returns what _loss_end takes (None without masks)."""
     if actmask is None:
         return None
     return actmask.begin(agent.learner, steps if stats is not None else 0)
@@ -406,7 +413,7 @@ def apply_suggest(agent, suggest, episode, max_episode):
 
 def _suggest_begin(agent, suggest, storages, stats, steps):
     """After the storages of a section are finished: the mark launch, then the learner's loss becomes "ppo+suggest" for the
-    section.  Returns the loss mode to restore (None without suggestions)."""
+    section.  Returns what _loss_end takes (None without suggestions)."""
     if suggest is None:
         return None
     suggest.mark(storages)
@@ -926,10 +933,7 @@ def _learner_section(agent, steer_rollout, throttle_rollout, done, train_cfg, sh
                               optimizer, traffic_light, counter, shared_model_list, in_process_chief, fused_gather,
                               losses_on_device, step_events, sec, lr, demo, episode, reuse, suggest, sil, smooth, actmask)
     finally:
-        if suggest is not None:
-            agent.learner.loss_mode = sug_prev
-        if actmask is not None:
-            agent.learner.loss_mode = am_prev
+        _loss_end(agent, sug_prev, am_prev)
 
 
 def _learner_steps(agent, steer_rollout, throttle_rollout, steer_adv, throttle_adv, train_cfg, shared_grad_buffers, optimizer,
@@ -1236,10 +1240,7 @@ def learner_section_multi(agent, rollouts, dones, train_cfg, shared_grad_buffers
     finally:
         if sec is not None:
             agent.learner.set_update_modes()
-        if sug_prev is not None:
-            agent.learner.loss_mode = sug_prev
-        if am_prev is not None:
-            agent.learner.loss_mode = am_prev
+        _loss_end(agent, sug_prev, am_prev)
     _curiosity_end(stats, curiosity)
     losses = torch.stack(dev_losses)
     if sec is not None and not losses_on_device:

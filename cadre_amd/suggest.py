@@ -195,10 +195,10 @@ class Suggestions(object):
         RolloutStorage.mark_suggestions(storages, self.Z, self.horizon)
 
     def begin(self, learner, steps=0):
-        """Switch the learner's loss for the section; `steps` > 0: collect the suggestion statistics of that many steps."""
+        """Switch the learner's loss for the section; `steps` > 0: collect the suggestion statistics of that many steps.  Returns
+        what learner.loss_restore takes."""
         learner.set_suggest_tables(self.prior, self.Z)
-        prev = learner.loss_mode
-        learner.set_loss("ppo+suggest")
+        prev = learner.loss_begin("ppo+suggest")
         self._n = 0
         if steps:
             if self._rows is None or self._rows.shape[0] < steps:

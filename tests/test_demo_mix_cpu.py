@@ -274,3 +274,14 @@ def test_learner_modes_without_a_device():
         lrn.set_loss("demo")
     with pytest.raises(ValueError):
         lrn.set_demo_rows(-1)
+
+
+@pytest.mark.parametrize("kw", [dict(demo_coeff=True), dict(demo_value_coeff=False)])
+def test_set_loss_refuses_a_bool_demo_coefficient(kw):
+    """The coefficient check is one for every loss mode: a bool is refused (it used to count as 1.0 / 0.0 here)."""
+    from cadre_amd.learner import PPOLearnerHIP
+    lrn = PPOLearnerHIP.__new__(PPOLearnerHIP)
+    lrn._hp_on, lrn._demo, lrn.loss_mode = False, (0.0, 0.5, 0.25), "ppo"
+    with pytest.raises(ValueError, match="set_loss: demo_coeff=.*, demo_value_coeff="):
+        lrn.set_loss("ppo+demo", **kw)
+    assert lrn._demo == (0.0, 0.5, 0.25) and lrn.loss_mode == "ppo"

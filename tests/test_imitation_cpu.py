@@ -402,3 +402,13 @@ def test_pretrain_key_is_refused_where_the_warm_start_would_be_lost():
         train_mod._pretrain(agent, cfg, rc, None, 0, None, None, {"n": Net(object())})
     assert train_mod._pretrain(agent, dict(pretrain=None), rc, None, 0, None, None, {"n": Net(object())}, object()) is None
     assert train_mod._pretrain(agent, cfg, rc, None, 0, None, "ckpt.pt", {"n": Net(object())}, object()) is None
+
+
+def test_set_loss_refuses_a_bool_bc_coefficient():
+    """The coefficient check is one for every loss mode: a bool is refused (it used to count as 1.0 here)."""
+    from cadre_amd.learner import PPOLearnerHIP
+    lrn = PPOLearnerHIP.__new__(PPOLearnerHIP)
+    lrn._hp_on, lrn._bc, lrn.loss_mode = False, (0.0, 1.0), "ppo"
+    with pytest.raises(ValueError, match="set_loss: bc_coeff=True"):
+        lrn.set_loss("bc", bc_coeff=True)
+    assert lrn._bc == (0.0, 1.0) and lrn.loss_mode == "ppo"

@@ -731,3 +731,47 @@ def test_get_values_equals_per_worker_get_value():
         assert got_dev[i][0].shape == (1, 1) and torch.equal(got_dev[i][0], gs) and torch.equal(got_dev[i][1], gt)
     assert abs(float(one_dev[0]) - float(want[2][0])) <= 1e-6 * max(1.0, abs(float(want[2][0])))
     assert abs(float(one_dev[1]) - float(want[2][1])) <= 1e-6 * max(1.0, abs(float(want[2][1])))
+
+
+@pytest.mark.parametrize("B", [64, 32])
+def test_scoped_loss_switch_leaves_the_captured_ppo_graph_alone(B):
+    """A loss borrowed for one call (PPOLearnerHIP.loss_scope) and the captured graphs: after a scoped "ppo+sil" step and a
+    scoped "ppo+mask" step on the same workspace, the plain update is a replay of the graph it had (no new key, no launch from
+    the host), gives the same bits and finds the learner's loss attributes as they were.  B = 64 (SORT_MIN_B) takes the sorted
+    path, B = 32 the unsorted one."""
+    from cadre_amd import hip
+    from ppo_agent.storage import RolloutStorage
+    agent = make_agent(84, 84)
+    lrn = agent.learner
+    srt = lrn.sorted_rows(B)
+    assert srt == (B == 64)
+    data, pair = fill_storages(2 * B, 900 + B), []
+    for hd in ("steer", "throttle"):
+        s = RolloutStorage(2 * B, 2, 530, 8, 530, True, 0.99, 0.95)
+        for k, v in data[hd].items():
+            getattr(s, k).copy_(torch.from_numpy(v))
+        s.to("cuda:0")
+        s.compute_returns(torch.tensor([0.05]))
+        pair.append(s)
+    idx = [torch.randperm(2 * B, generator=torch.Generator().manual_seed(3))[:B] for _ in range(2)]
+    agent.update_policy_from_storages([(pair[0], idx[0], pair[0].advantages, pair[1], idx[1], pair[1].advantages)], sync=False)
+    for _ in range(2):                                   # the second run captures, the third replays
+        losses = lrn.update(B, 1.0 / B, sorted_rows=srt)
+    attrs = ("loss_mode", "_bc", "_demo", "_demo_rows", "_sil", "_sil_rows", "_smooth_coeff", "_smooth_rows", "_smooth_tables",
+             "_sug_coeff", "_sug_tables", "_aux", "_aux_table")
+    graphs, state = dict(lrn._graphs), [getattr(lrn, k) for k in attrs]
+    assert sum(not isinstance(g, bool) for g in graphs.values()) == 1 and lrn._mode_key() == ()
+    l0, g0 = losses.clone(), agent.arena.grads.clone()
+    with lrn.loss_scope("ppo+sil", rows=B // 2):
+        assert lrn.loss_mode == "ppo+sil" and lrn._sil_rows == B // 2
+        lrn.update(B, 1.0 / B, sorted_rows=srt)
+    with lrn.loss_scope("ppo+mask"):
+        assert lrn.loss_mode == "ppo+mask"
+        lrn.update(B, 1.0 / B, sorted_rows=srt)
+    n0 = hip.N_CALLS
+    losses = lrn.update(B, 1.0 / B, sorted_rows=srt)
+    assert hip.N_CALLS == n0                             # a replay: nothing was launched from the host
+    assert all(lrn._graphs[k] is g for k, g in graphs.items())
+    assert all(any(p and p[0] in ("sil", "mask") for p in k if isinstance(p, tuple)) for k in set(lrn._graphs) - set(graphs))
+    assert torch.equal(losses, l0) and torch.equal(agent.arena.grads, g0)
+    assert [getattr(lrn, k) for k in attrs] == state
