@@ -240,6 +240,15 @@ SYMBOLS = {
     "cadre_allowed_rows": [vp, i32, vp, i32, i32, vp, i32, vp, vp],
     "cadre_ppo_am_loss": [vp, i64, i64, vp, i64, i64, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, vp, f32, f32, f32, f32, f32,
                           vp, vp, vp, vp, vp, vp, i32, vp, f32, vp, vp, vp, vp, i32, vp, vp],
+    # cost constraints (PPO-Lagrangian): costs pointer table, slots, costs, n, T, stream / obs table (one head), n, Tr, S, ldo, D, H,
+    # row0, rows, tower, values, h1, h2 (both may be NULL), stream / obs table, n, Tr, S, ldo, D, H, row0, rows, tower, values, h1, h2,
+    # returns, ldr, grads, loss[2], scratch, stream / costs pointer table, N, T, state, update, stream / {cost_adv, advantages}
+    # table, n, T, state, diag (may be NULL), stream
+    "cadre_cost_note": [vp, vp, vp, i32, i32, vp],
+    "cadre_cost_forward": [vp, i32, i32, i32, i64, i32, i32, i32, i32, vp, vp, vp, vp, vp],
+    "cadre_cost_backward": [vp, i32, i32, i32, i64, i32, i32, i32, i32, vp, vp, vp, vp, vp, i64, vp, vp, vp, vp],
+    "cadre_cost_lambda": [vp, i32, i32, vp, i32, vp],
+    "cadre_lag_mix": [vp, i32, i32, vp, vp, vp],
 }
 # entry points of the A/B build only (include/cadre_hip_ab.h; CADRE_BUILD_AB=1 python -m cadre_amd.build, then
 # CADRE_HIP_LIB=.../libcadre_hip_ab.so): bound when the loaded library has them
@@ -318,6 +327,8 @@ VTRACE_DIAG_FIELDS = 4  # CADRE_VTRACE_DIAG_FIELDS: mean ratio, share truncated,
 
 # CADRE_RND_*: the curiosity state block (float64; mu [D], M2 [D], carry [N] from RND_HEAD on)
 RND_N, RND_BETA, RND_EXT, RND_RHO_N, RND_RHO_MEAN, RND_RHO_M2, RND_SIGMA, RND_KEY, RND_CTR, RND_HEAD = 0, 1, 2, 3, 4, 5, 6, 7, 8, 16
+# CADRE_LAG_*: the cost-constraint state block (float64; LAG_STRIDE doubles per head)
+LAG_LAMBDA, LAG_BUDGET, LAG_LR, LAG_MAX, LAG_J, LAG_SHARE, LAG_UPDATES, LAG_STRIDE = 0, 1, 2, 3, 4, 5, 6, 8
 RS_SCALE, RS_CARRY = 6, 8 # CADRE_RS_SCALE / CADRE_RS_CARRY: the return-statistics block (count, mean, M2 per head first)
 
 CAPTURE_MAX_RANGES = 65535        # CADRE_CAPTURE_MAX_RANGES

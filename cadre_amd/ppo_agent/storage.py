@@ -74,6 +74,22 @@ class RolloutStorage(object):
             self.events, self.suggest = self.events.to(device), self.suggest.to(device)
         if getattr(self, "allowed", None) is not None:       # (action masks: the words travel along)
             self.allowed = self.allowed.to(device)
+        if getattr(self, "costs", None) is not None:         # (cost constraints: the costs travel along)
+            self.costs = self.costs.to(device)
+
+    def _costs_tensor(self):
+        """`costs` float32 [T + 1] (the cost of each row for this head; 0: none; see cadre_amd.constraint), allocated the first
+        time a cost is passed: a storage that never saw one has no such tensor and keeps today's launches and tensors."""
+        if getattr(self, "costs", None) is None:
+            self.costs = torch.zeros(self.num_steps + 1, dtype=torch.float32, device=self.device)
+        return self.costs
+
+    @staticmethod
+    def _cost_value(c):
+        import math
+        if isinstance(c, bool) or not isinstance(c, (int, float)) or not math.isfinite(c) or c < 0:
+            raise ValueError("cost %r: expected a finite number >= 0" % (c,))
+        return float(c)
 
     def _allowed_tensor(self):
         """`allowed` int64 [T + 1] (the allowed-bin word of each row; 0: unmasked), allocated the first time a word is passed: a
@@ -106,20 +122,25 @@ class RolloutStorage(object):
         return e
 
     def insert(self, obs, action, action_log_probs, value_preds, rewards, masks, hidden_state, command, time_limit=False,
-               event=0, allowed=None, allowed_bins=None):
+               event=0, allowed=None, allowed_bins=None, cost=None):
         """storage.py:45-58.  `time_limit`: this row's episode was cut by a step budget, not ended (see finish_rollouts).
         `event`: the code of the terminal event this row ends with for this head (0: none; see cadre_amd.suggest).  Once a
         storage has seen a code every insert writes the slot, zeros included: a stale code never survives the cursor's
         drift.  `allowed` (action masks): the word this head's action was sampled under (a Python int; None: unmasked).  Once
         a storage has seen a word every insert writes the slot, 0 = unmasked included.  `allowed_bins`: the head's K; with it a
-        word without a bit among the K bins is refused, without it only the all-zero word (the storage does not know K)."""
+        word without a bit among the K bins is refused, without it only the all-zero word (the storage does not know K).
+        `cost` (cost constraints): this head's cost of the row, a finite number >= 0 (None: none).  Once a storage has seen a
+        cost every insert writes the slot, 0 included."""
         s = self.step
         event = self._event_code(event)
+        cost = None if cost is None else self._cost_value(cost)                            # (checked before anything is written)
         word = None if allowed is None else self._allowed_word(allowed, allowed_bins)      # (checked before anything is written)
         if allowed is not None or getattr(self, "allowed", None) is not None:
             self._allowed_tensor()[s] = 0 if word is None else word
         if event or getattr(self, "events", None) is not None:
             self._event_tensors()[s] = event
+        if cost is not None or getattr(self, "costs", None) is not None:
+            self._costs_tensor()[s] = 0.0 if cost is None else cost
         if time_limit or self._tl_used:          # (a storage that never saw a flag keeps the reference's launches)
             self.time_limits[s] = 1.0 if time_limit else 0.0
             self._tl_used = True
@@ -137,7 +158,8 @@ class RolloutStorage(object):
         self.step = (s + 1) % (self.num_steps + 1)
 
     @staticmethod
-    def insert_batch(storages, outputs, rewards, masks, commands, time_limits=None, events=None, allowed=None, n_out=None):
+    def insert_batch(storages, outputs, rewards, masks, commands, time_limits=None, events=None, allowed=None, n_out=None,
+                     costs=None):
         """`insert` (storage.py:45-58) of one env step of N environments into their 2N storages in ONE launch
         (cadre_insert_rows; with `time_limits` its twin cadre_insert_rows_tl, which writes the flags in the same launch):
         time_limits = None, or per environment a bool or a (steer, throttle) pair of bools.  storages = [(steer_rollout, throttle_rollout), ...] per environment, outputs = what
@@ -151,8 +173,16 @@ class RolloutStorage(object):
         [N][2] tensor act_batch sampled under.  All 2N words of the step are written by ONE extra launch (cadre_allowed_note),
         which is not issued when `allowed` is None and no storage has the tensor (it then writes 0 = unmasked).  `n_out` =
         (K_steer, K_throttle): with it a Python-int word without a bit among its head's bins is refused, without it only the
-        all-zero word (the storages do not know K); a device tensor is taken as it is, as act_batch took it."""
+        all-zero word (the storages do not know K); a device tensor is taken as it is, as act_batch took it.
+        `costs` (cost constraints): None, or per environment a finite number >= 0 (written to both heads) or a (steer,
+        throttle) pair.  All 2N costs of the step are written by ONE extra launch (cadre_cost_note), which is not issued when
+        `costs` is None and no storage has the tensor (it then writes 0)."""
         N = len(storages)
+        co = None
+        if costs is not None:                # (checked before anything is launched)
+            if len(costs) != N or any(isinstance(c, (tuple, list)) and len(c) != 2 for c in costs):
+                raise ValueError("insert_batch: %d storage pairs, costs must hold as many numbers or (steer, throttle) pairs" % N)
+            co = [RolloutStorage._cost_value(v) for c in costs for v in (c if isinstance(c, (tuple, list)) else (c, c))]
         al = None
         if allowed is not None:              # (checked before anything is launched)
             if torch.is_tensor(allowed):
@@ -250,6 +280,14 @@ class RolloutStorage(object):
                 words = torch.tensor(al, dtype=torch.int64).to(dev)
             hip.check(hip.lib().cadre_allowed_note(hip.ptr(atable), hip.ptr(ints), hip.ptr(words), 2 * N, s0.num_steps,
                                                    hip.stream()), "cadre_allowed_note")
+        if co is not None or any(getattr(s, "costs", None) is not None for s in flat):
+            cptrs = tuple(hip.ptr(s._costs_tensor()) for s in flat)
+            ctable = tables.get(("costs",) + cptrs)
+            if ctable is None:
+                ctable = tables[("costs",) + cptrs] = torch.tensor(cptrs, dtype=torch.int64).to(dev)
+            vals = torch.tensor([0.0] * (2 * N) if co is None else co, dtype=torch.float32).to(dev)
+            hip.check(hip.lib().cadre_cost_note(hip.ptr(ctable), hip.ptr(ints), hip.ptr(vals), 2 * N, s0.num_steps,
+                                                hip.stream()), "cadre_cost_note")
         for s in flat:
             s.step = (s.step + 1) % (s.num_steps + 1)
 

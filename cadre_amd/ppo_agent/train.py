@@ -524,6 +524,53 @@ def _curiosity_stats(stats, cur):
         stats["curiosity"] = cur.summary()
 
 
+def cost_constraint(agent, train_cfg, n_envs=1, shared_grad_buffers=None, fused_gather=True, ck_interval=None, ck_resume=None):
+    """train_cfg["cost_constraint"] (absent / None: None — nothing runs, nothing is allocated): the CostConstraint of a run that
+    holds the cost rate of each head under a budget (cadre_amd.constraint.constraint_config for the keys, constraint_refusals for
+    what is refused at start-up and why)."""
+    cfg = _get(train_cfg, "cost_constraint")
+    if cfg is None:
+        return None
+    from ..constraint import constraint_runner
+    return constraint_runner(agent, cfg, n_envs, sample_reuse=_get(train_cfg, "sample_reuse"),
+                             self_imitation=_get(train_cfg, "self_imitation"), checkpoint_interval=ck_interval, resume_from=ck_resume,
+                             world=shared_grad_buffers.dist_world() if shared_grad_buffers is not None else 1,
+                             fused_gather=fused_gather, demo_mix=_get(train_cfg, "demo_mix"), suggest=_get(train_cfg, "suggest"),
+                             smoothness=_get(train_cfg, "smoothness"), aux_phase=_get(train_cfg, "aux_phase"))
+
+
+def _check_constraint(con, reuse, sil, shared_grad_buffers, fused_gather=True, demo=None, suggest=None, smooth=None):
+    if con is None:
+        return
+    if reuse is not None or sil is not None:
+        raise ValueError("constraint excludes reuse and sil (sample_reuse, self_imitation: their rows carry no costs)")
+    if shared_grad_buffers is not None and shared_grad_buffers.dist_world() > 1:
+        raise ValueError("constraint needs a single rank: each rank would own a multiplier")
+    if not fused_gather:
+        raise ValueError("constraint needs fused_gather=True")
+    if demo is not None or suggest is not None or smooth is not None:
+        raise ValueError("constraint excludes demo, suggest and smooth (demo_mix, suggest, smoothness: the combination is untested)")
+
+
+def _constraint_end(stats, con):
+    """Behind the PPO steps of a section: the cost critics' steps (with one more forward for the stats entry when one is wanted)."""
+    if con is not None:
+        con.update(stats=stats is not None)
+
+
+def _constraint_stats(stats, con):
+    if stats is not None and con is not None:
+        stats["constraint"] = con.summary()
+
+
+def _cost_kw(con, info, head=None):
+    """Keyword arguments of insert (head 0 / 1) for the step's info["cost"] ({} without the module: today's call)."""
+    if con is None:
+        return {}
+    from ..constraint import cost_pair
+    return dict(cost=cost_pair(info.get("cost", 0.0))[head])
+
+
 def _rewind(smooth, rollouts):
     """With the smoothness term every rollout starts at row 0 of its storages, so that rows 0 .. T - 1 are one rollout in
     time order (without it the cursors keep the reference's modulo-(T + 1) drift)."""
@@ -781,6 +828,9 @@ def stats_line(episode, stats):
     if "curiosity" in stats:                           # curiosity: the predictor's error, its scale and the bonus paid
         from ..curiosity import curiosity_stats_text
         line += curiosity_stats_text(stats)
+    if "constraint" in stats:                          # cost constraint: cost rate, multiplier, the two advantage terms
+        from ..constraint import constraint_stats_text
+        line += constraint_stats_text(stats)
     return line
 
 
@@ -798,7 +848,8 @@ def _check_sil(sil, demo, suggest, reuse, path_ok=True):
 def learner_section(agent, steer_rollout, throttle_rollout, done, train_cfg, shared_grad_buffers,
                     optimizer=None, traffic_light=None, counter=None, shared_model_list=None, in_process_chief=True,
                     fused_gather=True, losses_on_device=False, step_events=None, stats=None, reward_scaler=None,
-                    demo=None, episode=0, reuse=None, suggest=None, sil=None, smooth=None, curiosity=None, actmask=None):
+                    demo=None, episode=0, reuse=None, suggest=None, sil=None, smooth=None, curiosity=None, actmask=None,
+                    constraint=None):
     """train.py:76-110.  Returns (value_loss_list, policy_loss_list, ent_loss_list).
     With `in_process_chief` (one process per GPU) the optimiser step runs right after the gradient
     all-reduce instead of waiting on a separate chief process.  `fused_gather` uses the storage ->
@@ -842,7 +893,10 @@ def learner_section(agent, steer_rollout, throttle_rollout, done, train_cfg, sha
     `reward_scaler`, `reuse` and `sil`): the random network distillation bonus, as in learner_section_multi; the two storages
     are then finished by RolloutStorage.finish_rollouts.
     `actmask` (a cadre_amd.actmask.ActionMasks; needs fused_gather, excludes `demo`, `suggest`, `sil`, `smooth` and `reuse`):
-    action masks, as in learner_section_multi."""
+    action masks, as in learner_section_multi.
+    `constraint` (a cadre_amd.constraint.CostConstraint for one environment; needs fused_gather and a single rank, excludes
+    `reuse`, `sil`, `demo`, `suggest` and `smooth`): the cost constraint, as in learner_section_multi."""
+    _check_constraint(constraint, reuse, sil, shared_grad_buffers, fused_gather, demo, suggest, smooth)
     _check_actmask(actmask, demo, suggest, reuse, sil, smooth, fused_gather)
     _check_smooth(smooth, demo, suggest, reuse, sil, fused_gather)
     _check_curiosity(curiosity, reward_scaler, reuse, sil, shared_grad_buffers, fused_gather)
@@ -868,11 +922,12 @@ def learner_section(agent, steer_rollout, throttle_rollout, done, train_cfg, sha
         out = _learner_section(agent, steer_rollout, throttle_rollout, done, train_cfg, shared_grad_buffers, optimizer,
                                traffic_light, counter, shared_model_list, in_process_chief, fused_gather, losses_on_device,
                                step_events, use_adv_norm, sec, lr, reward_scaler, cons, demo, episode, reuse, suggest,
-                               stats, sil, smooth, curiosity, actmask)
+                               stats, sil, smooth, curiosity, actmask, constraint)
     finally:
         if sec is not None:
             agent.learner.set_update_modes()
     _curiosity_end(stats, curiosity)
+    _constraint_end(stats, constraint)
     if sec is None:
         return out
     if losses_on_device:
@@ -884,6 +939,7 @@ def learner_section(agent, steer_rollout, throttle_rollout, done, train_cfg, sha
         _sil_stats(stats, sil)
         _smooth_stats(stats, smooth)
         _curiosity_stats(stats, curiosity)
+        _constraint_stats(stats, constraint)
         return out
     dev_losses, (vl, pl, el) = out
     host = sec.finish(stats, tkl is not None, losses=torch.stack(dev_losses) if dev_losses else None)
@@ -894,6 +950,7 @@ def learner_section(agent, steer_rollout, throttle_rollout, done, train_cfg, sha
     _sil_stats(stats, sil)
     _smooth_stats(stats, smooth)
     _curiosity_stats(stats, curiosity)
+    _constraint_stats(stats, constraint)
     if host is not None:
         for v, p, e in host.tolist():
             vl.append(v); pl.append(p); el.append(e)
@@ -903,13 +960,15 @@ def learner_section(agent, steer_rollout, throttle_rollout, done, train_cfg, sha
 def _learner_section(agent, steer_rollout, throttle_rollout, done, train_cfg, shared_grad_buffers, optimizer, traffic_light,
                      counter, shared_model_list, in_process_chief, fused_gather, losses_on_device, step_events, use_adv_norm,
                      sec, lr, reward_scaler=None, cons=False, demo=None, episode=0, reuse=None, suggest=None, stats=None,
-                     sil=None, smooth=None, curiosity=None, actmask=None):
+                     sil=None, smooth=None, curiosity=None, actmask=None, constraint=None):
     if smooth is not None:                           # (the cursor check comes before any launch of the section)
         smooth.begin_section([(steer_rollout, throttle_rollout)],
                              train_cfg["ppo_epoch"] * _steps_per_epoch(steer_rollout) if stats is not None else 0)
     nv_s, nv_t = agent.get_value(done, steer_rollout.get_last(as_tensor=True), throttle_rollout.get_last(as_tensor=True))
     if curiosity is not None:
         curiosity.begin_section([(steer_rollout, throttle_rollout)])
+    if constraint is not None:
+        constraint.begin_section([(steer_rollout, throttle_rollout)], [done])
     if curiosity is not None or reward_scaler is not None or steer_rollout._tl_used or throttle_rollout._tl_used:
         steer_adv, throttle_adv = RolloutStorage.finish_rollouts(
             [steer_rollout, throttle_rollout], [nv_s.detach(), nv_t.detach()], normalise=use_adv_norm,
@@ -921,6 +980,8 @@ def _learner_section(agent, steer_rollout, throttle_rollout, done, train_cfg, sh
                                                   explained_variance=None if sec is None else sec.ev[0:1])
         throttle_adv = throttle_rollout.compute_returns(nv_t.detach(), normalise=use_adv_norm,
                                                         explained_variance=None if sec is None else sec.ev[1:2])
+    if constraint is not None:                       # (behind the reward advantages, whichever launch wrote them)
+        constraint.mix([(steer_rollout, throttle_rollout)])
     if reuse is not None:
         reuse.refresh(use_adv_norm, reward_scaler)
     sug_prev = _suggest_begin(agent, suggest, [steer_rollout, throttle_rollout], stats,
@@ -1029,6 +1090,7 @@ def train(rank, train_cfg, agent_cfg, env_cfg, rollout_cfg, traffic_light=None, 
     ck_interval, ck_resume = _checkpointing(train_cfg, shared_grad_buffers)
     # (refusals first: before a checkpoint is read or anything else is built)
     cur = agent.curiosity = curiosity(agent, train_cfg, 1, shared_grad_buffers, True, ck_interval, ck_resume)
+    con = agent.constraint = cost_constraint(agent, train_cfg, 1, shared_grad_buffers, True, ck_interval, ck_resume)
     ck, first_episode = None, 0
     if ck_interval is not None or ck_resume is not None:
         ck = _Checkpointer(env.work_dir, ck_interval, agent, [(steer_rollout, throttle_rollout)])
@@ -1066,10 +1128,10 @@ def train(rank, train_cfg, agent_cfg, env_cfg, rollout_cfg, traffic_light=None, 
                 ev = (dict(ev[0], allowed=words[0], allowed_bins=nS), dict(ev[1], allowed=words[1], allowed_bins=nT))
             steer_rollout.insert(feat, action[0], alp[0], values[0], reward[0],
                                  torch.tensor([[0.0] if ad[0] else [1.0]]), hidden, command, time_limit=tl[0],
-                                 **ev[0])
+                                 **ev[0], **_cost_kw(con, info, 0))
             throttle_rollout.insert(feat, action[1], alp[1], values[1], reward[1],
                                     torch.tensor([[0.0] if ad[1] else [1.0]]), hidden, command, time_limit=tl[1],
-                                    **ev[1])
+                                    **ev[1], **_cost_kw(con, info, 1))
             if done:
                 obs, info = env.reset(), None
         if recorder is not None:
@@ -1091,7 +1153,8 @@ def train(rank, train_cfg, agent_cfg, env_cfg, rollout_cfg, traffic_light=None, 
                                      **({} if actmask is None else dict(actmask=actmask)),
                                      **({} if sil is None else dict(sil=sil.buffer_for([(steer_rollout, throttle_rollout)]))),
                                      **({} if smooth is None else dict(smooth=smooth)),
-                                     **({} if cur is None else dict(curiosity=cur)))
+                                     **({} if cur is None else dict(curiosity=cur)),
+                                     **({} if con is None else dict(constraint=con)))
         log_now = episode % train_cfg.log_interval == 0 and rank == 0 and logger is not None
         # (the auxiliary phase: before the log line, the snapshot and the checkpoint, which then see its result)
         aux_records = _aux_after_section(aux, agent, train_cfg, episode, [(steer_rollout, throttle_rollout)],
@@ -1123,7 +1186,7 @@ def train(rank, train_cfg, agent_cfg, env_cfg, rollout_cfg, traffic_light=None, 
 # ----------------------------------------------------------------------------- N environments in one process
 def learner_section_multi(agent, rollouts, dones, train_cfg, shared_grad_buffers, optimizer=None, losses_on_device=False,
                           stats=None, reward_scaler=None, demo=None, episode=0, reuse=None, suggest=None, sil=None,
-                          smooth=None, curiosity=None, actmask=None):
+                          smooth=None, curiosity=None, actmask=None, constraint=None):
     """train.py:76-110 for N workers that share one agent (`num_processes = N` on one GPU, chief.py:13-21 semantics):
     rollouts = [(steer_rollout, throttle_rollout), ...] per worker, dones[i] = worker i's last `done`.  Bootstrap values
     of all workers in one pass (get_values), GAE + advantage normalisation per storage, then for each ppo_epoch and
@@ -1179,7 +1242,17 @@ def learner_section_multi(agent, rollouts, dones, train_cfg, shared_grad_buffers
     of its rows (what insert_batch(allowed=) stored beside them) into the update's layout (cadre_allowed_rows) before the
     update, whose loss launch is cadre_ppo_am_loss.  The loss is per rank and nothing new is exchanged.  `stats` gains
     "actmask" (masked_share, allowed_bins, pressure, forced_rows as (steer, throttle) pairs; one more small device-to-host
+    copy).
+    `constraint` (a cadre_amd.constraint.CostConstraint for N environments; single rank, excludes `reuse`, `sil`, `demo`, `suggest`
+    and `smooth`): the cost constraint (PPO-Lagrangian).  Beside the bootstrap values constraint.begin_section(rollouts, dones)
+    values the costs the storages recorded (insert_batch(costs=)), scans them with the reward scan's masks and cuts and steps the
+    multiplier of each head; after the storages are finished as they are without it, constraint.mix(rollouts) rewrites every
+    storage's `advantages` to (A_r - lambda (A_c - mean A_c)) / (1 + lambda) — nothing is stored for a head whose lambda is 0 —
+    and behind the PPO steps constraint.update() runs the cost critics' steps.  The loss launches, the update's graphs and the
+    sampler are untouched.  `stats` gains "constraint" (J, budget, lambda, costly_share, mean_abs_cost_term, mean_abs_reward_term,
+    loss_before, loss_after, explained_variance as (steer, throttle) pairs, steps, lambda_updates; one more small device-to-host
     copy)."""
+    _check_constraint(constraint, reuse, sil, shared_grad_buffers, True, demo, suggest, smooth)
     _check_actmask(actmask, demo, suggest, reuse, sil, smooth)
     _check_smooth(smooth, demo, suggest, reuse, sil)
     _check_curiosity(curiosity, reward_scaler, reuse, sil, shared_grad_buffers)
@@ -1201,12 +1274,16 @@ def learner_section_multi(agent, rollouts, dones, train_cfg, shared_grad_buffers
                             demo=demo is not None and stats is not None)
     if curiosity is not None:
         curiosity.begin_section(rollouts)
+    if constraint is not None:
+        constraint.begin_section(rollouts, dones)
     flat = RolloutStorage.finish_rollouts([x for pair in rollouts for x in pair], [v.detach() for pair in nv for v in pair],
                                           normalise=use_adv_norm, reward_scaler=reward_scaler,
                                           explained_variance=None if sec is None else sec.ev,
                                           **_scaler_consensus(cons, reward_scaler, shared_grad_buffers),
                                           **({} if curiosity is None else dict(intrinsic=curiosity)))
     advs = [(flat[2 * i], flat[2 * i + 1]) for i in range(len(rollouts))]
+    if constraint is not None:
+        constraint.mix(rollouts)
     if reuse is not None:
         reuse.refresh(use_adv_norm, reward_scaler)
     if sec is not None:
@@ -1242,6 +1319,7 @@ def learner_section_multi(agent, rollouts, dones, train_cfg, shared_grad_buffers
             agent.learner.set_update_modes()
         _loss_end(agent, sug_prev, am_prev)
     _curiosity_end(stats, curiosity)
+    _constraint_end(stats, constraint)
     losses = torch.stack(dev_losses)
     if sec is not None and not losses_on_device:
         host = sec.finish(stats, tkl is not None, losses=losses)
@@ -1252,6 +1330,7 @@ def learner_section_multi(agent, rollouts, dones, train_cfg, shared_grad_buffers
         _sil_stats(stats, sil)
         _smooth_stats(stats, smooth)
         _curiosity_stats(stats, curiosity)
+        _constraint_stats(stats, constraint)
         return tuple(list(c) for c in zip(*host.tolist()))
     if sec is not None:
         sec.finish(stats, tkl is not None)
@@ -1262,6 +1341,7 @@ def learner_section_multi(agent, rollouts, dones, train_cfg, shared_grad_buffers
         _sil_stats(stats, sil)
         _smooth_stats(stats, smooth)
         _curiosity_stats(stats, curiosity)
+        _constraint_stats(stats, constraint)
     if losses_on_device:
         return losses
     vl, pl, el = [], [], []
@@ -1333,6 +1413,7 @@ def train_vec(rank, train_cfg, agent_cfg, env_cfg, rollout_cfg, num_envs, env_cl
     ck_interval, ck_resume = _checkpointing(train_cfg, shared_grad_buffers)
     # (refusals first: before a checkpoint is read or anything else is built)
     cur = agent.curiosity = curiosity(agent, train_cfg, num_envs, shared_grad_buffers, True, ck_interval, ck_resume)
+    con = agent.constraint = cost_constraint(agent, train_cfg, num_envs, shared_grad_buffers, True, ck_interval, ck_resume)
     ck, first_episode = None, 0
     if ck_interval is not None or ck_resume is not None:
         ck = _Checkpointer(envs[0].work_dir, ck_interval, agent, rollouts, callback)
@@ -1359,7 +1440,7 @@ def train_vec(rank, train_cfg, agent_cfg, env_cfg, rollout_cfg, num_envs, env_cl
             commands = [o["command"] for o in obs]
             words = None if actmask is None else [actmask.words(o, f) for o, f in zip(obs, infos)]
             outs = agent.act_batch(obs, **({} if words is None else dict(allowed=words)))      # (key absent: today's call)
-            rewards, masks, tls, evs = [], [], [], []
+            rewards, masks, tls, evs, costs = [], [], [], [], []
             for i, (env, out) in enumerate(zip(envs, outs)):
                 obs[i], reward, dones[i], info = env.step(agent.convert_action(out[1]))
                 infos[i] = info
@@ -1369,11 +1450,14 @@ def train_vec(rank, train_cfg, agent_cfg, env_cfg, rollout_cfg, num_envs, env_cl
                 tls.append(info.get("time_limit"))
                 if suggest is not None:
                     evs.append(suggest.codes(info))
+                if con is not None:
+                    costs.append(info.get("cost", 0.0))
             RolloutStorage.insert_batch(rollouts, outs, rewards, masks, commands,
                                         time_limits=None if all(f is None for f in tls) else
                                         [_time_limit_pair(False if f is None else f) for f in tls],
                                         **({} if suggest is None else dict(events=evs)),
-                                        **({} if words is None else dict(allowed=outs.allowed)))
+                                        **({} if words is None else dict(allowed=outs.allowed)),
+                                        **({} if con is None else dict(costs=costs)))
             for i, env in enumerate(envs):
                 if dones[i]:
                     obs[i], infos[i] = env.reset(), None
@@ -1393,7 +1477,8 @@ def train_vec(rank, train_cfg, agent_cfg, env_cfg, rollout_cfg, num_envs, env_cl
                                            **({} if actmask is None else dict(actmask=actmask)),
                                            **({} if sil is None else dict(sil=sil.buffer_for(rollouts))),
                                            **({} if smooth is None else dict(smooth=smooth)),
-                                           **({} if cur is None else dict(curiosity=cur)))
+                                           **({} if cur is None else dict(curiosity=cur)),
+                                           **({} if con is None else dict(constraint=con)))
         log_now = episode % train_cfg.log_interval == 0 and rank == 0 and logger is not None
         # (the auxiliary phase: before the log line, the snapshot and the checkpoint, which then see its result)
         aux_records = _aux_after_section(aux, agent, train_cfg, episode, rollouts, shared_grad_buffers, optimizer,

@@ -1329,6 +1329,56 @@ int cadre_ppo_am_loss(const float* logits, int64_t ldl, int64_t l_ns, const floa
                       float* stats_row, int32_t F, float* stats_scratch, float target_kl, int32_t* stop, const int32_t* ord,
                       const int64_t* allowed, float* am_stats, int32_t am_F, float* am_scratch, void* stream);
 
+/* ---------------------------------------------------------------- cost constraints (opt-in, csrc/constraint.hip)
+ * PPO-Lagrangian (Ray et al. 2019) per head: a cost c >= 0 is recorded beside every reward, a cost critic per head values it,
+ * and the advantages of the update become (A_r - lambda (A_c - mean A_c)) / (1 + lambda) with a multiplier lambda per head
+ * that follows the cost RATE J = mean c of the section against a budget.  No loss kernel changes.
+ * A cost tower is one flat fp32 buffer: W1 [D][H], b1 [H], W2 [H][H], b2 [H], W3 [H], b3 [1] — every matrix input-major, the
+ * layout of the gradient buffer too.  H a multiple of 32, at most 256; 1 <= D <= 1024.  Rows: r = w * Tr + t for storage w < n
+ * of obs_table (n device pointers to window rows [..][S][ldo], the storages of ONE head) and row t < Tr; x = obs_w[t][S - 1][0 ..
+ * D-1] as stored.  Columns D .. ldo-1 and frames s < S - 1 are not read.
+ * State block (float64), CADRE_LAG_STRIDE doubles per head h at state + h * CADRE_LAG_STRIDE: [CADRE_LAG_LAMBDA] the multiplier,
+ * [CADRE_LAG_BUDGET] the budget of the cost rate, [CADRE_LAG_LR] lr_lambda, [CADRE_LAG_MAX] lambda_max, [CADRE_LAG_J] the last
+ * cost rate, [CADRE_LAG_SHARE] the share of the last section's rows with c > 0, [CADRE_LAG_UPDATES] the multiplier steps taken.
+ * cadre_cost_note: costs[k][slots[k]] = cost[k] for n storages in one launch; table: n device pointers to the storages' f32
+ * [T + 1] tensors (0: skipped), 0 <= slots[k] <= T.
+ * cadre_cost_forward: rows row0 .. row0 + rows - 1: h1 = relu(x W1 + b1), h2 = relu(h1 W2 + b2), values[i] = (sum_k h2_k W3_k in k
+ * order) + b3 for i = r - row0, strict fp32.  h1, h2 [rows][H]: each NULL when not wanted.  A row's result does not depend on the
+ * other rows of the launch.
+ * cadre_cost_backward: the rows of one critic step with the values, h1, h2 the forward saved.  R_i = returns[w * ldr + t] of row
+ * r = row0 + i.  d = v - R, dv = d / rows; loss[0] = 0.5 mean d^2 (float64 sum in a fixed order), loss[1] = rows; db3 = sum dv,
+ * dW3 = h2^T dv, dH2 = (dv W3^T) [h2 > 0], dW2 = h1^T dH2, dH1 = (dH2 W2^T) [h1 > 0], dW1 = x^T dH1 with x read from the storage rows
+ * themselves, db = column sums; every sum over rows runs in a fixed order.  scratch: rows (2 H + 1) floats.  Five launches, no
+ * atomics.
+ * cadre_cost_lambda: one workgroup per head.  cost_table: 2 N device pointers to costs f32 [T + 1], storage k of head k & 1.
+ * J_h = (sum of the head's N T costs, rows 0 .. T-1 of its storages, float64, thread i of 256 summing rows i, i + 256, ... of
+ * the (storage, time) order, the partials met in a fixed tree) / (N T); [CADRE_LAG_J] and [CADRE_LAG_SHARE] are written; with
+ * `update`, lambda <- min(max(lambda + lr (J - budget), 0), lambda_max) in float64, one rounding per operation, and the
+ * step count advances.
+ * cadre_lag_mix: one workgroup per storage k of n (head k & 1), row_table: n records {cost_adv f32 [T], advantages f32 [T]}.
+ * lf = (float)lambda_h.  m = (float)(float64 sum of cost_adv[0 .. T-1] in row order) / (float)T, then per row in strict fp32, one
+ * rounding per statement: c = cost_adv[t] - m; p = lf c; q = advantages[t] - p; advantages[t] = q / (1 + lf).  With lf == 0
+ * NOTHING is stored into that storage's advantages.  diag (may be NULL) double [n][2]: mean |p| / (1 + lf) and mean
+ * |advantages[t] before the mix| / (1 + lf) of the storage.  Must run behind the cadre_cost_lambda launch whose lambda it reads.
+ * Refused before any launch: null operands, dimensions outside the above, T outside 2 .. 3000 (cadre_gae_multi's range) for
+ * cadre_cost_lambda and cadre_lag_mix, rows outside the table. */
+#define CADRE_LAG_LAMBDA 0
+#define CADRE_LAG_BUDGET 1
+#define CADRE_LAG_LR 2
+#define CADRE_LAG_MAX 3
+#define CADRE_LAG_J 4
+#define CADRE_LAG_SHARE 5
+#define CADRE_LAG_UPDATES 6
+#define CADRE_LAG_STRIDE 8
+int cadre_cost_note(const void* table, const int32_t* slots, const float* costs, int32_t n, int32_t T, void* stream);
+int cadre_cost_forward(const void* obs_table, int32_t n, int32_t Tr, int32_t S, int64_t ldo, int32_t D, int32_t H, int32_t row0,
+                       int32_t rows, const float* tower, float* values, float* h1, float* h2, void* stream);
+int cadre_cost_backward(const void* obs_table, int32_t n, int32_t Tr, int32_t S, int64_t ldo, int32_t D, int32_t H, int32_t row0,
+                        int32_t rows, const float* tower, const float* values, const float* h1, const float* h2,
+                        const float* returns, int64_t ldr, float* grads, float* loss, float* scratch, void* stream);
+int cadre_cost_lambda(const void* cost_table, int32_t N, int32_t T, double* state, int32_t update, void* stream);
+int cadre_lag_mix(const void* row_table, int32_t n, int32_t T, const double* state, double* diag, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
