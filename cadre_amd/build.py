@@ -13,7 +13,7 @@ CSRC = os.path.join(os.path.dirname(os.path.abspath(__file__)), "csrc")
 INCLUDE = os.path.join(os.path.dirname(CSRC), "..", "include")
 SOURCES = ["gemm_f32.hip", "gemm_bf16.hip", "gemm_bf16_w128.hip", "stem_pool.hip", "conv3x3_ring.hip", "conv3x3_s2.hip", "conv3x3_s1x.hip", "ppo_update.hip", "peaks.hip", "winograd.hip", "winograd_c64.hip", "winograd_fused.hip",
            "cadre_kernels.hip", "act_batch.hip", "rollout_finish.hip", "checkpoint.hip", "consensus.hip", "ensemble.hip", "imitation.hip", "demo_mix.hip", "phasic.hip", "reuse.hip", "suggest.hip", "frame_table.hip", "deconv.hip", "selfimit.hip", "smooth.hip",
-           "curiosity.hip", "actmask.hip", "constraint.hip"]
+           "curiosity.hip", "actmask.hip", "constraint.hip", "average.hip"]
 AB_SOURCES = ["ab/gemm_f32_skinny.hip", "ab/gemm_stream_f32.hip", "ab/conv_stream_f32.hip", "ab/conv_stream_bf16.hip", "ab/conv3x3_c64_bf16.hip", "ab/conv3x3_w128.hip"]
 # per-file flags: the fused Winograd kernel is written in issue order; the machine scheduler's reordering costs it 40 spills.  Its
 # step loop (8 steps x 128 inline-asm MFMAs + the epilogue's pinned accumulator reads) is past the default size limit of

@@ -70,6 +70,9 @@ def _ranges(agent, pairs, reward_scaler):
         out.append(("hp", lrn._hp))
     if reward_scaler is not None:
         out.append(("scaler", reward_scaler.state))
+    avg = getattr(lrn, "_avg", None)
+    if avg is not None:                      # the weight average and its state block (cadre_amd.average.WeightAverage)
+        out += [("ema", avg.ema), ("ema_state", avg.state)]
     for e, pair in enumerate(pairs):
         for h, s in zip(HEADS, pair):
             out += [("storage%d.%s.%s" % (e, h, k), getattr(s, k)) for k in STORAGE_TENSORS]
@@ -88,6 +91,12 @@ def _layout(arena):
     return dict(D=int(arena.D), C=int(arena.C), n_out=[int(v) for v in arena.n_out], hid=int(arena.hid),
                 total=int(arena.total), ordinal_rank=None if rank is None else [None if r is None else [int(x) for x in r]
                                                                                  for r in rank])
+
+
+def _average_meta(lrn):
+    """meta["weight_average"]: None, or the settings of the learner's weight average."""
+    avg = getattr(lrn, "_avg", None)
+    return None if avg is None else dict(decay=float(avg.decay), warmup=bool(avg.warmup))
 
 
 def _fingerprint(agent):
@@ -200,6 +209,8 @@ def capture(agent, rollouts=None, reward_scaler=None, episode=None, extra=None):
     if getattr(a, "_shard", None) is not None:
         raise hip.CadreHipError("checkpoint: this arena's Adam state is sharded over the data-parallel ranks (elements "
                                 "[%d, %d)); the sharded optimiser is not captured" % a._shard)
+    if getattr(lrn, "_avg_swapped", False):
+        raise hip.CadreHipError("checkpoint: capture inside averaged_weights(): the arena holds the average")
     if not a.params.is_cuda:
         raise hip.CadreHipError("checkpoint: capture runs on the HIP device; the arena lives on %s" % a.params.device)
     if torch.cuda.is_current_stream_capturing():
@@ -244,7 +255,7 @@ def capture(agent, rollouts=None, reward_scaler=None, episode=None, extra=None):
         storages=[[dict(step=int(s.step), tl_used=bool(s._tl_used), **{k: int(getattr(s, k)) for k in STORAGE_GEOMETRY})
                    for s in pair] for pair in pairs],
         rng_state=torch.get_rng_state().clone(),
-        episode=None if episode is None else int(episode), extra=extra)
+        episode=None if episode is None else int(episode), extra=extra, weight_average=_average_meta(lrn))
     return Capture(st, plan, meta, done, st.generation)
 
 
@@ -300,7 +311,18 @@ def _check(agent, state, pairs, reward_scaler):
         raise ValueError("checkpoint mismatch in device_hyper: the flag and the hp block disagree")
     # the destinations, by name (moments and hp block may not exist yet: they have the shapes of params / the block)
     lrn = agent.learner
+    avg = getattr(lrn, "_avg", None)
+    if ("ema" in tensors) != ("ema_state" in tensors):
+        raise ValueError("checkpoint mismatch in ema / ema_state: only one of the two is in the file")
+    if ("ema" in tensors) != (avg is not None):
+        raise ValueError("checkpoint mismatch in ema: the file %s a weight average, the agent %s one (set_weight_average / "
+                         "train_cfg.weight_average)" % ("has" if "ema" in tensors else "lacks", "has" if avg is not None else "lacks"))
+    if state.get("weight_average") != _average_meta(lrn):
+        raise ValueError("checkpoint mismatch in weight_average: the file was taken with %r, the agent's ema runs with %r"
+                         % (state.get("weight_average"), _average_meta(lrn)))
     want = {"params": a.params, "exp_avg": a.params, "exp_avg_sq": a.params, "step_dev": a.step_dev}
+    if avg is not None:
+        want["ema"], want["ema_state"] = avg.ema, avg.state
     want["hp"] = lrn._hp if lrn._hp is not None else torch.empty(hip.HP_FIELDS, dtype=torch.float64, device="meta")
     if reward_scaler is not None:
         want["scaler"] = reward_scaler.state
@@ -333,6 +355,8 @@ def restore(agent, state, rollouts=None, reward_scaler=None):
     a, lrn = agent.arena, agent.learner
     if not a.params.is_cuda:
         raise hip.CadreHipError("checkpoint: restore runs on the HIP device; the arena lives on %s" % a.params.device)
+    if getattr(lrn, "_avg_swapped", False):
+        raise hip.CadreHipError("checkpoint: restore inside averaged_weights(): the arena holds the average")
     pairs = _pairs(rollouts)
     names = _check(agent, state, pairs, reward_scaler)
     tensors = state["tensors"]
@@ -373,6 +397,10 @@ def restore(agent, state, rollouts=None, reward_scaler=None):
     dest = {"params": a.params, "exp_avg": a.exp_avg, "exp_avg_sq": a.exp_avg_sq, "step_dev": a.step_dev, "hp": lrn._hp}
     if reward_scaler is not None:
         dest["scaler"] = reward_scaler.state
+    avg = getattr(lrn, "_avg", None)
+    if avg is not None:
+        dest["ema"], dest["ema_state"] = avg.ema, avg.state
+        avg._decay_set = None                  # (the block's decay is the file's now)
     for e, pair in enumerate(pairs):
         for h, s in zip(HEADS, pair):
             for k in STORAGE_TENSORS:

@@ -249,6 +249,11 @@ SYMBOLS = {
     "cadre_cost_backward": [vp, i32, i32, i32, i64, i32, i32, i32, i32, vp, vp, vp, vp, vp, i64, vp, vp, vp, vp],
     "cadre_cost_lambda": [vp, i32, i32, vp, i32, vp],
     "cadre_lag_mix": [vp, i32, i32, vp, vp, vp],
+    # weight averaging: params, ema, seg_off, n_models, state, work, stop (may be NULL), stream / a, b, n, stream / source
+    # pointer table, weights, K, out, n, stream
+    "cadre_ema_update": [vp, vp, vp, i32, vp, vp, vp, vp],
+    "cadre_arena_swap": [vp, vp, i64, vp],
+    "cadre_arena_mean": [vp, vp, i32, vp, i64, vp],
 }
 # entry points of the A/B build only (include/cadre_hip_ab.h; CADRE_BUILD_AB=1 python -m cadre_amd.build, then
 # CADRE_HIP_LIB=.../libcadre_hip_ab.so): bound when the loaded library has them
@@ -329,6 +334,10 @@ VTRACE_DIAG_FIELDS = 4  # CADRE_VTRACE_DIAG_FIELDS: mean ratio, share truncated,
 RND_N, RND_BETA, RND_EXT, RND_RHO_N, RND_RHO_MEAN, RND_RHO_M2, RND_SIGMA, RND_KEY, RND_CTR, RND_HEAD = 0, 1, 2, 3, 4, 5, 6, 7, 8, 16
 # CADRE_LAG_*: the cost-constraint state block (float64; LAG_STRIDE doubles per head)
 LAG_LAMBDA, LAG_BUDGET, LAG_LR, LAG_MAX, LAG_J, LAG_SHARE, LAG_UPDATES, LAG_STRIDE = 0, 1, 2, 3, 4, 5, 6, 8
+# CADRE_EMA_*: the weight-average state block (float64; dist2 [n_models] from EMA_HEAD on), the workgroups per model and the head
+# of the scratch `work` (float64 [EMA_WORK_HEAD + n_models * EMA_GRID]), the bounds of n_models and of cadre_arena_mean's K
+EMA_DECAY, EMA_WARMUP, EMA_COUNT, EMA_D, EMA_SKIPPED, EMA_HEAD = 0, 1, 2, 3, 4, 8
+EMA_GRID, EMA_WORK_HEAD, EMA_MAX_MODELS, MEAN_MAX_SOURCES = 256, 2, 4096, 64
 RS_SCALE, RS_CARRY = 6, 8 # CADRE_RS_SCALE / CADRE_RS_CARRY: the return-statistics block (count, mean, M2 per head first)
 
 CAPTURE_MAX_RANGES = 65535        # CADRE_CAPTURE_MAX_RANGES

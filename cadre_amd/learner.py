@@ -207,7 +207,28 @@ class PPOLearnerHIP:
         self._smooth_tables = None  # (ctrl: device float32 [2][64], (scale_steer, scale_throttle)); the address is part of the graph keys
         # "ppo+mask": cadre_ppo_am_loss — the PPO loss under the rows' allowed-bin words (workspace(B)["allowed"])
         self._last_am_stats = None  # workspace(B)["am_stats"] of the "ppo+mask" update that ran last
+        # weight averaging (opt-in, set_weight_average): clip_adam() issues the average's update behind the optimiser launches
+        self._avg = None           # a cadre_amd.average.WeightAverage of this arena; part of the optimiser graphs' keys
+        self._avg_swapped = False  # inside CadreAgent.averaged_weights(): the arena holds the average, nothing may step it
         hip.lib()
+
+    # ------------------------------------------------------------------ weight averaging
+    def set_weight_average(self, avg):
+        """avg: a cadre_amd.average.WeightAverage of this learner's arena, or None.  While one is set clip_adam() issues
+        cadre_ema_update directly behind the optimiser launches, in the same captured graph (the key gains one element; with
+        none set the key and the body are what they are without the module), and passes the gate's flag exactly when the gated
+        optimiser twin is used: a skipped step is skipped — and counted — there too.  Every in-process path that steps the
+        arena goes through clip_adam(); clip_adam_sharded() refuses an average."""
+        if avg is not None and avg.arena is not self.a:
+            raise hip.CadreHipError("set_weight_average: the average was built for another arena")
+        if self._avg_swapped:
+            raise hip.CadreHipError("set_weight_average inside averaged_weights(): the arena holds the average")
+        self._avg = avg
+
+    def _check_not_swapped(self, what):
+        if self._avg_swapped:
+            raise hip.CadreHipError("%s inside averaged_weights(): the arena holds the average, not the parameters the optimiser "
+                                    "state belongs to" % what)
 
     # ------------------------------------------------------------------ loss selection
     def set_loss(self, mode, label_smoothing=0.0, bc_coeff=1.0, demo_coeff=None, demo_value_coeff=None, beta_clone=1.0,
@@ -1079,6 +1100,7 @@ class PPOLearnerHIP:
         [2][>= hip.BC_STATS_FIELDS]) receives the imitation statistics of the demonstration rows; `stats_row` keeps its
         meaning there (the diagnostics of the PPO rows)."""
         a = self.a
+        self._check_not_swapped("update")
         m = LOSS_MODES[self.loss_mode]
         if demo_stats_row is not None and self.loss_mode != "ppo+demo":
             raise hip.CadreHipError("update(demo_stats_row=...) needs set_loss('ppo+demo')")
@@ -1290,6 +1312,7 @@ class PPOLearnerHIP:
         """Three launches (prep, per-model square norms, Adam) with the step count in device memory,
         captured into a hipGraph per hyper-parameter set."""
         a = self.a
+        self._check_not_swapped("clip_adam")
         a.ensure_adam()
         a.step += 1                 # (with the KL gate armed: steps attempted — the learner section reconciles it at its sync)
         fused = self.fused_pack
@@ -1301,6 +1324,9 @@ class PPOLearnerHIP:
             key = ("adam", "hp", b1, b2, eps, fused) + (("gated",) if gated else ())
         else:
             key = ("adam", float(lr), float(max_grad_norm), b1, b2, eps, fused) + (("gated",) if gated else ())
+        avg = self._avg
+        if avg is not None:         # (the average's buffers are baked into the graph: their addresses are the key's one more element)
+            key = key + (("ema", avg.ema.data_ptr(), avg.state.data_ptr(), avg.work.data_ptr()),)
         if fused:
             self._alloc_wp()
 
@@ -1315,6 +1341,8 @@ class PPOLearnerHIP:
             tail = ((hip.ptr(self._stop),) if gated else ()) + (hip.stream(),)
             name = "cadre_clip_adam_%sgraph%s%s" % ("pack_" if fused else "", "_hp" if hp else "", "_gated" if gated else "")
             hip.check(getattr(L, name)(*(head + pack + tail)), name)
+            if avg is not None:     # cadre_ema_update behind the step, under the same flag as the gated twin
+                avg.update(stop=self._stop if gated else None)
 
         def done():
             self._adam_fresh = self._pkey() if fused else None      # (the copies now match the stepped parameters)
@@ -1343,6 +1371,10 @@ class PPOLearnerHIP:
         `all_reduce_norms(norms2[:n_models])` (SUM of 16 doubles over the ranks) -> clip + Adam on the shard.
         The Adam moments exist for the shard only (1/N of the state and of the pass's HBM traffic)."""
         a = self.a
+        self._check_not_swapped("clip_adam_sharded")
+        if self._avg is not None:
+            raise hip.CadreHipError("a weight average is not available for the sharded optimiser step: it steps one shard of the "
+                                    "arena per rank (set_weight_average(None), or the all-reduce exchange)")
         if self.consensus:
             raise hip.CadreHipError("rank consensus is not available for the sharded optimiser step: it has no gated form "
                                     "(use the all-reduce exchange)")

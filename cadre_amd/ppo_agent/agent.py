@@ -569,6 +569,7 @@ class CadreAgent(object):
         B = steer_samples[1].shape[0]
         if throttle_samples[1].shape[0] != B:
             raise ValueError("steer/throttle minibatches differ in size")
+        self.learner._check_not_swapped("update_policy")
         w = self.learner.workspace(B)
         self._pack(w, 0, steer_samples)
         self._pack(w, 1, throttle_samples)
@@ -685,6 +686,7 @@ class CadreAgent(object):
 
     def _update_from_storages(self, batches, sync, mlp_grads_ready, stats_row, evaluate, demo_stats_row=None, record=None):
         nW = len(batches)
+        self.learner._check_not_swapped("update_policy_from_storages")
         mode = LOSS_MODES[self.learner.loss_mode]
         if (record is None and not evaluate and mode.ppo and not mode.reads_allowed
                 and any(getattr(b[k], "allowed", None) is not None for b in batches for k in (0, 3))):
@@ -998,9 +1000,26 @@ class CadreAgent(object):
         return ensemble_act_batch(agent_group, obs_list, shifted=shifted, deterministic=deterministic, allowed=allowed)
 
     # ------------------------------------------------------------------ snapshots
-    def save_snapshot(self, model_path, fix_missing_lstm=False):
+    def averaged_weights(self):
+        """Context manager: inside it the arena holds the weight average set on the learner (cadre_amd.average.WeightAverage,
+        learner.set_weight_average).  On entry ONE cadre_arena_swap puts the average where the parameters live — captured graphs
+        hold addresses, so the contents move, not the pointers —, arena.params._version is bumped by an in-place no-op (as
+        load_snapshot does) and the learner's packed recurrent weights are forgotten.  act, act_batch, get_value,
+        ensemble_act_batch and save_snapshot work inside; update_policy*, clip_adam* and a nested entry raise CadreHipError.  On
+        exit the swap is undone and the same caches are dropped, also when the body raises."""
+        from ..average import averaged_weights
+        return averaged_weights(self)
+
+    def save_snapshot(self, model_path, fix_missing_lstm=False, weights="live"):
         """agent.py:245-260: pickled nn.Modules keyed by model name.  The reference writes
-        steer_ppo twice and never throttle_lstm; `fix_missing_lstm=True` adds it."""
+        steer_ppo twice and never throttle_lstm; `fix_missing_lstm=True` adds it.
+        weights: "live" (the arena as it is), or "average": averaged_weights() is held around the same body, so the file has
+        the reference's format unchanged and holds the weight average (CadreHipError when none is set)."""
+        if weights not in ("live", "average"):
+            raise ValueError("save_snapshot: weights=%r (\"live\" or \"average\")" % (weights,))
+        if weights == "average" and not self.learner._avg_swapped:
+            with self.averaged_weights():
+                return self.save_snapshot(model_path, fix_missing_lstm)
         out = {}
         kinds = ["throttle_ppo_", "steer_ppo_", "steer_lstm_"] + (["throttle_lstm_"] if fix_missing_lstm else [])
         for c in range(self.command_num):

@@ -563,6 +563,45 @@ def _constraint_stats(stats, con):
         stats["constraint"] = con.summary()
 
 
+def weight_average_config(train_cfg, shared_grad_buffers=None, in_process_chief=True, agent=None):
+    """train_cfg["weight_average"] (absent / None: None — nothing is built, launched or changed): the key's dict with defaults
+    (cadre_amd.average.average_config) after its refusals (average_refusals), before anything is allocated.  With `agent`, one
+    more ValueError naming the key: shared nets in another parameter arena than the agent's (the optimiser then steps that
+    arena, and the average would follow nothing)."""
+    cfg = _get(train_cfg, "weight_average")
+    if cfg is None:
+        return None
+    from ..average import average_config, average_refusals
+    cfg = average_config(cfg)
+    average_refusals(shared_grad_buffers=shared_grad_buffers, in_process_chief=in_process_chief)
+    if agent is not None and shared_grad_buffers is not None and getattr(shared_grad_buffers, "arena", agent.arena) is not agent.arena:
+        raise ValueError("train_cfg.weight_average: the shared nets live in another parameter arena than the agent's; the average "
+                         "follows the optimiser steps of the agent's own arena")       # (the optimiser steps THAT arena: as for aux_phase)
+    return cfg
+
+
+def weight_average(agent, cfg):
+    """The WeightAverage of a run (cfg: what weight_average_config returned; None: None), set on the agent's learner: from here
+    on every in-process optimiser step is followed by the average's update."""
+    if cfg is None:
+        return None
+    from ..average import average_runner
+    avg = average_runner(agent, cfg)
+    agent.learner.set_weight_average(avg)
+    return avg
+
+
+def _average_snapshot(agent, avg, model_dir, episode):
+    if avg is not None and avg.snapshot:
+        agent.save_snapshot(os.path.join(model_dir, "ppo_model_{}_avg.pt".format(episode)), weights="average")
+
+
+def _average_stats(stats, agent):
+    avg = getattr(agent.learner, "_avg", None)
+    if stats is not None and avg is not None:
+        stats["weight_average"] = avg.summary()
+
+
 def _cost_kw(con, info, head=None):
     """Keyword arguments of insert (head 0 / 1) for the step's info["cost"] ({} without the module: today's call)."""
     if con is None:
@@ -831,6 +870,9 @@ def stats_line(episode, stats):
     if "constraint" in stats:                          # cost constraint: cost rate, multiplier, the two advantage terms
         from ..constraint import constraint_stats_text
         line += constraint_stats_text(stats)
+    if "weight_average" in stats:                      # weight averaging: updates, the decay used, parameter-to-average distance
+        from ..average import average_stats_text
+        line += average_stats_text(stats)
     return line
 
 
@@ -940,6 +982,7 @@ def learner_section(agent, steer_rollout, throttle_rollout, done, train_cfg, sha
         _smooth_stats(stats, smooth)
         _curiosity_stats(stats, curiosity)
         _constraint_stats(stats, constraint)
+        _average_stats(stats, agent)
         return out
     dev_losses, (vl, pl, el) = out
     host = sec.finish(stats, tkl is not None, losses=torch.stack(dev_losses) if dev_losses else None)
@@ -951,6 +994,7 @@ def learner_section(agent, steer_rollout, throttle_rollout, done, train_cfg, sha
     _smooth_stats(stats, smooth)
     _curiosity_stats(stats, curiosity)
     _constraint_stats(stats, constraint)
+    _average_stats(stats, agent)
     if host is not None:
         for v, p, e in host.tolist():
             vl.append(v); pl.append(p); el.append(e)
@@ -1091,15 +1135,19 @@ def train(rank, train_cfg, agent_cfg, env_cfg, rollout_cfg, traffic_light=None, 
     # (refusals first: before a checkpoint is read or anything else is built)
     cur = agent.curiosity = curiosity(agent, train_cfg, 1, shared_grad_buffers, True, ck_interval, ck_resume)
     con = agent.constraint = cost_constraint(agent, train_cfg, 1, shared_grad_buffers, True, ck_interval, ck_resume)
-    ck, first_episode = None, 0
+    avg_cfg = weight_average_config(train_cfg, shared_grad_buffers, traffic_light is None, agent)
+    ck, first_episode, avg = None, 0, None
     if ck_interval is not None or ck_resume is not None:
         ck = _Checkpointer(env.work_dir, ck_interval, agent, [(steer_rollout, throttle_rollout)])
         if ck_resume is not None:                # (the environment is the caller's: it restarts through reset())
+            avg = weight_average(agent, avg_cfg)      # (before the restore, which fills it; no warm start runs)
             first_episode = ck.resume(ck_resume)
     suggest = suggestions(agent, train_cfg, True, ck_interval, ck_resume)      # (refusals first: before anything is loaded)
     actmask = action_masks(agent, train_cfg, True, ck_interval, ck_resume)
     demo = demo_mixer(agent, train_cfg, rollout_cfg, rank)          # (before the warm start, which shares its DemoSet)
     _pretrain(agent, train_cfg, rollout_cfg, shared_grad_buffers, rank, logger, ck_resume, shared_model_list, traffic_light)
+    if ck_resume is None:                        # (behind the warm start: the average starts from its result)
+        avg = weight_average(agent, avg_cfg)
     aux = _aux_runner(agent, train_cfg, shared_grad_buffers, rank, traffic_light is None, ck_interval, first_episode,
                       shared_model_list)
     reuse = _reuse_runner(agent, train_cfg, shared_grad_buffers, rank, traffic_light is None, ck_interval, ck_resume,
@@ -1174,6 +1222,7 @@ def train(rank, train_cfg, agent_cfg, env_cfg, rollout_cfg, traffic_light=None, 
                     logger.log(aux_stats_line(episode, aux_records))
         if episode % train_cfg.save_interval == 0 and rank == 0:
             agent.save_snapshot(os.path.join(model_dir, "ppo_model_{}.pt".format(episode)))
+            _average_snapshot(agent, avg, model_dir, episode)
         if ck is not None:                       # (after the snapshot: building its nn.Modules draws from the generator)
             ck.after_episode(episode)
     if ck is not None:
@@ -1331,6 +1380,7 @@ def learner_section_multi(agent, rollouts, dones, train_cfg, shared_grad_buffers
         _smooth_stats(stats, smooth)
         _curiosity_stats(stats, curiosity)
         _constraint_stats(stats, constraint)
+        _average_stats(stats, agent)
         return tuple(list(c) for c in zip(*host.tolist()))
     if sec is not None:
         sec.finish(stats, tkl is not None)
@@ -1342,6 +1392,7 @@ def learner_section_multi(agent, rollouts, dones, train_cfg, shared_grad_buffers
         _smooth_stats(stats, smooth)
         _curiosity_stats(stats, curiosity)
         _constraint_stats(stats, constraint)
+        _average_stats(stats, agent)
     if losses_on_device:
         return losses
     vl, pl, el = [], [], []
@@ -1414,15 +1465,19 @@ def train_vec(rank, train_cfg, agent_cfg, env_cfg, rollout_cfg, num_envs, env_cl
     # (refusals first: before a checkpoint is read or anything else is built)
     cur = agent.curiosity = curiosity(agent, train_cfg, num_envs, shared_grad_buffers, True, ck_interval, ck_resume)
     con = agent.constraint = cost_constraint(agent, train_cfg, num_envs, shared_grad_buffers, True, ck_interval, ck_resume)
-    ck, first_episode = None, 0
+    avg_cfg = weight_average_config(train_cfg, shared_grad_buffers, True, agent)
+    ck, first_episode, avg = None, 0, None
     if ck_interval is not None or ck_resume is not None:
         ck = _Checkpointer(envs[0].work_dir, ck_interval, agent, rollouts, callback)
         if ck_resume is not None:                # (the environments are the caller's: they restart through reset())
+            avg = weight_average(agent, avg_cfg)      # (before the restore, which fills it; no warm start runs)
             first_episode = ck.resume(ck_resume)
     suggest = suggestions(agent, train_cfg, True, ck_interval, ck_resume)      # (refusals first: before anything is loaded)
     actmask = action_masks(agent, train_cfg, True, ck_interval, ck_resume)
     demo = demo_mixer(agent, train_cfg, rollout_cfg, rank)          # (before the warm start, which shares its DemoSet)
     _pretrain(agent, train_cfg, rollout_cfg, shared_grad_buffers, rank, logger, ck_resume)
+    if ck_resume is None:                        # (behind the warm start: the average starts from its result)
+        avg = weight_average(agent, avg_cfg)
     aux = _aux_runner(agent, train_cfg, shared_grad_buffers, rank, True, ck_interval, first_episode)
     reuse = _reuse_runner(agent, train_cfg, shared_grad_buffers, rank, True, ck_interval, ck_resume)
     sil = self_imitation(agent, train_cfg, shared_grad_buffers, rank, True, True, ck_interval, ck_resume)
@@ -1498,6 +1553,7 @@ def train_vec(rank, train_cfg, agent_cfg, env_cfg, rollout_cfg, num_envs, env_cl
                     logger.log(aux_stats_line(episode, aux_records))
         if episode % train_cfg.save_interval == 0 and rank == 0:
             agent.save_snapshot(os.path.join(model_dir, "ppo_model_{}.pt".format(episode)))
+            _average_snapshot(agent, avg, model_dir, episode)
         if ck is not None:                       # (after the snapshot: building its nn.Modules draws from the generator)
             ck.after_episode(episode)
         if callback is not None:

@@ -1379,6 +1379,55 @@ int cadre_cost_backward(const void* obs_table, int32_t n, int32_t Tr, int32_t S,
 int cadre_cost_lambda(const void* cost_table, int32_t N, int32_t T, double* state, int32_t update, void* stream);
 int cadre_lag_mix(const void* row_table, int32_t n, int32_t T, const double* state, double* diag, void* stream);
 
+/* ---------------------------------------------------------------- weight averaging (csrc/average.hip)
+ * Polyak / exponential moving average of a flat parameter buffer behind an optimiser step, the exchange of two flat buffers and
+ * the weighted mean of K of them.  Plain HBM streams: 16-byte loads and stores on the aligned body of a range, single words
+ * before and behind it; every store is a plain vector store and there is no atomic.
+ *
+ * State block of the average, float64 [CADRE_EMA_HEAD + n_models]: [CADRE_EMA_DECAY] the configured decay, [CADRE_EMA_WARMUP]
+ * 0 or 1, [CADRE_EMA_COUNT] updates applied so far, [CADRE_EMA_D] the decay the last applied update used,
+ * [CADRE_EMA_SKIPPED] updates skipped by the gate, the rest up to CADRE_EMA_HEAD reserved; then dist2[n_models], the
+ * per-model squared distance after the last applied update.
+ *
+ * cadre_ema_update: params / ema float32 (any 4-byte alignment, not overlapping), seg_off int64 [n_models + 1], any
+ * non-decreasing table of element offsets into both (model m = elements [seg_off[m], seg_off[m + 1])), 0 <= n_models <=
+ * CADRE_EMA_MAX_MODELS; state as above (8-byte aligned); work float64 [CADRE_EMA_WORK_HEAD + n_models * CADRE_EMA_GRID]
+ * scratch (8-byte aligned, need not be cleared); stop NULL or the device flag of cadre_ppo_loss_stats that
+ * cadre_clip_adam_graph_gated reads.  With stop != NULL and *stop != 0 nothing is written except state[CADRE_EMA_SKIPPED] += 1
+ * (and scratch).  Otherwise, with n = state[CADRE_EMA_COUNT] and d = state[CADRE_EMA_DECAY] — with warm-up d = min(d,
+ * (1 + n) / (10 + n)) in double, the num_updates rule, so that the initial copy fades fast — and om = (float)(1.0 - d), every
+ * element i of [seg_off[0], seg_off[n_models]):  t = p[i] - e[i] rounded to fp32;  e[i] = fmaf(om, t, e[i])  (the lerp form:
+ * p == e leaves e bit for bit, t == 0 keeps the bits of e outright);  dist2[m] = sum over model m of ((double)p[i] -
+ * (double)e_new[i])^2, each term rounded as written, summed in a fixed order (per lane, wave, workgroup into `work`, then the
+ * CADRE_EMA_GRID partials of a model by the finishing launch): two runs over equal bytes give equal bits.  Then state[CADRE_EMA_D]
+ * = d and state[CADRE_EMA_COUNT] = n + 1.  Three launches (preparation: gate and decay into `work`, read by every workgroup of
+ * the pass before the count moves; the pass; the finish), no host sync: hipGraph-capturable.  Nothing outside [seg_off[0],
+ * seg_off[n_models]) of ema is touched; params is only read.
+ *
+ * cadre_arena_swap: exchanges a[0 .. n) and b[0 .. n) (float32, any 4-byte alignment of either side, n >= 0) in one pass, one
+ * launch.  Overlapping ranges are refused.
+ *
+ * cadre_arena_mean: src_table device int64 [K] (the addresses of K float32 buffers of n elements, 4-byte aligned), weights
+ * device float64 [K], 1 <= K <= CADRE_MEAN_MAX_SOURCES; out[i] = (float)sum_k weights[k] (double)src_k[i], accumulated in
+ * double in the order k = 0 .. K - 1 with one fma per term (the first onto -0.0: the rounded product itself, so K = 1 with
+ * weight 1 copies the bits).  One launch.  out (any 4-byte alignment) may BE one of the sources — a thread reads all K values of
+ * its elements before it writes them — but may not overlap one at another offset.
+ * Refused before any launch, with a message: null operands, n_models / K / n outside the above, misaligned operands. */
+#define CADRE_EMA_DECAY 0
+#define CADRE_EMA_WARMUP 1
+#define CADRE_EMA_COUNT 2
+#define CADRE_EMA_D 3
+#define CADRE_EMA_SKIPPED 4
+#define CADRE_EMA_HEAD 8
+#define CADRE_EMA_GRID 256
+#define CADRE_EMA_WORK_HEAD 2
+#define CADRE_EMA_MAX_MODELS 4096
+#define CADRE_MEAN_MAX_SOURCES 64
+int cadre_ema_update(const float* params, float* ema, const int64_t* seg_off, int32_t n_models, double* state, double* work,
+                     const int32_t* stop, void* stream);
+int cadre_arena_swap(float* a, float* b, int64_t n, void* stream);
+int cadre_arena_mean(const int64_t* src_table, const double* weights, int32_t K, float* out, int64_t n, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
